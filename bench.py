@@ -16,20 +16,24 @@ Other workloads (parity-test configs, measured for DESIGN.md; 2^16 instances per
     --workload mixed           the config-5 opcode mix at --gates opcodes (every kernel class in one circuit)
     --workload config5         config 5 at circuit size: the 10^6-opcode mixed circuit (--gates), tiles of --tile-log2 (default 2^12) instances,
                                --total-log2 (default 2^14) per GPU; a step = solve + per-instance map digest of every tile (what config 5 keeps)
-The default run (N = 1) also appends `other_workloads`: legs of arith_pedersen (the north-star target shape, at the metric's batch: 2^20 in
-tiles), hash, grumpkin and ecdsa, each parity-checked against the oracle and carrying its own roofline / alu_roofline (--no-legs skips
-them), then the same legs once more as the compact `legs`, and `summary` as the last key of the line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1 without a launcher: spawns the N ranks itself
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N > 1 without a launcher: spawns the N ranks itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-One process per GPU. Rank 0 prints ONE JSON line: whole-job witnesses/s (max-over-ranks time), per-rank rates, the digest of
-digests over the per-instance witness-map digests of ALL ranks (identical for every N and tile size: the ranks provably solved
-disjoint shards of one batch), `roofline` of the dominant kernel (algorithmic bytes of its launches / their HIP-event durations,
-events on the batch's own streams; HBM traffic from in-run rocprofv3 PMC passes on rank 0's device), `end_to_end` (H2D of the inputs +
-solve + D2H of the return witnesses), and `cpu_baseline` (the CPU oracle -- a port of the reference's in-order solver -- timed on every
-host core on a bounded sample of the same workload, which is also the bit-exact parity check of the run; variants of BASELINE.md
-section 2). Rank 0 computes `cpu_baseline`, `parity` and `roofline.traffic` for EVERY world size, after the timed region and the last barrier.
+One process per GPU. Rank 0 prints ONE JSON line. A plain run sets up (workload, resident inputs, batch handle), warms up, times the K
+steps and prints the headline: whole-job witnesses/s (max-over-ranks time), `ms_per_step`, per-rank rates and the configuration.
+--dump-outputs DIR: after the timed steps rank 0 writes what the last step computed (its last tile) as DIR/<name>.npy (dump_outputs).
+
+--full adds everything else, after the timed region: the digest of digests over the per-instance witness-map digests of ALL ranks
+(identical for every N and tile size: the ranks provably solved disjoint shards of one batch), `roofline` of the dominant kernel
+(algorithmic bytes of its launches / their HIP-event durations, events on the batch's own streams; HBM traffic from in-run rocprofv3 PMC
+passes on rank 0's device), `end_to_end` (H2D of the inputs + solve + D2H of the return witnesses), and `cpu_baseline` (the CPU oracle --
+a port of the reference's in-order solver -- timed on every host core on a bounded sample of the same workload, which is also the
+bit-exact parity check of the run; variants of BASELINE.md section 2). Rank 0 computes `cpu_baseline`, `parity` and `roofline.traffic` for
+EVERY world size, after the timed region and the last barrier. A --full run of the default workload (N = 1) also appends
+`other_workloads`: legs of arith_pedersen (the north-star target shape, at the metric's batch: 2^20 in tiles), hash, grumpkin, ecdsa and
+config 5, each parity-checked against the oracle and carrying its own roofline / alu_roofline (--no-legs skips them), then the same legs
+once more as the compact `legs`, and `summary` as the last key of the line. The --no-* options trim a --full run.
 """
 import argparse
 import json
@@ -633,11 +637,59 @@ def end_to_end_node(gc, ids, values, total, tile, n_dev_rank):
                     "diverging instances re-solved beside the next tile); `value` of the line keeps inputs resident"}
 
 
+DUMP_SEED = 0xD0D0  # the fixed sample of --dump-outputs: the same instances and witnesses in every run with the same arguments
+
+
+def dump_outputs(out_dir, sh, first, initial_ids, ret, last_digest=None, n_inst=512, n_wit=256, max_rows=1 << 18):
+    """--dump-outputs: what the timed path computed in its last step -- the last tile, still in the batch handle -- as float64 .npy files
+    (at most about 40 MB). A field element is 8 uint32 words, most significant first. After acvm_batch_solve_then_import the table's initial
+    witnesses already hold the next tile's inputs, so only results and non-initial witnesses are read (what the library lets a caller read then).
+        instances.npy        [R]             global instance index of every instance of the last tile (R = tile; a fixed, seeded sample of
+                                             max_rows of them for larger tiles)
+        results.npy          [R, 5]          their results: status, error, opcode index, aux0, aux1
+        sample_instances.npy [S]             a fixed, seeded sample of the tile's instances (global indices)
+        sample_witnesses.npy [W]             the return witnesses + a fixed, seeded sample of the other non-initial witnesses
+        witness_values.npy   [S, W, 8]       their values (0 where unassigned)
+        witness_assigned.npy [S, W]          1 where assigned
+        witness_map_digests.npy [R, 8]       config 5 only: the per-instance map digests its step computed"""
+    import numpy as np
+    batch, tile = sh.batch, sh.tile
+    base = first + sh.starts[-1]
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick_i = np.sort(rng.choice(tile, size=min(n_inst, tile), replace=False))
+    rows = np.arange(tile) if tile <= max_rows else np.sort(rng.choice(tile, size=max_rows, replace=False))
+    res = batch.results()
+    out = {"instances": (base + rows).astype(np.float64),
+           "results": np.array([res[j].as_tuple() for j in rows], dtype=np.float64).reshape(len(rows), 5)}
+    ret = [w for w in ret if w not in set(initial_ids)]
+    skip = set(initial_ids) | set(ret)
+    others = np.array([w for w in range(batch.nw) if w not in skip], dtype=np.int64)
+    extra = rng.choice(others, size=min(max(n_wit - len(ret), 0), len(others)), replace=False) if len(others) else others
+    pick_w = sorted(set(ret) | set(int(w) for w in extra))
+    vals = np.zeros((len(pick_i), len(pick_w), 8), dtype=np.float64)
+    asg = np.zeros((len(pick_i), len(pick_w)), dtype=np.float64)
+    for k, w in enumerate(pick_w):
+        v, a = batch.witness(w)
+        vals[:, k] = np.ascontiguousarray(v[pick_i]).view(">u4").reshape(len(pick_i), 8)
+        asg[:, k] = a[pick_i]
+    out.update(sample_instances=(base + pick_i).astype(np.float64), sample_witnesses=np.array(pick_w, dtype=np.float64),
+               witness_values=vals, witness_assigned=asg)
+    if last_digest is not None:
+        out["witness_map_digests"] = np.ascontiguousarray(last_digest[rows]).view(">u4").reshape(len(rows), 8).astype(np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return sum(a.nbytes for a in out.values())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)  # the device reaches its clocks after about two solves (profiles/README.md)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: digest of digests, rooflines and PMC passes, end to end, CPU baselines "
+                                                        "and parity, the other workloads' legs (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (its last tile) to DIR/<name>.npy")
     ap.add_argument("--workload", default="arith", choices=["arith", "hash", "grumpkin", "ecdsa", "arith_pedersen", "mixed", "config5"])
     ap.add_argument("--gates", type=int, default=None, help="opcodes of the synthetic circuit (default 10000; 1000000 for config5)")
     ap.add_argument("--pedersen", type=int, default=8)
@@ -647,11 +699,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-digest", action="store_true", help="skip the digest-of-digests pass")
     ap.add_argument("--no-end-to-end", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the other_workloads legs of the default run")
+    ap.add_argument("--no-legs", action="store_true", help="skip the other_workloads legs of a --full run")
     ap.add_argument("--no-pipeline", action="store_true", help="plain acvm_batch_solve per tile instead of acvm_batch_solve_then_import (A/B of the tile boundary)")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)  # the one-tile run the PMC passes profile
     ap.add_argument("--inner-config5-leg", action="store_true", help=argparse.SUPPRESS)  # the config-5 leg's sequence of tiles, for its PMC pass
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.inner_config5_leg:
         import acvm_amd
         acvm_amd.set_device(0)
@@ -707,7 +761,9 @@ def main():
         shard.barrier(dist)
         acvm_amd.synchronize()
 
-    batch.set_profiling(True)  # warm-up with per-launch events, so that the event pool exists before the timed region
+    # per-launch HIP events feed the roofline figures only: a plain run (the headline) has none, a --full run (and the profiled --inner run) keeps them
+    events = args.full or args.inner
+    batch.set_profiling(events)  # warm-up with per-launch events, so that the event pool exists before the timed region
     for _ in range(args.warmup):
         sh.solve_pass()
     if config5 and args.warmup:
@@ -717,16 +773,17 @@ def main():
     dev_ms = 0.0
     n_failed = 0
     digest_ms = 0.0
+    last_digest = None
     # (the sampler forks rocm-smi every 50 ms: harmless beside the 190 ms steps of the gate kernel, whose VALU issue fraction needs the clock,
     # but it would disturb the sub-millisecond steps of the hash / Grumpkin workloads, and N ranks of it would disturb each other: it runs
-    # where its value is used -- rank 0 of a one-rank run of the gate workloads)
-    with ClockSampler(acvm_amd.current_device(), enabled=rank == 0 and world == 1 and args.workload in ("arith", "config5")) as clock:
+    # where its value is used -- rank 0 of a one-rank --full run of the gate workloads)
+    with ClockSampler(acvm_amd.current_device(), enabled=args.full and rank == 0 and world == 1 and args.workload in ("arith", "config5")) as clock:
         t0 = time.perf_counter()
         for i in range(args.steps):
             for k in range(n_tiles):
                 # per-launch HIP events (two per launch) cost 3 % of a solve: they bracket the launches of the LAST tile of the LAST step only
                 last = i == args.steps - 1 and k == n_tiles - 1
-                if last:
+                if last and events:
                     batch.set_profiling(True)
                 # the same step for every N and every tile count: ACVM::new of the tile (import of its resident inputs into the reused table),
                 # then ACVM::solve
@@ -737,7 +794,7 @@ def main():
                     dev_ms += batch.stats()["solve_device_ms"]
                 if config5:  # what config 5 keeps of a tile: the per-instance digest of the map (the return witness rides along)
                     d0 = time.perf_counter()
-                    batch.digest(0, tile)
+                    last_digest = batch.digest(0, tile)
                     digest_ms += (time.perf_counter() - d0) * 1e3
         acvm_amd.synchronize()
         my_elapsed = time.perf_counter() - t0
@@ -750,6 +807,47 @@ def main():
     if args.inner:  # the profiled one-tile run: nothing to report; the modmul probe runs so that the PMC passes see it
         acvm_amd.modmul_rate(100, 8)
         sh.free()
+        return
+
+    # ---- what the last step computed, before anything below solves a tile again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, sh, first, ids, gc.witness_set("return_values"), last_digest)
+
+    line = {
+        "metric": "witnesses solved/sec (whole node)",
+        "value": total * args.steps / elapsed,
+        "unit": "witnesses/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u256 (8x u32 limbs, BN254-Fr Montgomery)",
+        "data": "synthetic",
+        "full": args.full,
+        "config": {"workload": f"{workload_name}, batch 2^{total.bit_length() - 1} witnesses over {world} GPU(s)", "opcodes": st["n_opcodes"],
+                   "global_batch": total, "instances_per_gpu": n_rank, "tile_instances": tile, "tiles_per_gpu_per_step": n_tiles, "levels": st["n_levels"],
+                   "step": "per tile: import of the resident inputs (ACVM::new) + solve, the same for every N"
+                           + ("" if config5 or args.no_pipeline else "; the next tile's import is enqueued behind the solve (acvm_batch_solve_then_import)"),
+                   "not_solved_rank0_all_steps": n_failed, "slow_path_instances_last_tile": st["n_slow_instances"],
+                   "algorithmic_bytes_per_witness": st["algorithmic_bytes_per_instance"], "brillig_opcodes_inlined": st["n_brillig_inlined"],
+                   "device_ms_per_step_rank0": dev_ms, "inputs_resident_setup_s_rank0": round(h2d_resident_s, 3), "host_cores": os.cpu_count(),
+                   "parallelism": f"instances sharded x{world}, no collectives"},
+        "per_rank_witnesses_per_s": rank_rates,
+    }
+    if config5:
+        line["config"]["digest_ms_per_step_rank0"] = digest_ms / args.steps
+    if dumped is not None:
+        line["outputs_dumped"] = {"dir": args.dump_outputs, "bytes": dumped, "tile_first_instance": first + sh.starts[-1]}
+    if not args.full:  # a plain run: the headline and nothing else
+        sh.free()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
         return
 
     # ---- digest of digests: every rank hashes the witness maps of its shard (one more pass, untimed), rank 0 combines
@@ -797,7 +895,7 @@ def main():
     if sh is not None:
         sh.free()
 
-    value = total * args.steps / elapsed
+    value = line["value"]
     roof, alu = roofline_block(args, st, tile, world, clock.median())
     if not os.environ.get("ACVM_BENCH_NO_PMC"):
         try:
@@ -825,37 +923,7 @@ def main():
             legs["config5"] = run_config5_leg()
         except (acvm_amd.AcvmError, OSError, ValueError, MemoryError) as e:
             legs["config5"] = {"error": str(e)[:300]}
-    line = {
-        "metric": "witnesses solved/sec (whole node)",
-        "value": value,
-        "unit": "witnesses/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "u256 (8x u32 limbs, BN254-Fr Montgomery)",
-        "data": "synthetic",
-        "config": {"workload": f"{workload_name}, batch 2^{total.bit_length() - 1} witnesses over {world} GPU(s)", "opcodes": st["n_opcodes"],
-                   "global_batch": total, "instances_per_gpu": n_rank, "tile_instances": tile, "tiles_per_gpu_per_step": n_tiles, "levels": st["n_levels"],
-                   "step": "per tile: import of the resident inputs (ACVM::new) + solve, the same for every N"
-                           + ("" if config5 or args.no_pipeline else "; the next tile's import is enqueued behind the solve (acvm_batch_solve_then_import)"),
-                   "not_solved_rank0_all_steps": n_failed, "slow_path_instances_last_tile": st["n_slow_instances"],
-                   "algorithmic_bytes_per_witness": st["algorithmic_bytes_per_instance"], "brillig_opcodes_inlined": st["n_brillig_inlined"],
-                   "device_ms_per_step_rank0": dev_ms, "inputs_resident_setup_s_rank0": round(h2d_resident_s, 3), "host_cores": os.cpu_count(),
-                   "parallelism": f"instances sharded x{world}, no collectives"},
-        "per_rank_witnesses_per_s": rank_rates,
-        "digest_of_digests": dod,
-        "roofline": roof,
-        "alu_roofline": alu,
-        "end_to_end": e2e,
-        "cpu_baseline": cpu,
-        "parity": parity,
-    }
-    if config5:
-        line["config"]["digest_ms_per_step_rank0"] = digest_ms / args.steps
+    line.update(digest_of_digests=dod, roofline=roof, alu_roofline=alu, end_to_end=e2e, cpu_baseline=cpu, parity=parity)
     if legs is not None:
         line["other_workloads"] = legs
         # the same legs once more, compact, at the END of the line (a reader that keeps only the tail still sees them):

@@ -11,6 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--gates", "400", "--total-log2", "13", "--tile-log2", "11", "--steps", "1", "--warmup", "0", "--no-end-to-end"]
+FULL = ARGS + ["--full"]  # digest of digests, parity, cpu_baseline and roofline are --full's
 
 
 def run(cmd, **env):
@@ -26,9 +27,9 @@ def last_json(out):
 
 
 def test_two_ranks_equal_one_batch():
-    one = last_json(run([sys.executable, "bench.py", "--gpus", "1"] + ARGS))
+    one = last_json(run([sys.executable, "bench.py", "--gpus", "1"] + FULL))
     two = last_json(run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                         "--master-port", "29547", "bench.py", "--gpus", "2"] + ARGS, ACVM_BENCH_SHARE_GPU="1"))
+                         "--master-port", "29547", "bench.py", "--gpus", "2"] + FULL, ACVM_BENCH_SHARE_GPU="1"))
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     assert one["parity"]["bit_exact"] and one["parity"]["digests_checked"] > 0
     assert two["parity"]["bit_exact"] and two["cpu_baseline"]["value"] > 0  # rank 0 reports them for every world size
@@ -45,7 +46,7 @@ def test_eight_ranks_line_is_measurement_complete():
     """The shape the driver's 8-GPU run has, rehearsed on the one test GPU: 8 ranks under torch.distributed.run, every key of the line present and
     non-null at N > 1 -- cpu_baseline and parity (rank 0, after the last barrier), roofline.traffic from the in-run PMC passes on rank 0's
     device, end_to_end through the node driver on every rank -- the same step definition as at N = 1, and the digest of digests of the one batch."""
-    args = ["--gates", "400", "--total-log2", "15", "--tile-log2", "11", "--steps", "2", "--warmup", "1"]
+    args = ["--gates", "400", "--total-log2", "15", "--tile-log2", "11", "--steps", "2", "--warmup", "1", "--full"]
     one = last_json(run([sys.executable, "bench.py", "--gpus", "1"] + args + ["--no-end-to-end", "--no-legs"]))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", ACVM_BENCH_SHARE_GPU="1")
     env.pop("ACVM_BENCH_NO_PMC", None)
@@ -64,6 +65,37 @@ def test_eight_ranks_line_is_measurement_complete():
         assert eight["roofline"]["traffic"] and eight["roofline"]["traffic"] > 0, eight["roofline"]
     s = eight["summary"]
     assert s["n_gpus"] == 8 and s["parity_ok"] is True and 0 < s["cpu_baseline"][1] <= os.cpu_count() and s["end_to_end"] > 0
+
+
+def test_plain_run_is_the_headline_and_dumps_its_last_step(oracle, tmp_path):
+    """A plain run (no --full) prints the headline and none of --full's figures; --steps sets the timed steps; --dump-outputs writes the same
+    arrays in two runs, and the sampled witnesses of the last tile are the oracle's for those instances."""
+    import numpy as np
+    from acvm_amd import synth
+    args = ["--gates", "400", "--total-log2", "13", "--tile-log2", "11", "--steps", "3", "--warmup", "1"]
+    lines = [last_json(run([sys.executable, "bench.py", "--gpus", "1"] + args + ["--dump-outputs", str(tmp_path / d)])) for d in ("a", "b")]
+    for line in lines:
+        assert line["full"] is False and line["steps"] == 3 and line["unit"] == "witnesses/s" and line["higher_is_better"] is True and line["dtype"]
+        assert line["value"] == pytest.approx(line["config"]["global_batch"] / (line["ms_per_step"] / 1e3))
+        for key in ("roofline", "cpu_baseline", "parity", "digest_of_digests", "end_to_end", "other_workloads", "summary"):
+            assert key not in line, key
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"results.npy", "witness_values.npy", "witness_assigned.npy"} <= set(names)
+    got = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert got[n[:-4]].dtype == np.float64 and np.array_equal(got[n[:-4]], np.load(tmp_path / "b" / n)), n
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["instances"][0] == (1 << 13) - (1 << 11) and len(got["instances"]) == 1 << 11
+    circ, ids = synth.arithmetic_circuit(400, seed=0xAC1D0002)
+    inst = [int(g) for g in got["sample_instances"]]
+    values = b"".join(synth.witness_batch(1, seed=0xAC1D0002, first_instance=g) for g in inst)
+    ores, oasg, ovals = oracle.solve_batch(oracle.Circuit(circ.to_bytes()), ids, values, len(inst))
+    ws = [int(w) for w in got["sample_witnesses"]]
+    rows = {int(g): r for r, g in enumerate(got["instances"])}
+    for i, g in enumerate(inst):
+        assert tuple(got["results"][rows[g]]) == ores[i].as_tuple()
+        assert np.array_equal(got["witness_assigned"][i], oasg[i][ws])
+        assert np.array_equal(got["witness_values"][i], ovals[i][ws].view(">u4").astype(np.float64) * oasg[i][ws][:, None])
 
 
 def test_more_gpus_than_devices_is_refused():

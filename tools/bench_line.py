@@ -9,6 +9,9 @@ for line in sys.stdin:
             print(line)
         continue
     d = json.loads(line)
+    if "roofline" not in d:  # a plain run: the headline only (bench.py --full has the rest)
+        print(round(d["value"]), "w/s", round(d["ms_per_step"], 2), "ms/step | tile", d["config"]["tile_instances"])
+        continue
     r = d["roofline"]
     a = d.get("alu_roofline") or {}
     e = d.get("end_to_end") or {}

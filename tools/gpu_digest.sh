@@ -9,4 +9,4 @@ for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print(d['mode'], d['tile'], [ (t['solve_device_ms'], t['digest_wall_ms'], round(t['witnesses_per_s'])) for t in d['tiles']])"
 done
-timeout 600 python bench.py --steps 5 --warmup 2 --no-legs 2>/dev/null | python tools/bench_line.py | cut -c1-200
+timeout 600 python bench.py --steps 5 --warmup 2 --full --no-legs 2>/dev/null | python tools/bench_line.py | cut -c1-200

@@ -10,5 +10,5 @@ import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
         d=json.loads(l); print([ (t['solve_device_ms'], t['launches']) for t in d['tiles']], d['tiles'][-1].get('kernel_ms'))"
-  ACVM_TUNING="light_fuse=$f" timeout 600 python bench.py --workload mixed --steps 10 --warmup 3 --no-legs 2>/dev/null | python tools/bench_line.py
+  ACVM_TUNING="light_fuse=$f" timeout 600 python bench.py --workload mixed --steps 10 --warmup 3 --full --no-legs 2>/dev/null | python tools/bench_line.py
 done

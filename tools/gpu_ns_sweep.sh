@@ -5,7 +5,7 @@ OUT=gpurun_out/ns_$TAG.txt
 : > $OUT
 IFS=';' read -ra SPECS <<< "$LIST"
 for spec in "${SPECS[@]}"; do
-  ACVM_TUNING="$spec" ACVM_BENCH_NO_PMC=1 python bench.py --workload arith_pedersen --total-log2 20 --tile-log2 17 --steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end --no-digest 2>/dev/null | python -c "
+  ACVM_TUNING="$spec" ACVM_BENCH_NO_PMC=1 python bench.py --workload arith_pedersen --total-log2 20 --tile-log2 17 --steps 4 --warmup 2 --full --no-cpu-baseline --no-end-to-end --no-digest 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -14,9 +14,9 @@ print(json.dumps({'value':round(d['value']),'ms_per_step':round(d['ms_per_step']
 for round in 1 2; do
   for lib in "" tools/ab/libacvm_amd_base.so; do
     echo "== metric step, lib=${lib:-tree} (round $round)"
-    ACVM_AMD_LIB=$lib ACVM_BENCH_NO_PMC=1 timeout 600 python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | line
+    ACVM_AMD_LIB=$lib ACVM_BENCH_NO_PMC=1 timeout 600 python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-end-to-end --no-legs 2>/dev/null | line
     echo "== north-star shape 2^20, lib=${lib:-tree} (round $round)"
-    ACVM_AMD_LIB=$lib ACVM_BENCH_NO_PMC=1 timeout 600 python bench.py --workload arith_pedersen --total-log2 20 --tile-log2 17 --steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end --no-digest 2>/dev/null | line
+    ACVM_AMD_LIB=$lib ACVM_BENCH_NO_PMC=1 timeout 600 python bench.py --workload arith_pedersen --total-log2 20 --tile-log2 17 --steps 4 --warmup 2 --full --no-cpu-baseline --no-end-to-end --no-digest 2>/dev/null | line
   done
 done
 for lib in "" tools/ab/libacvm_amd_base.so "" tools/ab/libacvm_amd_base.so; do

@@ -1,4 +1,4 @@
-"""One leg of bench.py's default run on its own (bench.run_leg): python tools/t_leg.py NAME TOTAL_LOG2 TILE_LOG2 [STEPS WARMUP].  ACVM_TUNING applies."""
+"""One leg of a `bench.py --full` run on its own (bench.run_leg): python tools/t_leg.py NAME TOTAL_LOG2 TILE_LOG2 [STEPS WARMUP].  ACVM_TUNING applies."""
 import json
 import os
 import sys
