@@ -19,6 +19,9 @@ STATUS_SOLVED, STATUS_IN_PROGRESS, STATUS_FAILURE, STATUS_REQUIRES_FOREIGN_CALL 
 (ERR_NONE, ERR_MISSING_ASSIGNMENT, ERR_TOO_MANY_UNKNOWNS, ERR_UNSUPPORTED_BLACKBOX, ERR_UNSATISFIED, ERR_INDEX_OOB,
  ERR_BLACKBOX_FAILED, ERR_BRILLIG_FAILED, ERR_PANIC, ERR_DEVICE_LIMIT) = range(10)
 LIMIT_BRILLIG_STEPS, LIMIT_BRILLIG_CALL_DEPTH, LIMIT_BRILLIG_MEMORY, LIMIT_DEVICE_MEMORY = 1, 2, 3, 4
+# acvm_batch_export_device: ACVM_ENC_* / ACVM_LAYOUT_*
+ENC_BE32, ENC_LE32, ENC_MONT256_LE = 0, 1, 2
+LAYOUT_INSTANCE_MAJOR, LAYOUT_WITNESS_MAJOR = 0, 1
 
 # every symbol include/acvm_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -38,6 +41,7 @@ ABI_SYMBOLS = [
     "acvm_tuning_set", "acvm_tuning_get", "acvm_tuning_key",
     "acvm_device_release_tables", "acvm_circuit_opcode_kinds", "acvm_batch_error_expression", "acvm_debug_stream_rate", "acvm_node_new", "acvm_node_free", "acvm_node_tile_instances", "acvm_node_num_devices", "acvm_node_solve", "acvm_node_stats",
     "acvm_debug_cpulist", "acvm_debug_device_locality", "acvm_debug_plan_fingerprint", "acvm_circuit_plans_built", "acvm_circuit_check_schedule", "acvm_batch_digest_blake2s",
+    "acvm_batch_export_device", "acvm_device_download",
 ]
 
 
@@ -47,6 +51,12 @@ class AcvmError(RuntimeError):
 
 class ExpressionHead(C.Structure):
     _fields_ = [("n_mul", C.c_uint32), ("n_lin", C.c_uint32), ("opcode_index", C.c_uint32), ("q_c", C.c_uint8 * 32)]
+
+
+class ExportDesc(C.Structure):
+    """acvm_export_desc_t"""
+    _fields_ = [("encoding", C.c_uint32), ("layout", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32), ("witnesses", C.POINTER(C.c_uint32)),
+                ("n_witnesses", C.c_uint32), ("stride", C.c_uint64)]
 
 
 class Result(C.Structure):
@@ -303,6 +313,8 @@ def lib():
     L.acvm_device_malloc.argtypes = [C.c_size_t]
     L.acvm_device_free.argtypes = [C.c_void_p]
     L.acvm_device_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.acvm_device_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.acvm_batch_export_device.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p]
     L.acvm_batch_solve_opcode.argtypes = [C.c_void_p]
     L.acvm_bb_stubbed.restype = C.c_void_p
     L.acvm_bb_dummy.restype = C.c_void_p
@@ -784,6 +796,18 @@ class Batch:
         _check(lib().acvm_batch_extract_witnesses(self._h, arr, len(ws), first, n, vals.ctypes.data))
         return vals
 
+    def export_device(self, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, witnesses=None, first=0, n=None, stride=0, d_assigned=None):
+        """The map of instances [first, first + n) written into device memory at d_ptr (acvm_batch_export_device): 32 bytes per element in
+        `encoding`, element (instance i, list position k) where `layout` and `stride` (in elements, 0 = dense) put it; witnesses: list of
+        indices, None = the whole map; d_assigned: device pointer of the 0 / 1 mask bytes, or None. Nothing is copied to the host."""
+        n = self.B - first if n is None else n
+        desc = ExportDesc(encoding=encoding, layout=layout, first=first, n=n, stride=stride)
+        if witnesses is not None:
+            ws = list(witnesses)
+            arr = (C.c_uint32 * max(len(ws), 1))(*ws)
+            desc.witnesses, desc.n_witnesses = arr, len(ws)
+        _check(lib().acvm_batch_export_device(self._h, C.byref(desc), d_ptr, d_assigned))
+
     def digest(self, first=0, n=None):
         """Per-instance 32-byte digest of the witness map (acvm_batch_digest): uint8 array [n][32]."""
         import numpy as np
@@ -851,6 +875,15 @@ class DeviceBuffer:
         if offset + buf.size > self.size:
             raise ValueError("upload past the end of the device buffer")
         _check(lib().acvm_device_upload(self.ptr + offset, buf.ctypes.data, buf.size))
+
+    def download(self, size=None, offset=0) -> bytes:
+        """`size` bytes from `offset` on (default: to the end of the buffer), copied to the host (acvm_device_download)"""
+        size = self.size - offset if size is None else size
+        if offset < 0 or size < 0 or offset + size > self.size:
+            raise ValueError("download past the end of the device buffer")
+        out = C.create_string_buffer(max(size, 1))
+        _check(lib().acvm_device_download(out, self.ptr + offset, size))
+        return out.raw[:size]
 
     def free(self):
         if getattr(self, "ptr", None) and _lib is not None:

@@ -142,6 +142,7 @@ struct acvm_batch {
     std::vector<hipEvent_t> ev_sync;
     uint32_t *d_unscale_index = nullptr, *d_unscale_consts = nullptr, *d_unscale_plain = nullptr, *d_scaled_ids = nullptr;  // projective witnesses (plan.cpp)
     Unscale unscale{};
+    uint32_t *d_unscale_m256 = nullptr;  // 2^256 / scale as canonical integers (acvm_batch_export_device, Montgomery-256), built at the first use
     uint32_t *d_ped_seed = nullptr;  // seed table of the level Pedersen kernel (one row per Pedersen record)
     uint4 *d_inv = nullptr;  // inverse table: [plan.n_inverse_slots][2 halves][Bp] x 16 B
     uint32_t n_launches = 0;
@@ -216,7 +217,7 @@ struct acvm_batch {
         for (void *p : {(void *)d_Wx, (void *)d_Memx, (void *)d_init_rows, (void *)d_ids_x, (void *)d_byte_plane_of, (void *)d_byte_plane_of_input, (void *)d_byte_plane})
             if (p) hipFree(p);
         if (d_inv) hipFree(d_inv);
-        for (void *p : {(void *)d_unscale_index, (void *)d_unscale_consts, (void *)d_unscale_plain, (void *)d_scaled_ids})
+        for (void *p : {(void *)d_unscale_index, (void *)d_unscale_consts, (void *)d_unscale_plain, (void *)d_scaled_ids, (void *)d_unscale_m256})
             if (p) hipFree(p);
         if (d_ped_seed) hipFree(d_ped_seed);
         if (d_stage) hipFree(d_stage);

@@ -14,6 +14,7 @@
 #include <vector>
 #include "batch_internal.hpp"
 #include "display.hpp"
+#include "export_encode.hpp"
 
 static const uint8_t DIGEST_G[32] = {0x23, 0x35, 0x53, 0x18, 0xdb, 0xff, 0xab, 0x2f, 0xb7, 0x72, 0x11, 0x7c, 0x57, 0x5c, 0x61, 0xb1,
                                      0x79, 0xf8, 0xc9, 0x83, 0x3c, 0x83, 0xba, 0x65, 0x59, 0x7e, 0x17, 0x3c, 0x35, 0xc4, 0xbb, 0xe3};
@@ -724,6 +725,74 @@ int acvm_batch_extract_witnesses(acvm_batch_t *b, const uint32_t *witnesses, uin
     }
     return reuse_patch_exact(b, d_sel, n_witnesses, first, n, values_be32, d_out);
 } ABI_CATCH
+
+// ---------------------------------------------------------------------------------------------- the map for a consumer on the device
+// 2^256 / scale mod p as canonical integers, one row per scaled witness like Unscale::consts_plain: the planner's representative (R = 2^256,
+// fr_host.hpp) of 1 / scale IS that integer. Built when the first Montgomery-256 export asks for it.
+static int ensure_mont256_table(acvm_batch *b) {
+    const Plan &p = b->plan();
+    if (b->d_unscale_m256 || p.scaled_ids.empty()) return 0;
+    std::vector<uint32_t> uc(p.unscale.size() * 8);
+    for (size_t i = 0; i < p.unscale.size(); i++) memcpy(&uc[8 * i], p.unscale[i].l, 32);
+    return upload(&b->d_unscale_m256, uc);
+}
+
+int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
+    if (!d) return set_err(ACVM_E_INVALID, "null argument");
+    if (d->encoding >= EXPORT_N_ENC) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
+    if (d->layout >= EXPORT_N_LAYOUT) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(d->layout));
+    if (!b || !d_values) return set_err(ACVM_E_INVALID, "null argument");
+    if ((uintptr_t)d_values & 15u) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
+    if (b->pending)
+        if (int rc = batch_finish_pending(b, &b->last_outcome)) return rc;
+    if (!b->solved) return set_err(ACVM_E_STATE, "batch not solved");
+    const uint32_t first = d->first, n = d->n;
+    if ((uint64_t)first + n > b->B) return set_err(ACVM_E_INVALID, "instance range out of bounds");
+    const uint32_t nw = b->plan().n_witnesses;
+    const bool whole = d->witnesses == nullptr;
+    const uint32_t n_sel = whole ? nw : d->n_witnesses;
+    const uint64_t dense = export_dense_stride(d->layout, n, n_sel), stride = d->stride ? d->stride : dense;
+    if (stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
+    if (whole) {
+        if (b->side()) return set_err(ACVM_E_STATE, "the batch recycles witness rows (ACVM_BATCH_REUSE_SLOTS) or solved its exact lanes in the side table: full maps are not kept; read the kept witnesses and the digest");
+        if (int rc = refuse_if_next_imported(b, nullptr, 0, true)) return rc;
+    } else {
+        if (int rc = refuse_if_next_imported(b, d->witnesses, n_sel, false)) return rc;
+        if (int rc = reuse_check_kept(b, d->witnesses, n_sel)) return rc;
+    }
+    if (!n || !n_sel) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (d->encoding == EXPORT_ENC_MONT256_LE)
+        if (int rc = ensure_mont256_table(b)) return rc;
+    // the instances of the exact path among the range: (lane, index in the range) pairs for the second launch
+    std::vector<uint32_t> lanes;
+    for (uint32_t i = 0; i < n; i++)
+        if (b->slow_index[first + i] >= 0) { lanes.push_back((uint32_t)b->slow_index[first + i]); lanes.push_back(i); }
+    const uint32_t n_lanes = (uint32_t)(lanes.size() / 2);
+    const size_t sel_bytes = whole ? 0 : align256((size_t)n_sel * 4);
+    if (sel_bytes + lanes.size() * 4)
+        if (int rc = stage_reserve(b, sel_bytes + lanes.size() * 4)) return rc;
+    hipStream_t s = b->stream;
+    uint32_t *d_sel = whole ? nullptr : (uint32_t *)b->d_stage, *d_lanes = (uint32_t *)(b->d_stage + sel_bytes);
+    if (!whole) HIPCHK(hipMemcpyAsync(d_sel, d->witnesses, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
+    if (n_lanes) HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
+    const ExportDevice x{d->encoding, d->layout, first, n, d_sel, n_sel, nw, stride, d_values, d_assigned};
+    // every lane as a generic instance (scaled columns, the planner's assigned set) ...
+    if (n_lanes < n)
+        launch_export_device(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, d->encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain);
+    // ... then the exact lanes from where they live (their own columns of the level table, or the side table), scattered into their elements
+    if (n_lanes)
+        launch_export_device_lanes(s, x, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), d_lanes, n_lanes, b->d_assigned, (uint32_t)b->slow_ids.size());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps `lanes` and the caller's list alive for their copies)
+    return 0;
+} ABI_CATCH
+
+int acvm_device_download(void *dst_host, const void *src_device, size_t bytes) {
+    if (bytes && (!dst_host || !src_device)) return set_err(ACVM_E_INVALID, "null argument");
+    if (bytes) HIPCHK(hipMemcpy(dst_host, src_device, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 long long acvm_witness_map_decode(const uint8_t *bytes, size_t len, uint32_t *ids, uint8_t *values_be32, uint32_t cap) try {
     if (!bytes) return set_err(ACVM_E_INVALID, "null argument");

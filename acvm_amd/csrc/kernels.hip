@@ -7,11 +7,14 @@
 //  (the exact in-order kernels and every non-arithmetic opcode live in kernels_ops.hip / kernels_hash.hip /
 //   kernels_grumpkin.hip / kernels_brillig.hip)
 //  export_witness_kernel   FieldElement::to_be_bytes (generic_ark.rs:269-277) for witness_map()/finalize()
+//  export_device_*_kernel  the same map left in device memory for a GPU consumer: big-endian, little-endian limbs or Montgomery-256,
+//                          instance-major (through LDS) or witness-major (streaming)
 //
 // Wave64 throughout; no LDS is needed by the streaming kernels (every operand is read once per lane);
 // gate records and circuit constants are wave-uniform and travel through the scalar cache.
 #include "ops_common.hpp"
 #include "kernels.hpp"
+#include "export_encode.hpp"
 #include "tuning.hpp"
 
 namespace acvm {
@@ -142,6 +145,109 @@ __global__ void __launch_bounds__(256) export_witness_kernel(const uint4 *__rest
         q[2] = (uint8_t)(x.v[i] >> 8);
         q[3] = (uint8_t)x.v[i];
     }
+}
+// ------------------------------------------------------------------------------------------ export into device memory
+// acvm_batch_export_device (include/acvm_amd.h): the map stays on the device, in the consumer's encoding and layout (export_encode.hpp).
+// One product per element whatever the encoding; the bytes leave as 16-byte nontemporal stores (somebody else's kernel reads them).
+// The two kernels of the generic lanes read every lane of the range as a GENERIC instance -- the planner's assigned set, scaled columns, rows through
+// row_of under slot reuse; export_device_lanes_kernel behind them rewrites the elements of the instances of the exact path.
+struct ExportArgs {
+    const uint4 *W;
+    uint64_t Bp;
+    uint32_t first, n;            // instances [first, first + n)
+    const uint32_t *sel;          // the witness list; null: position k is witness k
+    uint32_t n_sel, n_witnesses;  // a listed index >= n_witnesses is unassigned
+    const uint32_t *row_of, *producer;
+    const uint32_t *u_index, *u_factor;  // scaled witnesses: row of u_factor (8 x u32 canonical integers: 1 / scale, or 2^256 / scale for Montgomery-256)
+    uint32_t encoding;
+    uint64_t stride;
+    uint4 *out;
+    uint8_t *mask;  // may be null
+};
+__device__ __forceinline__ void export_store_nt(uint4 *p, const uint4 &v) {
+    const fr_u32x4 x = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(x, (fr_u32x4 *)p);
+}
+// element of generic instance j at list position k (k is wave-uniform: the table lookups are scalar loads)
+__device__ __forceinline__ ExportElement export_generic_element(const ExportArgs &a, uint32_t k, uint64_t j, bool &assigned) {
+    const uint32_t w = a.sel ? a.sel[k] : k;
+    uint32_t row = 0xFFFFFFFFu, ui = 0xFFFFFFFFu;
+    if (w < a.n_witnesses && a.producer[w] != 0xFFFFFFFFu) {
+        row = a.row_of ? a.row_of[w] : w;
+        if (a.u_index) ui = a.u_index[w];
+    }
+    assigned = row != 0xFFFFFFFFu;
+    if (!assigned) return export_encode(fr_zero(), fr_zero(), a.encoding, false);
+    return export_encode(fr_load_nt(a.W, row, a.Bp, j), ui != 0xFFFFFFFFu ? fr_const(a.u_factor, ui) : export_plain_factor(a.encoding), a.encoding, true);
+}
+// direct: lane = instance, blockIdx.y = list position. Witness-major, a wave reads 1 KiB per half row and writes 64 x 32 contiguous bytes; no LDS.
+// Also the instance-major kernel of a list shorter than the tiled kernel's four waves (the return witness of a tile: at one position the two
+// layouts are the same bytes, and a tile of 16 positions would run one wave in four).
+__global__ void __launch_bounds__(256) export_device_direct_kernel(const ExportArgs a, uint32_t layout, uint32_t k0) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t k = k0 + blockIdx.y;
+    if (i >= a.n) return;
+    bool assigned;
+    const ExportElement e = export_generic_element(a, k, a.first + i, assigned);
+    const uint64_t at = export_element_index(layout, a.stride, i, k);
+    export_store_nt(a.out + 2 * at, e.lo);
+    export_store_nt(a.out + 2 * at + 1, e.hi);
+    if (a.mask) a.mask[at] = assigned;
+}
+// instance-major: the transpose goes through LDS like the import's (its mirror image). Rows of 65 units: phase 1 writes 64 consecutive
+// units per (position, half); phase 2 reads with consecutive lanes 65 units apart, i.e. on consecutive 16-byte slots of the bank row.
+template <uint32_t T>
+__global__ void __launch_bounds__(EXPORT_THREADS) export_device_im_kernel(const ExportArgs a, uint32_t k0) {
+    static_assert(T % EXPORT_WAVES == 0 && (EXPORT_TILE_I * 2u * T) % EXPORT_THREADS == 0, "four waves share the positions; whole steps");
+    __shared__ uint4 tile[T][2][65];
+    __shared__ uint8_t tile_assigned[T][64];
+    const uint32_t t = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * EXPORT_TILE_I;
+    const uint32_t kb = k0 + blockIdx.y * T;
+    {
+        const uint32_t ji = export_tile_lane(t);
+        const uint64_t i = i0 + ji;
+#pragma unroll 1
+        for (uint32_t kk = export_tile_first_position(t); kk < T; kk += EXPORT_WAVES) {
+            const uint32_t k = kb + kk;
+            if (k >= a.n_sel || i >= a.n) continue;
+            bool assigned;
+            const ExportElement e = export_generic_element(a, k, a.first + i, assigned);
+            tile[kk][0][ji] = e.lo;
+            tile[kk][1][ji] = e.hi;
+            tile_assigned[kk][ji] = assigned;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t step = 0; step < export_tile_steps(T); step++) {
+        const ExportTileUnit q = export_tile_unit(T, t, step);
+        const uint64_t i = i0 + q.ji;
+        const uint32_t k = kb + q.kk;
+        if (i >= a.n || k >= a.n_sel) continue;
+        const uint64_t at = export_element_index(EXPORT_INSTANCE_MAJOR, a.stride, i, k);
+        export_store_nt(a.out + 2 * at + q.half, tile[q.kk][q.half][q.ji]);
+        if (a.mask && q.half == 0) a.mask[at] = tile_assigned[q.kk][q.ji];
+    }
+}
+// The instances of the exact path among [first, first + n): lane x = (t, i) -- its lane of the assigned bitmap and its index in the range --
+// lives in column t of the side table, or in its own column first + i of the level table (side = false). Row = witness index, nothing is
+// scaled there (unscale_slow_kernel / gather_columns_kernel), assigned = its bit. Few lanes by construction: one thread per element.
+__global__ void __launch_bounds__(256) export_device_lanes_kernel(const ExportArgs a, const uint32_t *__restrict__ lanes, uint32_t n_lanes, bool side,
+                                                                  const uint32_t *__restrict__ assigned_bits, uint32_t n_slow, uint32_t layout, uint32_t k0) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t k = k0 + blockIdx.y;
+    if (x >= n_lanes) return;
+    const uint32_t t = lanes[2 * x], i = lanes[2 * x + 1];
+    const uint32_t w = a.sel ? a.sel[k] : k;
+    const bool assigned = w < a.n_witnesses && ((assigned_bits[(uint64_t)(w >> 5) * n_slow + t] >> (w & 31u)) & 1u) != 0u;
+    ExportElement e;
+    if (assigned) e = export_encode(fr_load(a.W, w, a.Bp, side ? (uint64_t)t : (uint64_t)a.first + i), export_plain_factor(a.encoding), a.encoding, true);
+    else e = export_encode(fr_zero(), fr_zero(), a.encoding, false);
+    const uint64_t at = export_element_index(layout, a.stride, i, k);
+    export_store_nt(a.out + 2 * at, e.lo);
+    export_store_nt(a.out + 2 * at + 1, e.hi);
+    if (a.mask) a.mask[at] = assigned;
 }
 // columns of the instances that continue on the exact path: every scaled witness the lane keeps back to its plain Montgomery value. The lane keeps
 // what init_assigned_kernel marks -- outputs of opcodes in front of its event; the rows behind it are written by the exact kernels before anything
@@ -437,6 +543,32 @@ void launch_export(hipStream_t s, const uint4 *W, uint64_t Bp, uint32_t first, u
     for (uint32_t done = 0; done < n_sel; done += 65535u) {
         const uint32_t m = n_sel - done > 65535u ? 65535u : n_sel - done;
         hipLaunchKernelGGL(export_witness_kernel, dim3((n + 255) / 256, m), dim3(256), 0, s, W, Bp, first, n, sel, n_sel, out, u, done, row_of);
+    }
+}
+void launch_export_device(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                          const uint32_t *u_factor) {
+    if (!x.n || !x.n_sel) return;
+    const ExportArgs a{W, Bp, x.first, x.n, x.sel, x.n_sel, x.n_witnesses, row_of, producer, u.index, u_factor, x.encoding, x.stride, (uint4 *)x.out, x.mask};
+    if (x.layout == EXPORT_WITNESS_MAJOR || x.n_sel < EXPORT_WAVES) {
+        for (uint32_t done = 0; done < x.n_sel; done += 65535u) {  // gridDim.y is limited to 65535
+            const uint32_t m = x.n_sel - done > 65535u ? 65535u : x.n_sel - done;
+            hipLaunchKernelGGL(export_device_direct_kernel, dim3((x.n + 255u) / 256u, m), dim3(256), 0, s, a, x.layout, done);
+        }
+        return;
+    }
+    const uint32_t tiles = (x.n_sel + EXPORT_TILE_T - 1u) / EXPORT_TILE_T;
+    for (uint32_t done = 0; done < tiles; done += 65535u) {
+        const uint32_t m = tiles - done > 65535u ? 65535u : tiles - done;
+        hipLaunchKernelGGL(export_device_im_kernel<EXPORT_TILE_T>, dim3((x.n + EXPORT_TILE_I - 1u) / EXPORT_TILE_I, m), dim3(EXPORT_THREADS), 0, s, a, done * EXPORT_TILE_T);
+    }
+}
+void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
+                                const uint32_t *assigned_bits, uint32_t n_slow) {
+    if (!n_lanes || !x.n_sel) return;
+    const ExportArgs a{W, Bp, x.first, x.n, x.sel, x.n_sel, x.n_witnesses, nullptr, nullptr, nullptr, nullptr, x.encoding, x.stride, (uint4 *)x.out, x.mask};
+    for (uint32_t done = 0; done < x.n_sel; done += 65535u) {
+        const uint32_t m = x.n_sel - done > 65535u ? 65535u : x.n_sel - done;
+        hipLaunchKernelGGL(export_device_lanes_kernel, dim3((n_lanes + 255u) / 256u, m), dim3(256), 0, s, a, lanes, n_lanes, side, assigned_bits, n_slow, x.layout, done);
     }
 }
 void launch_unscale_slow(hipStream_t s, uint4 *W, uint64_t Bp, const uint32_t *slow_ids, uint32_t n_slow, const Unscale &u, const uint32_t *producer,

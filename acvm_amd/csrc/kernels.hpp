@@ -84,6 +84,23 @@ bool launch_import(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint8
                    const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
 void launch_export(hipStream_t s, const uint4 *W, uint64_t Bp, uint32_t first, uint32_t n, const uint32_t *sel, uint32_t n_sel,
                    uint8_t *out, const Unscale &u, const uint32_t *row_of = nullptr);
+// acvm_batch_export_device: the map of instances [first, first + n) x the witness list into the caller's device buffer (export_encode.hpp:
+// encodings, layouts, where element (i, k) goes). sel: device array, or null = position k is witness k.
+struct ExportDevice {
+    uint32_t encoding, layout, first, n;
+    const uint32_t *sel;
+    uint32_t n_sel, n_witnesses;
+    uint64_t stride;  // in elements, >= the layout's dense stride
+    void *out;        // 16-byte aligned
+    uint8_t *mask;    // one byte per element, same layout and stride; may be null
+};
+// every lane of the range read as a generic instance (u_factor: Unscale::consts_plain, or its Montgomery-256 twin for that encoding) ...
+void launch_export_device(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                          const uint32_t *u_factor);
+// ... then the instances of the exact path over their elements: lanes = n_lanes pairs (lane of the assigned bitmap, index in the range), values in
+// column `lane` of W (side) or in column first + index
+void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
+                                const uint32_t *assigned_bits, uint32_t n_slow);
 void launch_gather_initial(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *W, uint64_t Bp, const uint32_t *init_ids, const uint32_t *init_rows, uint32_t n_init,
                            const uint32_t *slow_ids, uint32_t n_slow);
 void launch_gather_columns(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *W, uint64_t Bp, uint32_t n_rows, const uint32_t *slow_ids, uint32_t n_slow,

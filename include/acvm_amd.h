@@ -306,6 +306,7 @@ int acvm_batch_set_initial_witness_device(acvm_batch_t *b, const void *d_values_
 void *acvm_device_malloc(size_t bytes);
 int acvm_device_free(void *p);
 int acvm_device_upload(void *dst_device, const void *src_host, size_t bytes);
+int acvm_device_download(void *dst_host, const void *src_device, size_t bytes); /* its twin: what a caller inspects of an acvm_batch_export_device buffer */
 /* ACVM::solve for every instance. Returns the number of instances not Solved, or a negative error. */
 int acvm_batch_solve(acvm_batch_t *b);
 /*
@@ -449,6 +450,38 @@ int acvm_batch_digest_blake2s(acvm_batch_t *b, uint32_t first, uint32_t n, uint8
  */
 int acvm_batch_extract_witnesses(acvm_batch_t *b, const uint32_t *witnesses, uint32_t n_witnesses, uint32_t first, uint32_t n,
                                  uint8_t *values_be32);
+
+/*
+ * The witness map where it already is: ACVM::witness_map / finalize (acvm/src/pwg/mod.rs:161,176-181) written into DEVICE memory of the
+ * caller, in the encoding and layout of the GPU program that consumes it (a prover's wire columns, a commitment kernel, the initial
+ * witnesses of the next circuit of a pipeline). Every export above stages through host memory; this one moves no value over PCIe.
+ *   - d_values / d_assigned are plain device pointers on the batch's device. d_values must be 16-byte aligned (else ACVM_E_INVALID) and hold
+ *     32 bytes per element; d_assigned, which may be NULL, holds one byte (0 / 1) per element in the same layout and stride.
+ *   - witnesses: HOST array of n_witnesses indices, any order, repeats allowed; NULL = the whole map 0 .. acvm_circuit_num_witnesses - 1.
+ *   - An unassigned element is 32 zero bytes and mask 0, in every encoding; a listed index beyond the circuit's witnesses is unassigned.
+ *     Unlike acvm_batch_extract_witnesses an unassigned witness is not an error: the mask says it.
+ *   - stride, in elements: see the layouts; 0 = dense. The bytes between rows are never written. A stride below the dense one is ACVM_E_INVALID.
+ *   - The call enqueues on the batch's stream and returns after that stream is synchronised. No value is copied to the host and no host loop
+ *     runs per instance; at most one small host-to-device copy is made (the index list, the lanes of the instances of the exact path).
+ *   - Answers in every state in which acvm_batch_extract_witnesses answers, with the same values: solved, failed and waiting instances (the
+ *     map as it stands), after acvm_batch_solve_opcode steps, with the forced slow path, with ACVM_BATCH_REUSE_SLOTS (initial witnesses and
+ *     keep_ids only). The same refusals (ACVM_E_STATE): not solved; a witness that was not kept, or the whole map, of a batch that recycles
+ *     rows or keeps exact lanes in its side table; initial witnesses or the whole map after acvm_batch_solve_then_import.
+ * Not here: device outputs for acvm_node_solve, an asynchronous variant; the host exports above are unchanged.
+ */
+enum { ACVM_ENC_BE32 = 0,          /* canonical, 32 bytes big-endian: byte for byte what acvm_batch_witness_map writes */
+       ACVM_ENC_LE32 = 1,          /* canonical, 4 x u64 little-endian limbs (= 32 bytes little-endian) */
+       ACVM_ENC_MONT256_LE = 2 };  /* value * 2^256 mod p, 4 x u64 little-endian limbs (ark-ff BigInt<4> / barretenberg fr in memory) */
+enum { ACVM_LAYOUT_INSTANCE_MAJOR = 0,   /* element (i, k) at (i * stride + k) * 32, stride >= n_witnesses (0 = dense) */
+       ACVM_LAYOUT_WITNESS_MAJOR = 1 };  /* element (i, k) at (k * stride + i) * 32, stride >= n           (0 = dense) */
+typedef struct {
+    uint32_t encoding, layout;
+    uint32_t first, n;         /* instances [first, first + n): i = instance - first */
+    const uint32_t *witnesses; /* k = position in this list (NULL: k = witness index) */
+    uint32_t n_witnesses;      /* ignored when witnesses == NULL */
+    uint64_t stride;
+} acvm_export_desc_t;
+int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):
