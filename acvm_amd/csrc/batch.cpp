@@ -549,6 +549,7 @@ int acvm_batch_reset(acvm_batch_t *b) {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
     b->solved = false;
     b->stepping = false;
+    b->events_fresh = false;  // (whatever ran since the import may have written the event words: batch.hpp)
     clear_fc_store(b);
     return 0;
 }

@@ -85,7 +85,11 @@ struct acvm_batch {
     uint32_t *d_event = nullptr;       // the event words; EVENT_HDR_WORDS in front of them: the count of flagged instances and the device address of h_flag_count
     uint32_t *d_event_base = nullptr;  // (the allocation)
     uint32_t *h_flag_count = nullptr;  // pinned, device-mapped: the same count where the host reads it after a synchronisation
-    bool events_fresh = false;         // the last import left the event words "nobody flagged": the next solve skips its reset launch
+    // The one rule of events_fresh: true only between an import that wrote the event words ("nobody flagged": kernels.hip import_witness_kernel)
+    // and the first thing enqueued behind it; the level solve that finds it set skips its reset launch. Set where launch_import says it launched
+    // (not for a circuit without initial witnesses); cleared by everything else that writes d_event or changes what it covers: the level
+    // schedule's reset step, the fill of the exact-only solve and of solve_stepping, acvm_batch_reset, batch_set_live_count.
+    bool events_fresh = false;
     std::vector<uint32_t> h_event;
     bool events_clean = false;  // h_event is all 0xFFFFFFFF, slow_ids empty, slow_index all -1 (kept across solves that flag nothing)
     // exact in-order path

@@ -467,6 +467,7 @@ int solve_stepping(acvm_batch *b, bool one) {
         if (!n_slow) return 0;
         if (int rc = ensure_slow_capacity(b, n_slow)) return rc;
         launch_fill_u32(s, b->d_event, 0u, b->B);  // no column is scaled: the exact kernels write plain values
+        b->events_fresh = false;
         HIPCHK(hipMemcpyAsync(b->d_slow_ids, b->slow_ids.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(b->d_slow_start, b->slow_start.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
         launch_init_assigned(s, b->d_assigned, n_slow, b->n_words, p.n_witnesses, b->d_producer, b->d_slow_start);
@@ -709,6 +710,9 @@ int batch_set_live_count(acvm_batch *b, uint32_t n) {
         b->inputs_set = false;
         b->solved = false;
         b->stepping = false;
+        b->events_fresh = false;  // (the words behind the old count hold what an earlier solve left there)
+        b->next_imported = false;
+        b->next_inputs = nullptr;
     }
     return 0;
 }

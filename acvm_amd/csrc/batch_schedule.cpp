@@ -156,13 +156,14 @@ int batch_solve_impl(acvm_batch *b, const void *next_inputs) {
     // none: only their count comes back -- kept by the kernels that flag, in a host-mapped word the host reads after the synchronisation it
     // needs anyway (no counting kernel and no copy behind the last kernel of a solve)
     uint32_t n_flagged = b->B;
+    bool import_launched = false;
     if (!b->force_slow && b->B) {
         if (next_inputs) {
             if (!b->ev_counted) HIPCHK(hipEventCreate(&b->ev_counted));
             HIPCHK(hipEventRecord(b->ev_counted, s));
             // gate: the device's count of flagged instances, in front of the event words; the import leaves the event words ready for the next solve
-            launch_import(s, b->d_W, b->Bp, b->B, (const uint8_t *)next_inputs, b->reuse() ? b->d_init_rows : b->d_init_ids, (uint32_t)p.initial_ids.size(),
-                          b->d_event - 4, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
+            import_launched = launch_import(s, b->d_W, b->Bp, b->B, (const uint8_t *)next_inputs, b->reuse() ? b->d_init_rows : b->d_init_ids, (uint32_t)p.initial_ids.size(),
+                                            b->d_event - 4, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventSynchronize(b->ev_counted));
         } else HIPCHK(hipStreamSynchronize(s));
@@ -245,7 +246,7 @@ int batch_solve_impl(acvm_batch *b, const void *next_inputs) {
         HIPCHK(hipEventElapsedTime(&ms, b->ev_start, b->ev_counted));
         b->next_imported = true;
         b->next_inputs = next_inputs;
-        b->events_fresh = true;  // (the gated import ran: it left the event words ready)
+        b->events_fresh = import_launched;  // (the gated import ran: it left the event words ready -- unless there is no initial witness to import)
     } else {
         HIPCHK(hipEventRecord(b->ev_end, s));
         HIPCHK(hipStreamSynchronize(s));
