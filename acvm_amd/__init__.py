@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     "acvm_tuning_set", "acvm_tuning_get", "acvm_tuning_key",
     "acvm_device_release_tables", "acvm_circuit_opcode_kinds", "acvm_batch_error_expression", "acvm_debug_stream_rate", "acvm_node_new", "acvm_node_free", "acvm_node_tile_instances", "acvm_node_num_devices", "acvm_node_solve", "acvm_node_stats",
     "acvm_debug_cpulist", "acvm_debug_device_locality", "acvm_debug_plan_fingerprint", "acvm_circuit_plans_built", "acvm_circuit_check_schedule", "acvm_batch_digest_blake2s",
-    "acvm_batch_export_device", "acvm_device_download",
+    "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
 ]
 
 
@@ -288,6 +288,10 @@ def lib():
     L.acvm_witness_map_encode.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p, C.c_size_t]
     L.acvm_batch_witness_map_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
     L.acvm_debug_modmul_rate.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    if hasattr(L, "acvm_debug_fr"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has no such probes)
+        L.acvm_debug_fr.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.acvm_debug_inverse_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_uint32)]
     L.acvm_debug_secp_rate.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.acvm_circuit_opcode_kinds.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.acvm_batch_error_expression.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ExpressionHead), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -499,6 +503,39 @@ def debug_secp(curve, what, items):
     _check(lib().acvm_debug_secp(curve, what, data, len(items), out))
     raw = out.raw
     return [tuple(int.from_bytes(raw[32 * (wo * i + k):32 * (wo * i + k + 1)], "big") for k in range(wo)) for i in range(len(items))]
+
+
+# acvm_debug_fr: u32 words per item (in, out) of every `what` (acvm_amd/csrc/fr_probe.hpp)
+FR_PROBE_WORDS = ((16, 8), (16, 8), (8, 8), (16, 8), (16, 8), (8, 8), (8, 8), (8, 8), (8, 8), (8, 2), (8, 2), (1, 8), (8, 9), (9, 8), (18, 9), (18, 9), (9, 9),
+                  (9, 1), (9, 9), (10, 9), (9, 9), (9, 9), (9, 9), (9, 9), (19, 9), (18, 9), (9, 9), (9, 1), (18, 9), (36, 9), (54, 9), (27, 9), (45, 9), (27, 9),
+                  (45, 9), (18, 9), (36, 9), (27, 9))
+
+
+def debug_fr(what, items, uniform=None):
+    """Component probe of the BN254-Fr device library (see include/acvm_amd.h): items = an array [n][words in] of raw u32 limbs, uniform = the 18 words
+    of the two wave-uniform factors of what 35..37; returns the raw result limbs as a uint32 array [n][words out]."""
+    import numpy as np
+    wi, wo = FR_PROBE_WORDS[what]
+    a = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, wi)
+    out = np.zeros((a.shape[0], wo), dtype=np.uint32)
+    u = None if uniform is None else np.ascontiguousarray(uniform, dtype=np.uint32).reshape(18)
+    _check(lib().acvm_debug_fr(what, a.ctypes.data, a.shape[0], None if u is None else u.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_inverse_batch(den, inv_chunk, slot_of=None):
+    """The shipped inversion batch on denominators of the caller's (see include/acvm_amd.h): den = uint32 [n_jobs][B][8], canonical storage form.
+    Returns (inverse-table rows [n_jobs][B][8], row slot_of[k] for job k; event words [B]; the device's count of flagged instances; the host counter)."""
+    import numpy as np
+    d = np.ascontiguousarray(den, dtype=np.uint32)
+    n_jobs, B = d.shape[0], d.shape[1]
+    assert d.shape == (n_jobs, B, 8)
+    s = None if slot_of is None else np.ascontiguousarray(slot_of, dtype=np.uint32).reshape(n_jobs)
+    inv, ev = np.zeros((n_jobs, B, 8), dtype=np.uint32), np.zeros(B, dtype=np.uint32)
+    dc, hc = C.c_uint32(), C.c_uint32()
+    _check(lib().acvm_debug_inverse_batch(d.ctypes.data, n_jobs, B, inv_chunk, None if s is None else s.ctypes.data, inv.ctypes.data, ev.ctypes.data,
+                                          C.byref(dc), C.byref(hc)))
+    return inv, ev, dc.value, hc.value
 
 
 def decompress_witness(data: bytes) -> dict:

@@ -441,19 +441,23 @@ static int batch_init(acvm_batch *b) {
         size_t bytes = (size_t)p.n_inverse_slots * 2 * b->Bp * sizeof(uint4);
         HIPCHK(hipMalloc((void **)&b->d_inv, bytes ? bytes : 16));
     }
-    {   // event words, with the count of flagged instances and the device address of the host-visible counter in front (ops_common.hpp flag_instance)
-        HIPCHK(hipMalloc((void **)&b->d_event_base, ((size_t)b->B + 4 + 4) * 4));
-        b->d_event = b->d_event_base + 4;
-        HIPCHK(hipHostMalloc((void **)&b->h_flag_count, 64, hipHostMallocMapped));
-        void *d_count = nullptr;
-        HIPCHK(hipHostGetDevicePointer(&d_count, b->h_flag_count, 0));
-        uint32_t hdr[4] = {0, 0, 0, 0};
-        memcpy(&hdr[2], &d_count, sizeof d_count);
-        HIPCHK(hipMemcpy(b->d_event_base, hdr, sizeof hdr, hipMemcpyHostToDevice));
-    }
+    if (int rc = event_words_new(b->B, &b->d_event_base, &b->d_event, &b->h_flag_count)) return rc;
     b->unscale = Unscale{b->d_unscale_index, b->d_unscale_consts, b->d_unscale_plain, b->d_scaled_ids, (uint32_t)p.scaled_ids.size(), b->d_event};
     b->h_event.assign(b->B, 0xFFFFFFFFu);
     b->slow_index.assign(b->B, -1);
+    return 0;
+}
+
+// event words, with the count of flagged instances and the device address of the host-visible counter in front (ops_common.hpp flag_instance)
+int event_words_new(uint32_t B, uint32_t **base, uint32_t **event, uint32_t **h_flag_count) {
+    HIPCHK(hipMalloc((void **)base, ((size_t)B + 4 + 4) * 4));
+    *event = *base + 4;
+    HIPCHK(hipHostMalloc((void **)h_flag_count, 64, hipHostMallocMapped));
+    void *d_count = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&d_count, *h_flag_count, 0));
+    uint32_t hdr[4] = {0, 0, 0, 0};
+    memcpy(&hdr[2], &d_count, sizeof d_count);
+    HIPCHK(hipMemcpy(*base, hdr, sizeof hdr, hipMemcpyHostToDevice));
     return 0;
 }
 

@@ -18,6 +18,9 @@ int stage_reserve(acvm_batch *b, size_t bytes);
 // forget every resolved foreign-call result (a new ACVM: set_initial_witness / reset)
 void clear_fc_store(acvm_batch *b);
 void plan_stats(const Plan &p, acvm_stats_t *out);
+// the event words of B instances (*event) behind their four-word header (*base, the allocation: the count of flagged instances at event[-4], the device
+// address of *h_flag_count, pinned and device-mapped, at event[-2..-1]); the words themselves are left for launch_event_reset
+int event_words_new(uint32_t B, uint32_t **base, uint32_t **event, uint32_t **h_flag_count);
 
 // ---- batch_schedule.cpp
 // ACVM::solve for the batch; next_inputs: acvm_batch_solve_then_import

@@ -145,7 +145,7 @@ FR_HD __forceinline__ Fr fr29_pack(const Fr29 &a) {
     return r;
 }
 // Montgomery product a * b * 2^-261 mod p in the working form. Inputs: limbs < 2^29 (top limb < 2^28), values < 8p.
-// Output: limbs < 2^29, value < 1.4p (< 1.06p for inputs < 4p). Column k of a * b + m * p is summed in one 64-bit
+// Output: limbs < 2^29, value < p + a b / 2^261: < 1.4p (< 1.1p for inputs < 4p, < 1.06p for inputs whose product is below 10 p^2). Column k of a * b + m * p is summed in one 64-bit
 // accumulator (at most 18 products < 2^58 plus a 35-bit carry); m_k = column * (-p^-1) mod 2^29 zeroes the column's low
 // limb, and -p^-1 = 2^28 - 1, p_0 = 2^28 + 1 turn both of those multiplications into shifts.
 #ifdef FR_BLOCKS_ALL  // measurement only (tools/build_variant.sh): every fr29_mul of the translation unit takes the asm-block form below
@@ -483,6 +483,12 @@ FR_HD __forceinline__ Fr fr_mul_portable(const Fr &a, const Fr &b) {
 }
 
 FR_HD __forceinline__ Fr fr_sqr(const Fr &a) { return fr_mul(a, a); }
+// Montgomery form -> the canonical little-endian 8 x 32 integer: the product with the integer 1
+FR_HD __forceinline__ Fr fr_to_canonical(const Fr &a) {
+    Fr one = fr_zero();
+    one.v[0] = 1;
+    return fr_mul(a, one);
+}
 
 // R^3 mod p: takes the integer inverse of a Montgomery representative back into Montgomery form
 FR_HD __forceinline__ Fr fr_r3() {

@@ -39,7 +39,8 @@ FR_HD __forceinline__ void gate_h_sub(Fr29 &h, const Fr29 &x, uint32_t klog2) {
         for (int i = 0; i < 9; i++) h.v[i] += fr_kp29_sub(3, i) - x.v[i];
     }
 }
-// 8 inline words of a record -> working form (wave-uniform: scalar work on the device)
+// 8 inline words of a record -> working form (wave-uniform: scalar work on the device). The contract of the "s" operands it feeds (fr29_dot_add_b's UB
+// factors): every lane of the wave holds the SAME value -- a word of the record or a kernel argument, never a per-lane value.
 FR_HD __forceinline__ Fr29 gate_coef29(GateWords t) {
     Fr c;
 #pragma unroll

@@ -13,6 +13,8 @@
 // Wave64 throughout; no LDS is needed by the streaming kernels (every operand is read once per lane);
 // gate records and circuit constants are wave-uniform and travel through the scalar cache.
 #include "ops_common.hpp"
+#include "fr_probe.hpp"
+#include "inverse_batch.hpp"
 #include "kernels.hpp"
 #include "export_encode.hpp"
 #include "tuning.hpp"
@@ -283,7 +285,16 @@ arith_level_kernel(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_
 // inversions of a lane are batched with Montgomery's trick, so a lane pays one field inversion per chunk plus 3
 // multiplications per job. The prefix products are parked in the jobs' own rows of the inverse table (laid out like W,
 // [slot][half][instance], coalesced) and replaced by the inverses on the way back. Values stay in the 29-bit working form
-// between products (< 1.06p, never repacked); the table holds representatives < 2^256, not necessarily < p.
+// between products (below 1.01p here -- one factor is canonical, fr_device.hpp fr29_mul's bound --, never repacked); the table holds representatives < 2^256, not necessarily < p.
+// The device's accesses of inverse_batch_body (inverse_batch.hpp): the three nontemporal ones of this path (5.54 -> 5.565 M witnesses/s) and flag_instance.
+struct InverseDevicePolicy {
+    static __device__ __forceinline__ Fr load_den(const uint4 *W, uint32_t row, uint64_t Bp, uint64_t j) { return fr_load(W, row, Bp, j); }
+    static __device__ __forceinline__ Fr load_den_last(const uint4 *W, uint32_t row, uint64_t Bp, uint64_t j) { return fr_load_nt(W, row, Bp, j); }
+    static __device__ __forceinline__ void park(uint4 *Inv, uint32_t slot, uint64_t Bp, uint64_t j, const Fr &a) { fr_store(Inv, slot, Bp, j, a); }
+    static __device__ __forceinline__ Fr parked(const uint4 *Inv, uint32_t slot, uint64_t Bp, uint64_t j) { return fr_load(Inv, slot, Bp, j); }
+    static __device__ __forceinline__ void store_inverse(uint4 *Inv, uint32_t slot, uint64_t Bp, uint64_t j, const Fr &a) { fr_store_nt(Inv, slot, Bp, j, a); }
+    static __device__ __forceinline__ void flag(uint32_t *event, uint64_t j, uint32_t opcode) { flag_instance(event, j, opcode); }
+};
 __global__ void __launch_bounds__(64) inverse_batch_kernel(const uint4 *__restrict__ W, uint4 *__restrict__ Inv, uint64_t Bp, uint32_t B,
                                                            const uint32_t *__restrict__ gate_stream, const uint32_t *__restrict__ job_offset,
                                                            uint32_t n_jobs, uint32_t chunk, uint32_t *__restrict__ event) {
@@ -291,28 +302,7 @@ __global__ void __launch_bounds__(64) inverse_batch_kernel(const uint4 *__restri
     if (j >= B) return;
     const uint32_t first = blockIdx.y * chunk;
     const uint32_t n = n_jobs - first < chunk ? n_jobs - first : chunk;
-    Fr29 prefix = fr29_from(fr_one());
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t *__restrict__ g = gate_stream + job_offset[first + i];
-        Fr den = fr_load(W, g[0], Bp, j);
-        if (fr_is_zero(den)) {  // zero-coefficient drop (arithmetic.rs:217-221): this instance leaves the generic path at the gate
-            flag_instance(event, j, g[1]);
-            den = fr_one();
-        }
-        prefix = fr29_mul(prefix, fr29_from(den));
-        fr_store(Inv, g[2], Bp, j, fr29_pack(prefix));
-    }
-    Fr29 inv = fr29_from(fr_inv(fr29_pack(fr29_cond_sub_p(prefix))));  // 1 / (den_0 ... den_{n-1})
-    for (uint32_t i = n; i-- > 0;) {
-        const uint32_t *__restrict__ g = gate_stream + job_offset[first + i];
-        Fr den = fr_load_nt(W, g[0], Bp, j);  // second and last read of the row by this launch
-        if (fr_is_zero(den)) den = fr_one();
-        // (the first job's "prefix before it" is 1: one product more per wave, and no second path for the compiler to merge with 126 register moves per job)
-        const Fr prev = i > 0 ? fr_load(Inv, gate_stream[job_offset[first + i - 1] + 2], Bp, j) : fr_one();
-        const Fr29 inv_i = fr29_mul(inv, fr29_from(prev));
-        inv = fr29_mul(inv, fr29_from(den));
-        fr_store_nt(Inv, g[2], Bp, j, fr29_pack(inv_i));  // read once, by a gate levels later (the three nontemporal accesses of this path: 5.54 -> 5.565 M witnesses/s)
-    }
+    inverse_batch_body<InverseDevicePolicy>(W, Inv, Bp, j, gate_stream, job_offset, first, n, event);
 }
 
 // ------------------------------------------------------------------------------------------ self test
@@ -411,6 +401,23 @@ __global__ void __launch_bounds__(256) fr_selftest_kernel(uint64_t seed, uint32_
         if (!same(fr29_dot_add_b<2, 3u>(l2, m2uu, h), fr29_dot_add<2>(l2, m2uu, h))) bad |= 2048;
     }
     if (bad) atomicAdd(mismatches, 1u);
+}
+
+// ---- component probe of the field library (acvm_debug_fr): one lane per item, raw limbs in and out (fr_probe.hpp fr_probe_item is the switch;
+// tests/test_gpu_fr_probe.py compares every word with Python integers). `un` is a kernel argument: the second factors of the "U" forms are
+// wave-uniform in fact, as the scalar-register operands of the asm blocks require.
+__global__ void __launch_bounds__(64) fr_probe_kernel(uint32_t what, const uint32_t *__restrict__ in, uint32_t n_items, uint32_t words_in, uint32_t words_out,
+                                                      FrProbeUniform un, uint32_t *__restrict__ out) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_items) return;
+    fr_probe_item(what, in + (size_t)t * words_in, un, out + (size_t)t * words_out);
+}
+uint32_t fr_probe_words(uint32_t what, bool out) { return out ? fr_probe_words_out(what) : fr_probe_words_in(what); }
+void launch_fr_probe(hipStream_t s, uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out) {
+    if (!n_items || what >= FRP_COUNT) return;
+    FrProbeUniform un;
+    for (int k = 0; k < 18; k++) un.u[k / 9].v[k % 9] = uniform18 ? uniform18[k] : 0u;
+    hipLaunchKernelGGL(fr_probe_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, what, in, n_items, fr_probe_words_in(what), fr_probe_words_out(what), un, out);
 }
 
 // ------------------------------------------------------------------------------------------ modmul rate probe

@@ -118,6 +118,10 @@ void launch_modmul_rate(hipStream_t s, uint32_t *out, uint32_t blocks, uint32_t 
 void launch_secp_rate(hipStream_t s, uint32_t curve, uint32_t *out, uint32_t blocks, uint32_t iters);  // kernels_ecdsa.hip
 void launch_stream_rate(hipStream_t s, const uint4 *a, const uint4 *b, uint4 *out, uint64_t n);  // n: multiple of 256
 void launch_fr_selftest(hipStream_t s, uint64_t seed, uint32_t n, uint32_t *mismatches);
+// acvm_debug_fr (fr_probe.hpp): words per item of `what` going in / coming out (0: no such routine); one lane per item, in / out on the device,
+// uniform18: host memory, the two wave-uniform working-form factors of the "U" forms (null: zeros)
+uint32_t fr_probe_words(uint32_t what, bool out);
+void launch_fr_probe(hipStream_t s, uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out);
 void launch_fill_u32(hipStream_t s, uint32_t *p, uint32_t v, uint64_t n);
 // event words [0, B) <- 0xFFFFFFFF, the count of flagged instances in front of them (event[-4], ops_common.hpp flag_instance) <- 0
 void launch_event_reset(hipStream_t s, uint32_t *event, uint32_t B);

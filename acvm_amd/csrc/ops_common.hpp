@@ -147,12 +147,7 @@ __device__ __forceinline__ Fr fr_r2() {
     Fr r = {{0x45b69bd4u, 0x38c2e14bu, 0x85883377u, 0x0ffedb18u, 0xabc6e54du, 0x7840f9f0u, 0x848b0f05u, 0x0a054a3eu}};  // 2^522 mod p
     return r;
 }
-// Montgomery <-> canonical little-endian 8x32 integers
-__device__ __forceinline__ Fr fr_to_canonical(const Fr &a) {
-    Fr one = fr_zero();
-    one.v[0] = 1;
-    return fr_mul(a, one);
-}
+// canonical little-endian 8x32 integers -> Montgomery (the other direction: fr_device.hpp fr_to_canonical)
 __device__ __forceinline__ Fr fr_from_canonical(const Fr &c) { return fr_mul(c, fr_r2()); }  // c < p
 __device__ __forceinline__ Fr fr_from_u32(uint32_t x) {
     Fr c = fr_zero();

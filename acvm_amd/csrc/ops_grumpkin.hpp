@@ -16,7 +16,7 @@ namespace acvm {
 // Affine points travel in the storage form (tables, witnesses); Jacobian accumulators live in the 29-bit working form with
 // LAZY reduction (fr_device.hpp): coordinates are kept "class A" = normalised limbs, value < 2p, and inside a formula sums
 // and differences are limb-wise (a difference adds a multiple of p first) and only renormalised before they feed a product,
-// which accepts values < 16p and returns < 1.4p. The bounds are written beside each line (in units of p). This removes every
+// which accepts values < 16p and returns < 1.4p. The bounds are written beside each line (in units of p). (Each follows fr29_mul's contract, result < 1 + 0.005908 a b for operands below a p and b p -- e.g. "< 1.06" where a b < 10 --, not a fixed figure per operand class.) This removes every
 // pack / unpack / conditional subtraction between the 11-16 products of a point operation (about 1.3x fewer instructions).
 struct GAff { Fr x, y; };
 struct GJac { Fr29 X, Y, Z; };  // class A coordinates; Z == 0 (mod p) <=> point at infinity

@@ -161,4 +161,88 @@ int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, u
     return 0;
 } ABI_CATCH
 
+// One routine of the BN254-Fr device library per call, one device lane per item, raw limbs in and out (fr_probe.hpp).
+int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out) try {
+    const uint32_t wi = fr_probe_words(what, false), wo = fr_probe_words(what, true);
+    if (!wi || !wo) return set_err(ACVM_E_INVALID, "no such routine");
+    if (!n_items) return 0;
+    if (!in || !out) return set_err(ACVM_E_INVALID, "null argument");
+    uint32_t *d_in = nullptr, *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_in, (size_t)n_items * wi * 4));
+    if (hipMalloc((void **)&d_out, (size_t)n_items * wo * 4) != hipSuccess) {
+        hipFree(d_in);
+        return set_err(ACVM_E_DEVICE, "hipMalloc failed");
+    }
+    int rc = 0;
+    auto step = [&](hipError_t e, const char *what_) { if (!rc && e != hipSuccess) rc = set_err(ACVM_E_DEVICE, std::string(what_) + ": " + hipGetErrorString(e)); };
+    step(hipMemcpy(d_in, in, (size_t)n_items * wi * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    step(hipMemset(d_out, 0, (size_t)n_items * wo * 4), "hipMemset");
+    if (!rc) launch_fr_probe(nullptr, what, d_in, n_items, uniform18, d_out);
+    step(hipGetLastError(), "fr_probe_kernel");
+    step(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    step(hipMemcpy(out, d_out, (size_t)n_items * wo * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+    hipFree(d_in);
+    hipFree(d_out);
+    return rc;
+} ABI_CATCH
 
+// The shipped inverse_batch_kernel through its launcher on a table made for the call: row k of W = the denominators of job k, job k = {row k, opcode
+// k, inverse slot slot_of[k] (k when null)}, the batch's row stride, event words behind the header a batch gives them (event_words_new).
+int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
+                             uint32_t *event_out, uint32_t *device_count, uint32_t *host_count) try {
+    if (!den || !n_jobs || !B || !inv_out || !event_out || !device_count || !host_count) return set_err(ACVM_E_INVALID, "bad argument");
+    if (slot_of) {  // a permutation of [0, n_jobs): every job owns one row of the inverse table
+        std::vector<uint8_t> seen(n_jobs, 0);
+        for (uint32_t k = 0; k < n_jobs; k++) {
+            if (slot_of[k] >= n_jobs || seen[slot_of[k]]) return set_err(ACVM_E_INVALID, "slot_of is not a permutation");
+            seen[slot_of[k]] = 1;
+        }
+    }
+    const uint64_t Bp = ((uint64_t)B + 63) / 64 * 64;
+    const size_t row = (size_t)2 * Bp, table_bytes = (size_t)n_jobs * row * sizeof(uint4);
+    std::vector<uint4> hW((size_t)n_jobs * row, make_uint4(0, 0, 0, 0));
+    std::vector<uint32_t> stream((size_t)n_jobs * 3), offset(n_jobs);
+    for (uint32_t k = 0; k < n_jobs; k++) {
+        for (uint32_t j = 0; j < B; j++) {
+            const uint32_t *v = den + ((size_t)k * B + j) * 8;
+            hW[(size_t)k * row + j] = make_uint4(v[0], v[1], v[2], v[3]);
+            hW[(size_t)k * row + Bp + j] = make_uint4(v[4], v[5], v[6], v[7]);
+        }
+        stream[3 * (size_t)k] = k;
+        stream[3 * (size_t)k + 1] = k;
+        stream[3 * (size_t)k + 2] = slot_of ? slot_of[k] : k;
+        offset[k] = 3 * k;
+    }
+    struct Mem {
+        uint4 *W = nullptr, *inv = nullptr;
+        uint32_t *stream = nullptr, *offset = nullptr, *event_base = nullptr, *event = nullptr, *h_count = nullptr;
+        ~Mem() {
+            for (void *p : {(void *)W, (void *)inv, (void *)stream, (void *)offset, (void *)event_base})
+                if (p) hipFree(p);
+            if (h_count) hipHostFree(h_count);
+        }
+    } m;
+    HIPCHK(hipMalloc((void **)&m.W, table_bytes));
+    HIPCHK(hipMalloc((void **)&m.inv, table_bytes));
+    HIPCHK(hipMemcpy(m.W, hW.data(), table_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(m.inv, 0, table_bytes));
+    if (int rc = upload(&m.stream, stream)) return rc;
+    if (int rc = upload(&m.offset, offset)) return rc;
+    if (int rc = event_words_new(B, &m.event_base, &m.event, &m.h_count)) return rc;
+    *m.h_count = 0;
+    launch_event_reset(nullptr, m.event, B);
+    launch_inverse_batch(nullptr, m.W, m.inv, Bp, B, m.stream, m.offset, n_jobs, m.event, inv_chunk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(hW.data(), m.inv, table_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(event_out, m.event, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(device_count, m.event - 4, 4, hipMemcpyDeviceToHost));
+    *host_count = *(volatile uint32_t *)m.h_count;
+    for (uint32_t k = 0; k < n_jobs; k++)
+        for (uint32_t j = 0; j < B; j++) {
+            const uint4 lo = hW[(size_t)k * row + j], hi = hW[(size_t)k * row + Bp + j];
+            uint32_t *v = inv_out + ((size_t)k * B + j) * 8;
+            v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+        }
+    return 0;
+} ABI_CATCH

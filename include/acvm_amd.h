@@ -219,6 +219,27 @@ int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, u
  * (a difference against a multiple of p); 11 a -> a^32 (the squaring loop of the square-root chains).
  * in: n_items x (2, 1, 2, 2, 1, 1, 3, 5, 1, 2, 2, 1) x 32 bytes big-endian, values < p; out: n_items x (1, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1) x 32 bytes. */
 int acvm_debug_secp(uint32_t curve, uint32_t what, const uint8_t *in_be32, uint32_t n_items, uint8_t *out_be32);
+/* Component probe of the BN254-Fr field library (acvm_amd/csrc/fr_device.hpp and the byte helpers of ops_common.hpp run ON THE DEVICE against integers:
+ * the tests compare every word with Python, tests/fr_ref.py): one device lane per item, RAW limbs in and out -- S = the storage form, 8 x u32 little-endian,
+ * W = the 29-bit working form, 9 x u32, k = one u32; nothing is converted or reduced on the way, so unreduced representatives go in and the routine's own
+ * result comes out. what (acvm_amd/csrc/fr_probe.hpp): 0 fr_mul S S -> S; 1 fr_mul_portable S S -> S; 2 fr_sqr S -> S; 3 fr_add, 4 fr_sub S S -> S; 5 fr_neg,
+ * 6 fr_inv, 7 fr_inv_eea, 8 fr_to_canonical S -> S; 9 fr_low_limb S -> k limb, k is_byte; 10 fr_is_byte S -> k is_byte, k byte; 11 fr_from_byte k -> S;
+ * 12 fr29_from S -> W; 13 fr29_pack W -> S; 14 fr29_mul, 15 fr29_mul_b W W -> W; 16 fr29_sqr W -> W; 17 fr29_redc_low W -> k; 18 fr29_cond_sub_p W -> W;
+ * 19 fr29_csub W k -> W (k = log2 of the multiple of p, 0..4); 20 fr29_lt2p, 21 fr29_weak, 22 fr29_canon, 23 fr29_norm W -> W; 24 fr29_subl W W k -> W
+ * (k = 1..4); 25 fr29_addl W W -> W; 26 fr29_dbll W -> W; 27 fr29_is_zero_mod_p W -> k; 28 / 29 / 30 fr29_dot<1 / 2 / 3> (W a_t, W b_t) x N -> W;
+ * 31 / 32 fr29_dot_add<1 / 2> (W a_t, W b_t) x N, W h -> W; 33 fr29_dot_add_b<1, 0> as 31; 34 fr29_dot_add_b<2, 0> as 32; 35 fr29_dot_add_b<1, 1>
+ * W a0, W h -> a0 u0 + h; 36 fr29_dot_add_b<2, 2> W a0, W b0, W a1, W h -> a0 b0 + a1 u0 + h; 37 fr29_dot_add_b<2, 3> W a0, W a1, W h -> a0 u0 + a1 u1 + h.
+ * uniform18: the wave-uniform factors u0, u1 of 35..37 (2 x W; null: zeros) -- ONE value per call, handed to the kernel as an argument, because those forms
+ * read them from scalar registers. in: n_items x words-in u32, out: n_items x words-out u32, host memory. */
+int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out);
+/* The inversion batch of the level schedule (inverse_batch_kernel through its launcher, exactly as a solve starts it) on a table made for the call.
+ * den: [n_jobs][B] canonical denominators in the storage form (8 x u32; zero = the instance leaves the generic path at that job). Job k reads row k,
+ * carries opcode index k and owns row slot_of[k] of the inverse table (null: row k; otherwise a permutation of [0, n_jobs)); the rows have the batch's
+ * stride, the event words the header of a batch. inv_chunk: the tuning's jobs per wave. Out: inv_out [n_jobs][B] x 8 u32 = the RAW rows of the
+ * inverse table (row slot_of[k] holds 1 / den[k]), event_out [B] event words, *device_count = the device's count of flagged instances (the word four in
+ * front of the event words), *host_count = the host-mapped counter the same kernels keep. */
+int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
+                             uint32_t *event_out, uint32_t *device_count, uint32_t *host_count);
 
 /* Peak of the ALU roofline of the integer-bound kernels: back-to-back Montgomery products (fr29_mul, the product every
  * kernel uses) on every SIMD, waves_per_simd dependent chains of 2 * iters products interleaved per SIMD; the best of three timed

@@ -159,7 +159,8 @@ def test_empty_and_ragged(oracle):
 
 
 def test_device_field_selftest():
-    """hand-scheduled gfx950 field routines against the portable ones on 2^18 random operand pairs"""
+    """hand-scheduled gfx950 field routines against the portable ones on 2^18 random operand pairs
+    (device code against device code; against Python integers at the edges of the contracts: test_gpu_fr_probe.py, test_gpu_inverse_batch.py)"""
     import acvm_amd
     assert acvm_amd.selftest(1 << 18, 7) == 0
 
