@@ -19,7 +19,7 @@ STATUS_SOLVED, STATUS_IN_PROGRESS, STATUS_FAILURE, STATUS_REQUIRES_FOREIGN_CALL 
 (ERR_NONE, ERR_MISSING_ASSIGNMENT, ERR_TOO_MANY_UNKNOWNS, ERR_UNSUPPORTED_BLACKBOX, ERR_UNSATISFIED, ERR_INDEX_OOB,
  ERR_BLACKBOX_FAILED, ERR_BRILLIG_FAILED, ERR_PANIC, ERR_DEVICE_LIMIT) = range(10)
 LIMIT_BRILLIG_STEPS, LIMIT_BRILLIG_CALL_DEPTH, LIMIT_BRILLIG_MEMORY, LIMIT_DEVICE_MEMORY = 1, 2, 3, 4
-# acvm_batch_export_device: ACVM_ENC_* / ACVM_LAYOUT_*
+# acvm_batch_export_device / acvm_batch_import_device: ACVM_ENC_* / ACVM_LAYOUT_*
 ENC_BE32, ENC_LE32, ENC_MONT256_LE = 0, 1, 2
 LAYOUT_INSTANCE_MAJOR, LAYOUT_WITNESS_MAJOR = 0, 1
 
@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "acvm_device_release_tables", "acvm_circuit_opcode_kinds", "acvm_batch_error_expression", "acvm_debug_stream_rate", "acvm_node_new", "acvm_node_free", "acvm_node_tile_instances", "acvm_node_num_devices", "acvm_node_solve", "acvm_node_stats",
     "acvm_debug_cpulist", "acvm_debug_device_locality", "acvm_debug_plan_fingerprint", "acvm_circuit_plans_built", "acvm_circuit_check_schedule", "acvm_batch_digest_blake2s",
     "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
+    "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
 ]
 
 
@@ -57,6 +58,11 @@ class ExportDesc(C.Structure):
     """acvm_export_desc_t"""
     _fields_ = [("encoding", C.c_uint32), ("layout", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32), ("witnesses", C.POINTER(C.c_uint32)),
                 ("n_witnesses", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class ImportDesc(C.Structure):
+    """acvm_import_desc_t"""
+    _fields_ = [("encoding", C.c_uint32), ("layout", C.c_uint32), ("columns", C.POINTER(C.c_uint32)), ("n_columns", C.c_uint32), ("stride", C.c_uint64)]
 
 
 class Result(C.Structure):
@@ -319,6 +325,9 @@ def lib():
     L.acvm_device_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.acvm_device_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.acvm_batch_export_device.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has neither)
+        L.acvm_batch_import_device.argtypes = [C.c_void_p, C.POINTER(ImportDesc), C.c_void_p]
+        L.acvm_batch_solve_then_import_ex.argtypes = [C.c_void_p, C.POINTER(ImportDesc), C.c_void_p]
     L.acvm_batch_solve_opcode.argtypes = [C.c_void_p]
     L.acvm_bb_stubbed.restype = C.c_void_p
     L.acvm_bb_dummy.restype = C.c_void_p
@@ -746,9 +755,13 @@ class Batch:
             raise ValueError("initial witness buffer has the wrong size")
         _check(lib().acvm_batch_set_initial_witness(self._h, buf.ctypes.data))
 
-    def solve(self, then_import: int = 0) -> int:
+    def solve(self, then_import: int = 0, then_import_desc=None) -> int:
         """ACVM::solve for every instance; then_import: device pointer of the NEXT tile's inputs, imported behind the solve when no instance
-        left the generic path (acvm_batch_solve_then_import)"""
+        left the generic path (acvm_batch_solve_then_import). then_import_desc: how that buffer is to be read, as a dict of import_device's
+        keywords (encoding, layout, columns, n_columns, stride): acvm_batch_solve_then_import_ex"""
+        if then_import and then_import_desc is not None:
+            desc, _keep = self._import_desc(**then_import_desc)
+            return _check(lib().acvm_batch_solve_then_import_ex(self._h, C.byref(desc), then_import))
         if then_import:
             return _check(lib().acvm_batch_solve_then_import(self._h, then_import))
         return _check(lib().acvm_batch_solve(self._h))
@@ -760,6 +773,26 @@ class Batch:
     def set_initial_witness_device(self, d_ptr: int):
         """values already resident on the device (same layout as set_initial_witness), e.g. a slice of a DeviceBuffer."""
         _check(lib().acvm_batch_set_initial_witness_device(self._h, d_ptr))
+
+    def _import_desc(self, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, columns=None, n_columns=None, stride=0):
+        """(acvm_import_desc_t, the array its column pointer refers to)"""
+        desc = ImportDesc(encoding=encoding, layout=layout, n_columns=0, stride=stride)
+        arr = None
+        if columns is not None:
+            cols = list(columns)
+            if len(cols) != len(self.ids):
+                raise ValueError("columns needs one entry per initial witness")
+            arr = (C.c_uint32 * max(len(cols), 1))(*cols)
+            desc.columns, desc.n_columns = arr, len(cols) if n_columns is None else n_columns
+        return desc, arr
+
+    def import_device(self, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, columns=None, n_columns=None, stride=0):
+        """The initial witnesses read from device memory at d_ptr (acvm_batch_import_device), the mirror image of export_device: 32 bytes per
+        element in `encoding`, element (instance i, column c) where `layout` and `stride` (in elements, 0 = dense) put it; columns: per initial
+        witness (in the order of the ids the batch was created with) the column of the buffer that holds it, None = column k; n_columns: the
+        buffer's width in columns (default: len(columns)). The defaults are set_initial_witness_device."""
+        desc, _keep = self._import_desc(encoding, layout, columns, n_columns, stride)
+        _check(lib().acvm_batch_import_device(self._h, C.byref(desc), d_ptr))
 
     def reset(self):
         _check(lib().acvm_batch_reset(self._h))

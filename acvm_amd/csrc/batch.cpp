@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "batch_internal.hpp"
+#include "export_encode.hpp"
 
 static thread_local std::string g_last_error;
 int set_err(int code, const std::string &msg) {
@@ -496,15 +497,76 @@ acvm_batch_t *acvm_batch_new_ex(const acvm_circuit_t *c, const acvm_bb_solver_t 
 } ABI_CATCH_PTR
 void acvm_batch_free(acvm_batch_t *b) { delete b; }
 
-int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported) {
+ImportSpec import_spec_plain(const acvm_batch *b) {
+    ImportSpec sp;
+    sp.encoding = EXPORT_ENC_BE32;
+    sp.layout = EXPORT_INSTANCE_MAJOR;
+    sp.n_columns = (uint32_t)b->plan().initial_ids.size();
+    sp.stride = sp.n_columns;
+    return sp;
+}
+int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out) {
+    if (!d) return set_err(ACVM_E_INVALID, "null argument");
+    if (d->encoding >= EXPORT_N_ENC) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
+    if (d->layout >= EXPORT_N_LAYOUT) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(d->layout));
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
+    if (n_in && !d_values) return set_err(ACVM_E_INVALID, "null values");
+    ImportSpec sp;
+    sp.encoding = d->encoding;
+    sp.layout = d->layout;
+    sp.has_columns = d->columns != nullptr;
+    sp.n_columns = sp.has_columns ? d->n_columns : n_in;
+    if (sp.has_columns) {
+        sp.columns.assign(d->columns, d->columns + n_in);
+        for (uint32_t k = 0; k < n_in; k++)
+            if (sp.columns[k] >= sp.n_columns)
+                return set_err(ACVM_E_INVALID, "column " + std::to_string(sp.columns[k]) + " of initial witness " + std::to_string(k) + " is not below n_columns " + std::to_string(sp.n_columns));
+    }
+    const uint64_t dense = export_dense_stride(sp.layout, b->B, sp.n_columns);
+    sp.stride = d->stride ? d->stride : dense;
+    if (sp.stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
+    // (the byte offset of the last element fits 63 bits)
+    const unsigned __int128 rows = sp.layout == EXPORT_WITNESS_MAJOR ? sp.n_columns : b->B;
+    if (rows * sp.stride > ((unsigned __int128)1 << 57)) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is beyond any device buffer");
+    sp.plain = sp.encoding == EXPORT_ENC_BE32 && sp.layout == EXPORT_INSTANCE_MAJOR && !sp.has_columns && sp.stride == n_in;
+    // (the plain shape IS acvm_batch_set_initial_witness_device, which reads any pointer: import_witness_kernel<false>)
+    if (!sp.plain && ((uintptr_t)d_values & 15u)) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
+    *out = std::move(sp);
+    return 0;
+}
+// One small host-to-device copy when the list differs from the last call's, none otherwise. The stream is waited for first: an import enqueued
+// behind the last solve may still be reading the old list.
+int import_columns_ready(acvm_batch *b, const ImportSpec &spec) {
+    if (!spec.has_columns || spec.columns.empty()) return 0;
+    if (b->d_import_cols && b->import_cols == spec.columns) return 0;
     HIPCHK(hipSetDevice(b->device));
-    // (acvm_batch_solve_then_import put exactly this import behind the previous solve, and it ran: the rows are there, in stream order)
-    const bool already = b->next_imported && b->next_inputs == d_values_be32;
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->import_cols.clear();
+    if (spec.columns.size() > b->import_cols_cap) {
+        if (b->d_import_cols) { hipFree(b->d_import_cols); b->d_import_cols = nullptr; b->import_cols_cap = 0; }
+        HIPCHK(hipMalloc((void **)&b->d_import_cols, spec.columns.size() * 4));
+        b->import_cols_cap = spec.columns.size();
+    }
+    HIPCHK(hipMemcpy(b->d_import_cols, spec.columns.data(), spec.columns.size() * 4, hipMemcpyHostToDevice));
+    b->import_cols = spec.columns;
+    return 0;
+}
+bool batch_launch_import(acvm_batch *b, const ImportSpec &spec, const void *d_values, const uint32_t *gate) {
+    const uint32_t *rows = b->reuse() ? b->d_init_rows : b->d_init_ids;
+    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
+    if (spec.plain) return launch_import(b->stream, b->d_W, b->Bp, b->B, (const uint8_t *)d_values, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
+    const ImportDevice x{spec.encoding, spec.layout, spec.has_columns ? b->d_import_cols : nullptr, spec.stride, d_values};
+    return launch_import_device(b->stream, x, b->d_W, b->Bp, b->B, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
+}
+
+int batch_import_spec_async(acvm_batch *b, const ImportSpec &spec, const void *d_values, hipEvent_t imported) {
+    HIPCHK(hipSetDevice(b->device));
+    // (acvm_batch_solve_then_import(_ex) put exactly this import behind the previous solve, and it ran: the rows are there, in stream order)
+    const bool already = b->next_imported && b->next_inputs == d_values && b->next_spec == spec;
     b->next_imported = false;
     b->next_inputs = nullptr;
-    if (!already)
-        b->events_fresh = launch_import(b->stream, b->d_W, b->Bp, b->B, (const uint8_t *)d_values_be32, b->reuse() ? b->d_init_rows : b->d_init_ids,
-                                        (uint32_t)b->plan().initial_ids.size(), nullptr, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
+    if (!already) b->events_fresh = batch_launch_import(b, spec, d_values, nullptr);
     HIPCHK(hipGetLastError());
     if (imported) HIPCHK(hipEventRecord(imported, b->stream));
     b->inputs_set = true;
@@ -513,11 +575,23 @@ int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t impo
     clear_fc_store(b);
     return 0;
 }
+int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported) { return batch_import_spec_async(b, import_spec_plain(b), d_values_be32, imported); }
 int acvm_batch_set_initial_witness_device(acvm_batch_t *b, const void *d_values_be32) try {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    const bool already = b->next_imported && b->next_inputs == d_values_be32;
+    const bool already = b->next_imported && b->next_inputs == d_values_be32 && b->next_spec == import_spec_plain(b);
     if (int rc = batch_import_async(b, d_values_be32, nullptr)) return rc;
     // the caller may reuse its buffer as soon as the call returns (an import that ran behind the previous solve left the buffer alone since)
+    if (!already) HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+} ABI_CATCH
+// The import as the mirror image of acvm_batch_export_device: any encoding, layout, stride and column list (include/acvm_amd.h).
+int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values) try {
+    ImportSpec sp;
+    if (int rc = import_spec_of(b, d, d_values, &sp)) return rc;
+    const bool already = b->next_imported && b->next_inputs == d_values && b->next_spec == sp;
+    if (!already)
+        if (int rc = import_columns_ready(b, sp)) return rc;
+    if (int rc = batch_import_spec_async(b, sp, d_values, nullptr)) return rc;
     if (!already) HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 } ABI_CATCH

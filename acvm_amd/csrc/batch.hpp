@@ -61,6 +61,22 @@ struct acvm_circuit {
 // the plan of `c` for these options: from the circuit's cache, or built (and cached) now. Never null; a refused circuit's plan has `unsupported` set.
 std::shared_ptr<const Plan> plan_for(const acvm_circuit *c, const uint32_t *initial_ids, uint32_t n_initial, const acvm::PlanOpts &opts);
 
+// One import of initial witnesses from a device buffer, checked and normalised (batch.cpp import_spec_of): what acvm_batch_import_device and
+// acvm_batch_solve_then_import_ex describe by an acvm_import_desc_t, and -- `plain` -- the one shape of acvm_batch_set_initial_witness_device /
+// acvm_batch_solve_then_import: BE32, instance-major, dense, no column list (kernels.hip import_witness_kernel, any alignment). The handle keeps a
+// COPY of the one it enqueued behind a solve: the following import costs nothing only if pointer and spec are both the same.
+struct ImportSpec {
+    uint32_t encoding = 0, layout = 0;
+    bool has_columns = false, plain = true;
+    std::vector<uint32_t> columns;  // (has_columns) one per initial witness
+    uint32_t n_columns = 0;
+    uint64_t stride = 0;            // as launched: never 0
+    bool operator==(const ImportSpec &o) const {
+        return encoding == o.encoding && layout == o.layout && has_columns == o.has_columns && plain == o.plain && columns == o.columns && n_columns == o.n_columns &&
+               stride == o.stride;
+    }
+};
+
 struct acvm_batch {
     // The static plan: immutable once built and shared -- by the handles of a node (node.cpp: one plan per circuit, not one per device) and
     // by every handle created for the same (circuit, initial ids, options, tuning) through the circuit's plan cache (batch.cpp plan_for).
@@ -85,7 +101,7 @@ struct acvm_batch {
     uint32_t *d_event = nullptr;       // the event words; EVENT_HDR_WORDS in front of them: the count of flagged instances and the device address of h_flag_count
     uint32_t *d_event_base = nullptr;  // (the allocation)
     uint32_t *h_flag_count = nullptr;  // pinned, device-mapped: the same count where the host reads it after a synchronisation
-    // The one rule of events_fresh: true only between an import that wrote the event words ("nobody flagged": kernels.hip import_witness_kernel)
+    // The one rule of events_fresh: true only between an import that wrote the event words ("nobody flagged": kernels.hip import_witness_kernel, kernels_import.hip)
     // and the first thing enqueued behind it; the level solve that finds it set skips its reset launch. Set where launch_import says it launched
     // (not for a circuit without initial witnesses); cleared by everything else that writes d_event or changes what it covers: the level
     // schedule's reset step, the fill of the exact-only solve and of solve_stepping, acvm_batch_reset, batch_set_live_count.
@@ -153,6 +169,11 @@ struct acvm_batch {
     // the next tile's import behind this solve (acvm_batch_solve_then_import): the caller's device buffer, and whether the import ran
     const void *next_inputs = nullptr;
     bool next_imported = false;
+    ImportSpec next_spec;  // how next_inputs was read (acvm_batch_solve_then_import_ex; plain for acvm_batch_solve_then_import)
+    // the column list of the last import that had one, on the device: uploaded again only when it changes (batch.cpp import_columns_ready)
+    std::vector<uint32_t> import_cols;
+    uint32_t *d_import_cols = nullptr;
+    size_t import_cols_cap = 0;
     hipEvent_t ev_counted = nullptr;  // behind the event count of a solve: what the host waits for instead of the whole stream
     bool holds_tables = false;  // a reference on the device's lookup-table set (grumpkin_host.hpp device_tables_retain)
     // caller-supplied BlackBoxFunctionSolver
@@ -226,6 +247,7 @@ struct acvm_batch {
         if (d_ped_seed) hipFree(d_ped_seed);
         if (d_stage) hipFree(d_stage);
         if (d_fetch) hipFree(d_fetch);
+        if (d_import_cols) hipFree(d_import_cols);
         if (stream_x) { hipStreamSynchronize(stream_x); hipStreamDestroy(stream_x); }
         if (ev_x_ready) hipEventDestroy(ev_x_ready);
         for (int k = 0; k < (int)N_CLS; k++)
@@ -260,6 +282,8 @@ int batch_set_live_count(acvm_batch *b, uint32_t n);
 // acvm_batch_set_initial_witness_device without the wait: the import is enqueued on the handle's stream and `imported` recorded behind it;
 // the caller keeps d_values_be32 untouched until that event has fired.
 int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported);
+// the same for any checked import (batch_import_async is this with the plain spec); a spec with a column list needs import_columns_ready first
+int batch_import_spec_async(acvm_batch *b, const ImportSpec &spec, const void *d_values, hipEvent_t imported);
 // waits for the exact job in flight (if any) and moves its outcome into *out (cleared first)
 int batch_finish_pending(acvm_batch *b, ExactOutcome *out);
 // the outcome of the previous solve's exact job, which the last acvm_batch_solve collected on its way (moved into *out; empty if none)

@@ -22,9 +22,19 @@ void plan_stats(const Plan &p, acvm_stats_t *out);
 // address of *h_flag_count, pinned and device-mapped, at event[-2..-1]); the words themselves are left for launch_event_reset
 int event_words_new(uint32_t B, uint32_t **base, uint32_t **event, uint32_t **h_flag_count);
 
+// the plain spec of this handle (what acvm_batch_set_initial_witness_device reads)
+ImportSpec import_spec_plain(const acvm_batch *b);
+// an acvm_import_desc_t checked against the handle and the pointer: 0 and *out, or ACVM_E_INVALID
+int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out);
+// the spec's column list is on the device (nothing to do for a spec without one, or for the list of the last call)
+int import_columns_ready(acvm_batch *b, const ImportSpec &spec);
+// THE launch of an import on the handle's stream, whatever the entry point: the old kernel for the plain spec, the import_device kernels otherwise.
+// gate: null, or the device word that must be zero for the import to happen. Returns whether the launch wrote the event words (events_fresh's rule).
+bool batch_launch_import(acvm_batch *b, const ImportSpec &spec, const void *d_values, const uint32_t *gate);
+
 // ---- batch_schedule.cpp
-// ACVM::solve for the batch; next_inputs: acvm_batch_solve_then_import
-int batch_solve_impl(acvm_batch *b, const void *next_inputs);
+// ACVM::solve for the batch; next_inputs: acvm_batch_solve_then_import(_ex), read as next_spec says (null: nothing is imported behind the solve)
+int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *next_spec);
 
 // ---- batch_exact.cpp
 int ensure_slow_capacity(acvm_batch *b, uint32_t n);

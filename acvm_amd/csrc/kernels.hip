@@ -5,7 +5,7 @@
 //  arith_level_kernel      ArithmeticSolver::solve (pwg/arithmetic.rs:27-127) for one dependency level,
 //                          one lane per witness instance, generic-instance plan from plan.cpp
 //  (the exact in-order kernels and every non-arithmetic opcode live in kernels_ops.hip / kernels_hash.hip /
-//   kernels_grumpkin.hip / kernels_brillig.hip)
+//   kernels_grumpkin.hip / kernels_brillig.hip; the import from a caller's device buffer in kernels_import.hip)
 //  export_witness_kernel   FieldElement::to_be_bytes (generic_ark.rs:269-277) for witness_map()/finalize()
 //  export_device_*_kernel  the same map left in device memory for a GPU consumer: big-endian, little-endian limbs or Montgomery-256,
 //                          instance-major (through LDS) or witness-major (streaming)

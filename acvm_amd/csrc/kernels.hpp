@@ -82,6 +82,16 @@ struct Unscale {
 // event_reset: null, or the batch's event words: the import also leaves them "nobody flagged" (returns true when it did: the solve behind it needs no reset launch)
 bool launch_import(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint8_t *in, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
                    const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
+// acvm_batch_import_device: the initial witnesses from the caller's device buffer in any encoding, layout, stride and column list of the device export
+// (import_decode.hpp). The other arguments and the return value as launch_import.
+struct ImportDevice {
+    uint32_t encoding, layout;
+    const uint32_t *columns;  // device array, one column per input; null: input k is column k
+    uint64_t stride;          // in elements, >= the layout's dense stride
+    const void *in;           // 16-byte aligned
+};
+bool launch_import_device(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
+                          const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
 void launch_export(hipStream_t s, const uint4 *W, uint64_t Bp, uint32_t first, uint32_t n, const uint32_t *sel, uint32_t n_sel,
                    uint8_t *out, const Unscale &u, const uint32_t *row_of = nullptr);
 // acvm_batch_export_device: the map of instances [first, first + n) x the witness list into the caller's device buffer (export_encode.hpp:

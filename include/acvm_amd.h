@@ -503,6 +503,36 @@ typedef struct {
     uint64_t stride;
 } acvm_export_desc_t;
 int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned);
+/*
+ * The way in as the mirror image of that way out: ACVM::new's initial WitnessMap (pwg/mod.rs:146-156) read from DEVICE memory of the caller in
+ * the encoding and layout its producer writes -- a prover's wire columns (ACVM_ENC_MONT256_LE, ACVM_LAYOUT_WITNESS_MAJOR), or the buffer
+ * acvm_batch_export_device of another batch filled, whole map and all: the column list picks the initial witnesses out of it.
+ *   - Element (instance i, column c) lies at (i * stride + c) * 32 instance-major and at (c * stride + i) * 32 witness-major; i runs over the live
+ *     instances [0, B) (acvm_batch_set_instances is honoured). stride in elements, 0 = dense: n_columns instance-major, the live B witness-major.
+ *     The bytes between rows are never read.
+ *   - columns: HOST array, one entry per initial witness in the order of initial_ids given to acvm_batch_new: columns[k] = the column of the
+ *     buffer that holds it; repeats allowed. NULL: column k, and n_columns is taken as n_initial. The list is copied before the call returns.
+ *   - Every 256-bit string is accepted, as by acvm_batch_set_initial_witness: BE32 is int(bytes, big) mod p, LE32 int(bytes, little) mod p,
+ *     MONT256_LE m * 2^-256 mod p for m = int(bytes, little) -- any m < 2^256, m >= p is not an error. The inverse of what the export writes.
+ *   - ACVM_E_INVALID: a stride below the dense one, columns[k] >= n_columns, an unknown encoding or layout, a null descriptor, null values with
+ *     n_initial > 0, and a d_values that is not 16-byte aligned -- except for BE32, instance-major, columns == NULL, dense: that descriptor IS
+ *     acvm_batch_set_initial_witness_device, takes the same kernel and reads any pointer. A refused call leaves the handle as it was.
+ *   - Leaves the handle in the state acvm_batch_set_initial_witness_device leaves it in and returns after the batch's stream is synchronised;
+ *     at most one small host-to-device copy is made (the column list, when it differs from the last call's).
+ * acvm_batch_solve_then_import_ex is acvm_batch_solve_then_import for such a buffer: the same gate, the same refusals, a plain solve in the same
+ * cases. The following acvm_batch_import_device costs nothing only when the pointer AND the descriptor's contents, column list included, are the
+ * same (the library keeps a copy of the descriptor, not the caller's pointer); anything else imports again.
+ * Not here: device inputs for acvm_node_solve, an asynchronous variant, a mask of unassigned inputs (every instance of a batch assigns the same
+ * ids); the host import and the two entry points above keep their behaviour.
+ */
+typedef struct {
+    uint32_t encoding, layout;   /* ACVM_ENC_*, ACVM_LAYOUT_* */
+    const uint32_t *columns;     /* HOST array of n_initial entries, or NULL */
+    uint32_t n_columns;          /* width of the caller's buffer in columns (ignored when columns == NULL: n_initial) */
+    uint64_t stride;             /* elements; 0 = dense */
+} acvm_import_desc_t;
+int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values);
+int acvm_batch_solve_then_import_ex(acvm_batch_t *b, const acvm_import_desc_t *d_next, const void *d_next_values);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):
