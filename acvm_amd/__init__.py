@@ -21,7 +21,9 @@ STATUS_SOLVED, STATUS_IN_PROGRESS, STATUS_FAILURE, STATUS_REQUIRES_FOREIGN_CALL 
 LIMIT_BRILLIG_STEPS, LIMIT_BRILLIG_CALL_DEPTH, LIMIT_BRILLIG_MEMORY, LIMIT_DEVICE_MEMORY = 1, 2, 3, 4
 # acvm_batch_export_device / acvm_batch_import_device: ACVM_ENC_* / ACVM_LAYOUT_*
 ENC_BE32, ENC_LE32, ENC_MONT256_LE = 0, 1, 2
+ENC_U8, ENC_U16, ENC_U32, ENC_U64, ENC_U128 = 16, 17, 18, 19, 20  # unsigned little-endian integers of 1 .. 16 bytes per element
 LAYOUT_INSTANCE_MAJOR, LAYOUT_WITNESS_MAJOR = 0, 1
+LAYOUT_BROADCAST = 16  # parts of import_device_parts only: one element per column, the value of every instance
 
 # every symbol include/acvm_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -43,6 +45,7 @@ ABI_SYMBOLS = [
     "acvm_debug_cpulist", "acvm_debug_device_locality", "acvm_debug_plan_fingerprint", "acvm_circuit_plans_built", "acvm_circuit_check_schedule", "acvm_batch_digest_blake2s",
     "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
     "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
+    "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
 ]
 
 
@@ -63,6 +66,17 @@ class ExportDesc(C.Structure):
 class ImportDesc(C.Structure):
     """acvm_import_desc_t"""
     _fields_ = [("encoding", C.c_uint32), ("layout", C.c_uint32), ("columns", C.POINTER(C.c_uint32)), ("n_columns", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class ImportPart(C.Structure):
+    """acvm_import_part_t"""
+    _fields_ = [("d_values", C.c_void_p), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("positions", C.POINTER(C.c_uint32)),
+                ("columns", C.POINTER(C.c_uint32)), ("n", C.c_uint32), ("n_columns", C.c_uint32), ("stride", C.c_uint64)]
+
+
+def element_size(encoding):
+    """bytes per element of an ACVM_ENC_*: 32, or the width of a narrow integer"""
+    return 1 << (encoding - ENC_U8) if ENC_U8 <= encoding <= ENC_U128 else 32
 
 
 class Result(C.Structure):
@@ -328,6 +342,10 @@ def lib():
     if hasattr(L, "acvm_batch_import_device"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has neither)
         L.acvm_batch_import_device.argtypes = [C.c_void_p, C.POINTER(ImportDesc), C.c_void_p]
         L.acvm_batch_solve_then_import_ex.argtypes = [C.c_void_p, C.POINTER(ImportDesc), C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_parts"):
+        L.acvm_batch_import_device_parts.argtypes = [C.c_void_p, C.POINTER(ImportPart), C.c_uint32]
+        L.acvm_debug_import_list_copies.restype = C.c_uint64
+        L.acvm_debug_import_list_copies.argtypes = [C.c_void_p]
     L.acvm_batch_solve_opcode.argtypes = [C.c_void_p]
     L.acvm_bb_stubbed.restype = C.c_void_p
     L.acvm_bb_dummy.restype = C.c_void_p
@@ -788,11 +806,36 @@ class Batch:
 
     def import_device(self, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, columns=None, n_columns=None, stride=0):
         """The initial witnesses read from device memory at d_ptr (acvm_batch_import_device), the mirror image of export_device: 32 bytes per
-        element in `encoding`, element (instance i, column c) where `layout` and `stride` (in elements, 0 = dense) put it; columns: per initial
+        element in `encoding` (ENC_U8 .. ENC_U128: the integer's 1 .. 16 bytes, little-endian, d_ptr aligned to that size), element (instance i, column c) where `layout` and `stride` (in elements, 0 = dense) put it; columns: per initial
         witness (in the order of the ids the batch was created with) the column of the buffer that holds it, None = column k; n_columns: the
         buffer's width in columns (default: len(columns)). The defaults are set_initial_witness_device."""
         desc, _keep = self._import_desc(encoding, layout, columns, n_columns, stride)
         _check(lib().acvm_batch_import_device(self._h, C.byref(desc), d_ptr))
+
+    def import_device_parts(self, parts):
+        """One import from several device buffers (acvm_batch_import_device_parts). parts: dicts with d_ptr, positions (which initial witnesses,
+        as positions in the ids the batch was created with, the part supplies) and import_device's keywords encoding, layout (LAYOUT_BROADCAST
+        too: one element per column, the value of every instance), columns, n_columns, stride. Every initial witness needs exactly one part."""
+        arr = (ImportPart * max(len(parts), 1))()
+        keep = []
+        for q, part in enumerate(parts):
+            pos = list(part["positions"])
+            p_arr = (C.c_uint32 * max(len(pos), 1))(*pos)
+            keep.append(p_arr)
+            arr[q].d_values, arr[q].encoding, arr[q].layout = part["d_ptr"], part.get("encoding", ENC_BE32), part.get("layout", LAYOUT_INSTANCE_MAJOR)
+            arr[q].positions, arr[q].n, arr[q].n_columns, arr[q].stride = p_arr, len(pos), 0, part.get("stride", 0)
+            if part.get("columns") is not None:
+                cols = list(part["columns"])
+                if len(cols) != len(pos):
+                    raise ValueError("columns needs one entry per position of the part")
+                c_arr = (C.c_uint32 * max(len(cols), 1))(*cols)
+                keep.append(c_arr)
+                arr[q].columns, arr[q].n_columns = c_arr, len(cols) if part.get("n_columns") is None else part["n_columns"]
+        _check(lib().acvm_batch_import_device_parts(self._h, arr, len(parts)))
+
+    def import_list_copies(self) -> int:
+        """host-to-device copies of import_device_parts' lists this handle has made (acvm_debug_import_list_copies)"""
+        return lib().acvm_debug_import_list_copies(self._h)
 
     def reset(self):
         _check(lib().acvm_batch_reset(self._h))
@@ -868,8 +911,8 @@ class Batch:
 
     def export_device(self, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, witnesses=None, first=0, n=None, stride=0, d_assigned=None):
         """The map of instances [first, first + n) written into device memory at d_ptr (acvm_batch_export_device): 32 bytes per element in
-        `encoding`, element (instance i, list position k) where `layout` and `stride` (in elements, 0 = dense) put it; witnesses: list of
-        indices, None = the whole map; d_assigned: device pointer of the 0 / 1 mask bytes, or None. Nothing is copied to the host."""
+        `encoding` (ENC_U8 .. ENC_U128: the low 1 .. 16 bytes of the value, little-endian; mask 2 = the value does not fit), element (instance i, list position k) where `layout` and `stride` (in elements, 0 = dense) put it; witnesses: list of
+        indices, None = the whole map; d_assigned: device pointer of the mask bytes (0 / 1, for a narrow encoding 0 / 1 / 2), or None. Nothing is copied to the host."""
         n = self.B - first if n is None else n
         desc = ExportDesc(encoding=encoding, layout=layout, first=first, n=n, stride=stride)
         if witnesses is not None:

@@ -505,35 +505,48 @@ ImportSpec import_spec_plain(const acvm_batch *b) {
     sp.stride = sp.n_columns;
     return sp;
 }
-int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out) {
-    if (!d) return set_err(ACVM_E_INVALID, "null argument");
-    if (d->encoding >= EXPORT_N_ENC) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
-    if (d->layout >= EXPORT_N_LAYOUT) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(d->layout));
+// The checks every described buffer gets, for the n inputs it supplies (all initial witnesses for a descriptor, a part's positions for a part).
+// part: the broadcast layout is allowed, and the plain shape's exemption from the alignment rule is not.
+static int import_spec_check(const acvm_batch *b, uint32_t encoding, uint32_t layout, const uint32_t *columns, uint32_t n, uint32_t n_columns, uint64_t stride,
+                             const void *d_values, bool part, ImportSpec *out) {
+    if (!export_enc_is_valid(encoding)) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(encoding));
+    if (layout >= EXPORT_N_LAYOUT && !(part && layout == EXPORT_LAYOUT_BROADCAST)) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(layout));
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
-    if (n_in && !d_values) return set_err(ACVM_E_INVALID, "null values");
+    if (n && !d_values) return set_err(ACVM_E_INVALID, "null values");
     ImportSpec sp;
-    sp.encoding = d->encoding;
-    sp.layout = d->layout;
-    sp.has_columns = d->columns != nullptr;
-    sp.n_columns = sp.has_columns ? d->n_columns : n_in;
+    sp.encoding = encoding;
+    sp.layout = layout;
+    sp.elem_size = export_element_size(encoding);
+    sp.has_columns = columns != nullptr;
+    sp.n_columns = sp.has_columns ? n_columns : n;
     if (sp.has_columns) {
-        sp.columns.assign(d->columns, d->columns + n_in);
-        for (uint32_t k = 0; k < n_in; k++)
+        sp.columns.assign(columns, columns + n);
+        for (uint32_t k = 0; k < n; k++)
             if (sp.columns[k] >= sp.n_columns)
                 return set_err(ACVM_E_INVALID, "column " + std::to_string(sp.columns[k]) + " of initial witness " + std::to_string(k) + " is not below n_columns " + std::to_string(sp.n_columns));
     }
-    const uint64_t dense = export_dense_stride(sp.layout, b->B, sp.n_columns);
-    sp.stride = d->stride ? d->stride : dense;
-    if (sp.stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
-    // (the byte offset of the last element fits 63 bits)
-    const unsigned __int128 rows = sp.layout == EXPORT_WITNESS_MAJOR ? sp.n_columns : b->B;
-    if (rows * sp.stride > ((unsigned __int128)1 << 57)) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is beyond any device buffer");
-    sp.plain = sp.encoding == EXPORT_ENC_BE32 && sp.layout == EXPORT_INSTANCE_MAJOR && !sp.has_columns && sp.stride == n_in;
+    if (layout == EXPORT_LAYOUT_BROADCAST) sp.stride = 1;  // (ignored: element c lies at c * size)
+    else {
+        const uint64_t dense = export_dense_stride(sp.layout, b->B, sp.n_columns);
+        sp.stride = stride ? stride : dense;
+        if (sp.stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
+        // (the byte offset of the last element fits 63 bits)
+        const unsigned __int128 rows = sp.layout == EXPORT_WITNESS_MAJOR ? sp.n_columns : b->B;
+        if (rows * sp.stride > ((unsigned __int128)1 << 57)) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is beyond any device buffer");
+    }
+    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
+    sp.plain = !part && sp.encoding == EXPORT_ENC_BE32 && sp.layout == EXPORT_INSTANCE_MAJOR && !sp.has_columns && sp.stride == n_in;
     // (the plain shape IS acvm_batch_set_initial_witness_device, which reads any pointer: import_witness_kernel<false>)
-    if (!sp.plain && ((uintptr_t)d_values & 15u)) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
+    const uint32_t align = sp.elem_size < 16u ? sp.elem_size : 16u;
+    if (!sp.plain && ((uintptr_t)d_values & (align - 1u)))
+        return set_err(ACVM_E_INVALID, sp.elem_size == 32u ? std::string("d_values must be 16-byte aligned") : "d_values must be aligned to the element size, " + std::to_string(sp.elem_size) + " bytes");
     *out = std::move(sp);
     return 0;
+}
+int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out) {
+    if (!d) return set_err(ACVM_E_INVALID, "null argument");
+    // (encoding and layout are judged before the batch: import_spec_check)
+    return import_spec_check(b, d->encoding, d->layout, d->columns, b ? (uint32_t)b->plan().initial_ids.size() : 0u, d->n_columns, d->stride, d_values, false, out);
 }
 // One small host-to-device copy when the list differs from the last call's, none otherwise. The stream is waited for first: an import enqueued
 // behind the last solve may still be reading the old list.
@@ -557,6 +570,7 @@ bool batch_launch_import(acvm_batch *b, const ImportSpec &spec, const void *d_va
     const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
     if (spec.plain) return launch_import(b->stream, b->d_W, b->Bp, b->B, (const uint8_t *)d_values, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
     const ImportDevice x{spec.encoding, spec.layout, spec.has_columns ? b->d_import_cols : nullptr, spec.stride, d_values};
+    if (spec.elem_size != 32u) return launch_import_typed(b->stream, x, b->d_W, b->Bp, b->B, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
     return launch_import_device(b->stream, x, b->d_W, b->Bp, b->B, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
 }
 
@@ -595,6 +609,85 @@ int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const
     if (!already) HIPCHK(hipStreamSynchronize(b->stream));
     return 0;
 } ABI_CATCH
+
+// One import from several buffers (include/acvm_amd.h): every part is checked like a descriptor, then the parts are launched one after the
+// other through the launchers of batch_launch_import, each with the rows, planes and columns of ITS inputs. All lists of the call travel in one
+// buffer -- per part: rows, planes (circuits with byte planes), columns (parts with a list) -- which is copied only when it differs from the
+// last call's. The event reset is given to exactly one launch.
+int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts) try {
+    if (n_parts && !parts) return set_err(ACVM_E_INVALID, "null argument");
+    std::vector<ImportSpec> specs(n_parts);
+    for (uint32_t q = 0; q < n_parts; q++) {
+        const acvm_import_part_t &pt = parts[q];
+        if (int rc = import_spec_check(b, pt.encoding, pt.layout, pt.columns, pt.n, pt.n_columns, pt.stride, pt.d_values, true, &specs[q])) {
+            return set_err(rc, "part " + std::to_string(q) + ": " + acvm_last_error());
+        }
+        if (pt.n && !pt.positions) return set_err(ACVM_E_INVALID, "part " + std::to_string(q) + ": null positions");
+    }
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    const Plan &p = b->plan();
+    const uint32_t n_in = (uint32_t)p.initial_ids.size();
+    std::vector<int32_t> owner(n_in, -1);
+    for (uint32_t q = 0; q < n_parts; q++)
+        for (uint32_t k = 0; k < parts[q].n; k++) {
+            const uint32_t pos = parts[q].positions[k];
+            if (pos >= n_in) return set_err(ACVM_E_INVALID, "part " + std::to_string(q) + ": position " + std::to_string(pos) + " is not below n_initial " + std::to_string(n_in));
+            if (owner[pos] >= 0) return set_err(ACVM_E_INVALID, "position " + std::to_string(pos) + " is supplied twice (parts " + std::to_string(owner[pos]) + " and " + std::to_string(q) + ")");
+            owner[pos] = (int32_t)q;
+        }
+    for (uint32_t pos = 0; pos < n_in; pos++)
+        if (owner[pos] < 0) return set_err(ACVM_E_INVALID, "position " + std::to_string(pos) + " (initial witness " + std::to_string(p.initial_ids[pos]) + ") is supplied by no part");
+    // every part has passed: the lists, then the launches
+    const bool planes = p.n_byte_planes != 0;
+    std::vector<uint32_t> lists;
+    std::vector<size_t> at(n_parts);
+    for (uint32_t q = 0; q < n_parts; q++) {
+        at[q] = lists.size();
+        for (uint32_t k = 0; k < parts[q].n; k++) {
+            const uint32_t id = p.initial_ids[parts[q].positions[k]];
+            lists.push_back(b->reuse() ? p.slot_of[id] : id);
+        }
+        if (planes)
+            for (uint32_t k = 0; k < parts[q].n; k++) lists.push_back(p.byte_plane_of[p.initial_ids[parts[q].positions[k]]]);
+        lists.insert(lists.end(), specs[q].columns.begin(), specs[q].columns.end());
+    }
+    HIPCHK(hipSetDevice(b->device));
+    if (!lists.empty() && !(b->d_import_lists && b->import_lists == lists)) {
+        HIPCHK(hipStreamSynchronize(b->stream));  // (an import enqueued behind the last solve may still be reading the old lists)
+        b->import_lists.clear();
+        if (lists.size() > b->import_lists_cap) {
+            if (b->d_import_lists) { hipFree(b->d_import_lists); b->d_import_lists = nullptr; b->import_lists_cap = 0; }
+            HIPCHK(hipMalloc((void **)&b->d_import_lists, lists.size() * 4));
+            b->import_lists_cap = lists.size();
+        }
+        HIPCHK(hipMemcpy(b->d_import_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
+        b->import_lists = lists;
+        b->n_import_list_copies++;
+    }
+    b->next_imported = false;
+    b->next_inputs = nullptr;
+    bool reset_given = false;
+    for (uint32_t q = 0; q < n_parts; q++) {
+        const uint32_t n = parts[q].n;
+        if (!n) continue;
+        const ImportSpec &sp = specs[q];
+        const uint32_t *d_rows = b->d_import_lists + at[q], *d_planes = planes ? d_rows + n : nullptr, *d_cols = sp.has_columns ? d_rows + (planes ? 2 : 1) * (size_t)n : nullptr;
+        const ImportDevice x{sp.encoding, sp.layout, d_cols, sp.stride, parts[q].d_values};
+        uint32_t *reset = reset_given ? nullptr : b->d_event;
+        const bool typed = sp.elem_size != 32u || sp.layout == EXPORT_LAYOUT_BROADCAST;
+        const bool did = (typed ? launch_import_typed : launch_import_device)(b->stream, x, b->d_W, b->Bp, b->B, d_rows, n, nullptr, d_planes, b->d_byte_plane, reset);
+        reset_given = reset_given || did;
+    }
+    b->events_fresh = reset_given;
+    HIPCHK(hipGetLastError());
+    b->inputs_set = true;
+    b->solved = false;
+    b->stepping = false;
+    clear_fc_store(b);
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+} ABI_CATCH
+uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b) { return b ? b->n_import_list_copies : 0; }
 
 int acvm_batch_set_initial_witness(acvm_batch_t *b, const uint8_t *values_be32) try {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");

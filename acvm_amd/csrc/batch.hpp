@@ -64,15 +64,18 @@ std::shared_ptr<const Plan> plan_for(const acvm_circuit *c, const uint32_t *init
 // One import of initial witnesses from a device buffer, checked and normalised (batch.cpp import_spec_of): what acvm_batch_import_device and
 // acvm_batch_solve_then_import_ex describe by an acvm_import_desc_t, and -- `plain` -- the one shape of acvm_batch_set_initial_witness_device /
 // acvm_batch_solve_then_import: BE32, instance-major, dense, no column list (kernels.hip import_witness_kernel, any alignment). The handle keeps a
-// COPY of the one it enqueued behind a solve: the following import costs nothing only if pointer and spec are both the same.
+// COPY of the one it enqueued behind a solve: the following import costs nothing only if pointer and spec are both the same. The narrow
+// encodings (elem_size < 32) take the kernels of kernels_typed_io.hip; a part of acvm_batch_import_device_parts is checked into the same struct
+// (layout may then be EXPORT_LAYOUT_BROADCAST, `columns` has one entry per position of the part, `plain` is never set).
 struct ImportSpec {
     uint32_t encoding = 0, layout = 0;
+    uint32_t elem_size = 32;        // bytes per element: 32, or 1 .. 16 for the narrow encodings (export_encode.hpp export_element_size)
     bool has_columns = false, plain = true;
     std::vector<uint32_t> columns;  // (has_columns) one per initial witness
     uint32_t n_columns = 0;
     uint64_t stride = 0;            // as launched: never 0
     bool operator==(const ImportSpec &o) const {
-        return encoding == o.encoding && layout == o.layout && has_columns == o.has_columns && plain == o.plain && columns == o.columns && n_columns == o.n_columns &&
+        return encoding == o.encoding && layout == o.layout && elem_size == o.elem_size && has_columns == o.has_columns && plain == o.plain && columns == o.columns && n_columns == o.n_columns &&
                stride == o.stride;
     }
 };
@@ -174,6 +177,11 @@ struct acvm_batch {
     std::vector<uint32_t> import_cols;
     uint32_t *d_import_cols = nullptr;
     size_t import_cols_cap = 0;
+    // all lists of the last acvm_batch_import_device_parts -- per part its rows, planes and columns -- on the device: uploaded again only when they change
+    std::vector<uint32_t> import_lists;
+    uint32_t *d_import_lists = nullptr;
+    size_t import_lists_cap = 0;
+    uint64_t n_import_list_copies = 0;  // (acvm_debug_import_list_copies)
     hipEvent_t ev_counted = nullptr;  // behind the event count of a solve: what the host waits for instead of the whole stream
     bool holds_tables = false;  // a reference on the device's lookup-table set (grumpkin_host.hpp device_tables_retain)
     // caller-supplied BlackBoxFunctionSolver
@@ -248,6 +256,7 @@ struct acvm_batch {
         if (d_stage) hipFree(d_stage);
         if (d_fetch) hipFree(d_fetch);
         if (d_import_cols) hipFree(d_import_cols);
+        if (d_import_lists) hipFree(d_import_lists);
         if (stream_x) { hipStreamSynchronize(stream_x); hipStreamDestroy(stream_x); }
         if (ev_x_ready) hipEventDestroy(ev_x_ready);
         for (int k = 0; k < (int)N_CLS; k++)

@@ -739,10 +739,13 @@ static int ensure_mont256_table(acvm_batch *b) {
 
 int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
     if (!d) return set_err(ACVM_E_INVALID, "null argument");
-    if (d->encoding >= EXPORT_N_ENC) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
+    if (!export_enc_is_valid(d->encoding)) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
     if (d->layout >= EXPORT_N_LAYOUT) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(d->layout));
     if (!b || !d_values) return set_err(ACVM_E_INVALID, "null argument");
-    if ((uintptr_t)d_values & 15u) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
+    const bool narrow = export_enc_is_narrow(d->encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
+    if (!narrow && ((uintptr_t)d_values & 15u)) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
+    if (narrow && ((uintptr_t)d_values & (export_element_size(d->encoding) - 1u)))
+        return set_err(ACVM_E_INVALID, "d_values must be aligned to the element size, " + std::to_string(export_element_size(d->encoding)) + " bytes");
     if (b->pending)
         if (int rc = batch_finish_pending(b, &b->last_outcome)) return rc;
     if (!b->solved) return set_err(ACVM_E_STATE, "batch not solved");
@@ -778,11 +781,14 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
     if (n_lanes) HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
     const ExportDevice x{d->encoding, d->layout, first, n, d_sel, n_sel, nw, stride, d_values, d_assigned};
     // every lane as a generic instance (scaled columns, the planner's assigned set) ...
-    if (n_lanes < n)
-        launch_export_device(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, d->encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain);
+    if (n_lanes < n) {
+        if (narrow) launch_export_narrow(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale);
+        else launch_export_device(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, d->encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain);
+    }
     // ... then the exact lanes from where they live (their own columns of the level table, or the side table), scattered into their elements
     if (n_lanes)
-        launch_export_device_lanes(s, x, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), d_lanes, n_lanes, b->d_assigned, (uint32_t)b->slow_ids.size());
+        (narrow ? launch_export_narrow_lanes : launch_export_device_lanes)(s, x, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), d_lanes, n_lanes, b->d_assigned,
+                                                                           (uint32_t)b->slow_ids.size());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));  // (also what keeps `lanes` and the caller's list alive for their copies)
     return 0;

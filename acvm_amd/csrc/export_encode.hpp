@@ -61,6 +61,44 @@ FR_HD __forceinline__ uint64_t export_element_index(uint32_t layout, uint64_t st
 // the dense stride of a layout; a caller's stride must not be below it
 FR_HD __forceinline__ uint64_t export_dense_stride(uint32_t layout, uint32_t n, uint32_t n_sel) { return layout == EXPORT_WITNESS_MAJOR ? n : n_sel; }
 
+// ---- the narrow encodings (ACVM_ENC_U8 .. ACVM_ENC_U128): an element is an unsigned little-endian integer of 1, 2, 4, 8 or 16 bytes.
+// EXPORT_N_ENC keeps guarding the 32-byte range [0, 3); 3 .. 15 and 21 and up stay invalid.
+enum : uint32_t { EXPORT_ENC_U8 = 16, EXPORT_ENC_U16 = 17, EXPORT_ENC_U32 = 18, EXPORT_ENC_U64 = 19, EXPORT_ENC_U128 = 20 };
+enum : uint32_t { EXPORT_LAYOUT_BROADCAST = 16 };  // (ACVM_LAYOUT_BROADCAST: parts of acvm_batch_import_device_parts only)
+FR_HD __forceinline__ bool export_enc_is_narrow(uint32_t encoding) { return encoding >= EXPORT_ENC_U8 && encoding <= EXPORT_ENC_U128; }
+FR_HD __forceinline__ bool export_enc_is_valid(uint32_t encoding) { return encoding < EXPORT_N_ENC || export_enc_is_narrow(encoding); }
+// bytes per element: 32, or the width of the integer
+FR_HD __forceinline__ uint32_t export_element_size(uint32_t encoding) { return export_enc_is_narrow(encoding) ? 1u << (encoding - EXPORT_ENC_U8) : 32u; }
+// where element (i, k) lies, in BYTES from the buffer's start: the index rule above times the element's size; a broadcast column holds one
+// element for every instance
+FR_HD __forceinline__ uint64_t export_element_offset(uint32_t layout, uint64_t stride, uint64_t i, uint64_t k, uint32_t size) {
+    return (layout == EXPORT_LAYOUT_BROADCAST ? k : export_element_index(layout, stride, i, k)) * size;
+}
+// One narrow element: the low `size` bytes of the canonical value, little-endian, in the low bytes of `lo` (the rest zero) -- the truncation
+// of FieldElement::to_u128 -- and the mask byte: 0 unassigned (zero bytes), 1 the value fits, 2 the value is 2^(8 size) or more.
+struct ExportNarrow {
+    uint4 lo;
+    uint32_t mask;
+};
+FR_HD __forceinline__ ExportNarrow export_encode_narrow(const Fr &row, const Fr &factor, uint32_t size, bool assigned) {
+    ExportNarrow e;
+    e.lo = make_uint4(0u, 0u, 0u, 0u);
+    e.mask = 0u;
+    if (!assigned) return e;
+    const Fr x = fr_mul(row, factor);
+    uint32_t above = x.v[4] | x.v[5] | x.v[6] | x.v[7];
+    e.lo = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+    if (size < 16u) { above |= e.lo.z | e.lo.w; e.lo.z = 0u; e.lo.w = 0u; }
+    if (size < 8u) { above |= e.lo.y; e.lo.y = 0u; }
+    if (size < 4u) {
+        const uint32_t keep = size == 1u ? 0xffu : 0xffffu;
+        above |= e.lo.x & ~keep;
+        e.lo.x &= keep;
+    }
+    e.mask = above ? 2u : 1u;
+    return e;
+}
+
 // The tiled (instance-major) kernel: block (bx, by) owns instances [64 bx, 64 bx + 64) x list positions [T by, T by + T).
 // Phase 1: wave v of the block's four computes positions v, v + 4, ... of the tile, lane = instance (coalesced row loads).
 // Phase 2: the tile leaves as 64 runs of 2 T consecutive 16-byte units; in step s thread t moves unit g = 256 s + t of the tile, counted

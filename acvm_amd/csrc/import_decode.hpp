@@ -87,4 +87,32 @@ FR_HD __forceinline__ ImportDecoded import_decode(const uint4 &lo, const uint4 &
     return d;
 }
 
+// ---- the narrow encodings (export_encode.hpp EXPORT_ENC_U8 ..): the value IS the integer, below 2^128 < p, so nothing is reduced.
+// lo: the element's bytes, zero-extended to 16
+FR_HD __forceinline__ Fr import_narrow_limbs(const uint4 &lo) {
+    Fr x = fr_zero();
+    x.v[0] = lo.x; x.v[1] = lo.y; x.v[2] = lo.z; x.v[3] = lo.w;
+    return x;
+}
+// the element's `size` bytes at p (aligned to size), zero-extended: one load of the natural width
+FR_HD __forceinline__ uint4 import_narrow_read(const void *p, uint32_t size) {
+    uint4 lo = make_uint4(0u, 0u, 0u, 0u);
+    switch (size) {
+        case 1: lo.x = *(const uint8_t *)p; break;
+        case 2: lo.x = *(const uint16_t *)p; break;
+        case 4: lo.x = *(const uint32_t *)p; break;
+        case 8: { const uint2 v = *(const uint2 *)p; lo.x = v.x; lo.y = v.y; break; }
+        default: lo = *(const uint4 *)p; break;
+    }
+    return lo;
+}
+// One narrow element, everything (the kernels take a wave of bytes from fr_mont_of_byte instead of the product, and U8 always: the same row)
+FR_HD __forceinline__ ImportDecoded import_decode_narrow(const uint4 &lo) {
+    ImportDecoded d;
+    d.canonical = import_narrow_limbs(lo);
+    d.row = fr_mul(d.canonical, import_r522());
+    d.plane = import_plane_word(d.canonical);
+    return d;
+}
+
 }  // namespace acvm

@@ -88,7 +88,7 @@ struct ImportDevice {
     uint32_t encoding, layout;
     const uint32_t *columns;  // device array, one column per input; null: input k is column k
     uint64_t stride;          // in elements, >= the layout's dense stride
-    const void *in;           // 16-byte aligned
+    const void *in;           // 16-byte aligned (launch_import_typed: aligned to the element size)
 };
 bool launch_import_device(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
                           const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
@@ -110,6 +110,14 @@ void launch_export_device(hipStream_t s, const ExportDevice &x, const uint4 *W, 
 // ... then the instances of the exact path over their elements: lanes = n_lanes pairs (lane of the assigned bitmap, index in the range), values in
 // column `lane` of W (side) or in column first + index
 void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
+                                const uint32_t *assigned_bits, uint32_t n_slow);
+// ---- kernels_typed_io.hip: the narrow encodings (export_encode.hpp EXPORT_ENC_U8 .. U128: elements of 1 .. 16 bytes, `in` / `out` aligned to
+// the element size) and the broadcast layout of an import part (EXPORT_LAYOUT_BROADCAST, any encoding; 32-byte elements 16-byte aligned).
+// Arguments and return value as launch_import_device / launch_export_device(_lanes); the mask byte of a narrow element is 0 / 1 / 2.
+bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
+                         const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
+void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u);
+void launch_export_narrow_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow);
 void launch_gather_initial(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *W, uint64_t Bp, const uint32_t *init_ids, const uint32_t *init_rows, uint32_t n_init,
                            const uint32_t *slow_ids, uint32_t n_slow);

@@ -476,10 +476,14 @@ int acvm_batch_extract_witnesses(acvm_batch_t *b, const uint32_t *witnesses, uin
  * The witness map where it already is: ACVM::witness_map / finalize (acvm/src/pwg/mod.rs:161,176-181) written into DEVICE memory of the
  * caller, in the encoding and layout of the GPU program that consumes it (a prover's wire columns, a commitment kernel, the initial
  * witnesses of the next circuit of a pipeline). Every export above stages through host memory; this one moves no value over PCIe.
- *   - d_values / d_assigned are plain device pointers on the batch's device. d_values must be 16-byte aligned (else ACVM_E_INVALID) and hold
- *     32 bytes per element; d_assigned, which may be NULL, holds one byte (0 / 1) per element in the same layout and stride.
+ *   - d_values / d_assigned are plain device pointers on the batch's device. d_values holds one element per (instance, witness): 32 bytes, 16-byte
+ *     aligned, for the 32-byte encodings; the integer's 1, 2, 4, 8 or 16 bytes, aligned to that size, for the narrow ones (else ACVM_E_INVALID).
+ *     d_assigned, which may be NULL, holds one byte per element in the same layout and stride (in elements): 0 / 1 for the 32-byte encodings.
+ *   - A narrow element is the low `size` bytes of the canonical value, little-endian: the truncation of FieldElement::to_u128
+ *     (acir_field/src/generic_ark.rs:227-230). Its mask byte says whether that is the whole value: 0 = unassigned (zero bytes), 1 = assigned and
+ *     the value fits, 2 = assigned but the value is 2^(8 size) or more (the low bytes are written all the same).
  *   - witnesses: HOST array of n_witnesses indices, any order, repeats allowed; NULL = the whole map 0 .. acvm_circuit_num_witnesses - 1.
- *   - An unassigned element is 32 zero bytes and mask 0, in every encoding; a listed index beyond the circuit's witnesses is unassigned.
+ *   - An unassigned element is zero bytes (32, or the narrow element's size) and mask 0, in every encoding; a listed index beyond the circuit's witnesses is unassigned.
  *     Unlike acvm_batch_extract_witnesses an unassigned witness is not an error: the mask says it.
  *   - stride, in elements: see the layouts; 0 = dense. The bytes between rows are never written. A stride below the dense one is ACVM_E_INVALID.
  *   - The call enqueues on the batch's stream and returns after that stream is synchronised. No value is copied to the host and no host loop
@@ -492,9 +496,15 @@ int acvm_batch_extract_witnesses(acvm_batch_t *b, const uint32_t *witnesses, uin
  */
 enum { ACVM_ENC_BE32 = 0,          /* canonical, 32 bytes big-endian: byte for byte what acvm_batch_witness_map writes */
        ACVM_ENC_LE32 = 1,          /* canonical, 4 x u64 little-endian limbs (= 32 bytes little-endian) */
-       ACVM_ENC_MONT256_LE = 2 };  /* value * 2^256 mod p, 4 x u64 little-endian limbs (ark-ff BigInt<4> / barretenberg fr in memory) */
-enum { ACVM_LAYOUT_INSTANCE_MAJOR = 0,   /* element (i, k) at (i * stride + k) * 32, stride >= n_witnesses (0 = dense) */
-       ACVM_LAYOUT_WITNESS_MAJOR = 1 };  /* element (i, k) at (k * stride + i) * 32, stride >= n           (0 = dense) */
+       ACVM_ENC_MONT256_LE = 2,    /* value * 2^256 mod p, 4 x u64 little-endian limbs (ark-ff BigInt<4> / barretenberg fr in memory) */
+       /* The narrow encodings: an element is an unsigned little-endian integer of 1, 2, 4, 8 or 16 bytes -- message and digest bytes, flags,
+        * counters, 128-bit scalar limbs. Noir's signed types (i8 .. i64) are their two's-complement bit pattern at that width, bool is U8.
+        * 3 .. 15 and 21 and up are ACVM_E_INVALID. Not here: big-endian or sign-extending narrow types. */
+       ACVM_ENC_U8 = 16, ACVM_ENC_U16 = 17, ACVM_ENC_U32 = 18, ACVM_ENC_U64 = 19, ACVM_ENC_U128 = 20 };
+/* size = bytes per element: 32, or the integer's width for the narrow encodings; stride is in elements */
+enum { ACVM_LAYOUT_INSTANCE_MAJOR = 0,   /* element (i, k) at (i * stride + k) * size, stride >= n_witnesses (0 = dense) */
+       ACVM_LAYOUT_WITNESS_MAJOR = 1,    /* element (i, k) at (k * stride + i) * size, stride >= n           (0 = dense) */
+       ACVM_LAYOUT_BROADCAST = 16 };     /* parts of acvm_batch_import_device_parts only: element (i, c) at c * size -- one value for every instance */
 typedef struct {
     uint32_t encoding, layout;
     uint32_t first, n;         /* instances [first, first + n): i = instance - first */
@@ -507,15 +517,18 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
  * The way in as the mirror image of that way out: ACVM::new's initial WitnessMap (pwg/mod.rs:146-156) read from DEVICE memory of the caller in
  * the encoding and layout its producer writes -- a prover's wire columns (ACVM_ENC_MONT256_LE, ACVM_LAYOUT_WITNESS_MAJOR), or the buffer
  * acvm_batch_export_device of another batch filled, whole map and all: the column list picks the initial witnesses out of it.
- *   - Element (instance i, column c) lies at (i * stride + c) * 32 instance-major and at (c * stride + i) * 32 witness-major; i runs over the live
+ *   - Element (instance i, column c) lies at (i * stride + c) * size instance-major and at (c * stride + i) * size witness-major (size: 32, or
+ *     the width of a narrow encoding); i runs over the live
  *     instances [0, B) (acvm_batch_set_instances is honoured). stride in elements, 0 = dense: n_columns instance-major, the live B witness-major.
  *     The bytes between rows are never read.
  *   - columns: HOST array, one entry per initial witness in the order of initial_ids given to acvm_batch_new: columns[k] = the column of the
  *     buffer that holds it; repeats allowed. NULL: column k, and n_columns is taken as n_initial. The list is copied before the call returns.
  *   - Every 256-bit string is accepted, as by acvm_batch_set_initial_witness: BE32 is int(bytes, big) mod p, LE32 int(bytes, little) mod p,
  *     MONT256_LE m * 2^-256 mod p for m = int(bytes, little) -- any m < 2^256, m >= p is not an error. The inverse of what the export writes.
+ *     A narrow element (ACVM_ENC_U8 .. U128) is the integer itself: it is below p, nothing is reduced.
  *   - ACVM_E_INVALID: a stride below the dense one, columns[k] >= n_columns, an unknown encoding or layout, a null descriptor, null values with
- *     n_initial > 0, and a d_values that is not 16-byte aligned -- except for BE32, instance-major, columns == NULL, dense: that descriptor IS
+ *     n_initial > 0, and a d_values that is not aligned -- to 16 bytes for the 32-byte encodings, to the element's size for the narrow ones (U8
+ *     takes any pointer) -- except for BE32, instance-major, columns == NULL, dense: that descriptor IS
  *     acvm_batch_set_initial_witness_device, takes the same kernel and reads any pointer. A refused call leaves the handle as it was.
  *   - Leaves the handle in the state acvm_batch_set_initial_witness_device leaves it in and returns after the batch's stream is synchronised;
  *     at most one small host-to-device copy is made (the column list, when it differs from the last call's).
@@ -533,6 +546,29 @@ typedef struct {
 } acvm_import_desc_t;
 int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values);
 int acvm_batch_solve_then_import_ex(acvm_batch_t *b, const acvm_import_desc_t *d_next, const void *d_next_values);
+/*
+ * One import from several buffers: fn main(msg: [u8; 64], root: Field) takes its bytes from one producer and its root, the same for every
+ * instance, from another. Each part names the initial witnesses it supplies (positions in the initial_ids given to acvm_batch_new) and how
+ * its buffer is to be read, exactly as a descriptor does -- plus ACVM_LAYOUT_BROADCAST: one element per column, the value of every instance.
+ *   - Every initial witness must be supplied by exactly one part: a position that no part or more than one part supplies, or a position
+ *     >= n_initial, is ACVM_E_INVALID and the message names the position. Every part gets the checks of acvm_batch_import_device (no part is
+ *     exempt from the alignment rule). Nothing is enqueued before every part has passed: a refused call leaves the handle as it was.
+ *   - Leaves the handle exactly as acvm_batch_import_device leaves it -- rows, planes and event words are written once -- and returns after the
+ *     batch's stream is synchronised. At most one small host-to-device copy is made: all lists of the call in one buffer, which is reused while
+ *     they do not change (acvm_debug_import_list_copies counts the copies a handle has made).
+ *   - n_parts == 0 is valid only for a circuit without initial witnesses; a part with n == 0 supplies nothing.
+ * Not here: an acvm_batch_solve_then_import form for parts, an asynchronous variant, device I/O for acvm_node_solve.
+ */
+typedef struct {
+    const void *d_values;        /* device, aligned to the element size (16 bytes for the 32-byte encodings) */
+    uint32_t encoding, layout;   /* any ACVM_ENC_*; ACVM_LAYOUT_* or ACVM_LAYOUT_BROADCAST */
+    const uint32_t *positions;   /* HOST, n entries: which initial witnesses (positions in initial_ids) this part supplies */
+    const uint32_t *columns;     /* HOST, n entries or NULL (the k-th position reads column k; n_columns is then n) */
+    uint32_t n, n_columns;
+    uint64_t stride;             /* elements; 0 = dense; ignored for BROADCAST */
+} acvm_import_part_t;
+int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts);
+uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):
