@@ -834,7 +834,8 @@ class Batch:
         _check(lib().acvm_batch_import_device_parts(self._h, arr, len(parts)))
 
     def import_list_copies(self) -> int:
-        """host-to-device copies of import_device_parts' lists this handle has made (acvm_debug_import_list_copies)"""
+        """host-to-device copies of the imports' lists -- a descriptor's column list, the lists of import_device_parts -- this handle has made
+        (acvm_debug_import_list_copies)"""
         return lib().acvm_debug_import_list_copies(self._h)
 
     def reset(self):

@@ -1,8 +1,8 @@
-// batch.cpp -- the batch handle behind the C ABI (include/acvm_amd.h): creation (plan + device tables), the initial witness, the small entry
+// batch.cpp -- the batch handle behind the C ABI (include/acvm_amd.h): creation (plan + device tables), the small entry
 // points of devices / tuning / circuits, statistics. One handle = one circuit plan, one device-resident witness table W[slot][half][instance],
 // one stream set. Mirrors the call shape of acvm::pwg::ACVM (acvm/src/pwg/mod.rs:145-304) for B instances at once. The solve lives in
-// batch_schedule.cpp (level schedule) and batch_exact.cpp (exact in-order path, foreign calls, stepping), what leaves the device in
-// batch_export.cpp, the measurement probes in probes.cpp.
+// batch_schedule.cpp (level schedule) and batch_exact.cpp (exact in-order path, foreign calls, stepping), the initial witness in batch_import.cpp,
+// what leaves the device in batch_export.cpp, the measurement probes in probes.cpp.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -15,7 +15,6 @@
 #include <string>
 #include <vector>
 #include "batch_internal.hpp"
-#include "export_encode.hpp"
 
 static thread_local std::string g_last_error;
 int set_err(int code, const std::string &msg) {
@@ -342,10 +341,10 @@ static int batch_init(acvm_batch *b) {
     if (int rc = upload(&b->d_bytecode, p.bytecode)) return rc;
     if (int rc = upload(&b->d_init_ids, p.initial_ids)) return rc;
     if (p.n_byte_planes) {  // plan.hpp "Byte planes"
-        std::vector<uint32_t> of_input(p.initial_ids.size());
-        for (size_t i = 0; i < p.initial_ids.size(); i++) of_input[i] = p.byte_plane_of[p.initial_ids[i]];
+        b->plane_of_input.resize(p.initial_ids.size());
+        for (size_t i = 0; i < p.initial_ids.size(); i++) b->plane_of_input[i] = p.byte_plane_of[p.initial_ids[i]];
         if (int rc = upload(&b->d_byte_plane_of, p.byte_plane_of)) return rc;
-        if (int rc = upload(&b->d_byte_plane_of_input, of_input)) return rc;
+        if (int rc = upload(&b->d_byte_plane_of_input, b->plane_of_input)) return rc;
         HIPCHK(hipMalloc((void **)&b->d_byte_plane, (size_t)p.n_byte_planes * b->Bp * 4));
         HIPCHK(hipMemsetAsync(b->d_byte_plane, 0, (size_t)p.n_byte_planes * b->Bp * 4, b->stream));
     }
@@ -389,9 +388,9 @@ static int batch_init(acvm_batch *b) {
     if (!p.slot_of.empty()) {
         if (int rc = upload(&b->d_slot_of, p.slot_of)) return rc;
         b->dp.slot_of = b->d_slot_of;
-        std::vector<uint32_t> rows(p.initial_ids.size());
-        for (size_t i = 0; i < rows.size(); i++) rows[i] = p.slot_of[p.initial_ids[i]];
-        if (int rc = upload(&b->d_init_rows, rows)) return rc;
+        b->init_rows.resize(p.initial_ids.size());
+        for (size_t i = 0; i < b->init_rows.size(); i++) b->init_rows[i] = p.slot_of[p.initial_ids[i]];
+        if (int rc = upload(&b->d_init_rows, b->init_rows)) return rc;
     }
     if (!p.fc_slot_opcode.empty()) {
         b->fc_slots.resize(p.fc_slot_opcode.size());
@@ -496,208 +495,6 @@ acvm_batch_t *acvm_batch_new_ex(const acvm_circuit_t *c, const acvm_bb_solver_t 
     return b.release();
 } ABI_CATCH_PTR
 void acvm_batch_free(acvm_batch_t *b) { delete b; }
-
-ImportSpec import_spec_plain(const acvm_batch *b) {
-    ImportSpec sp;
-    sp.encoding = EXPORT_ENC_BE32;
-    sp.layout = EXPORT_INSTANCE_MAJOR;
-    sp.n_columns = (uint32_t)b->plan().initial_ids.size();
-    sp.stride = sp.n_columns;
-    return sp;
-}
-// The checks every described buffer gets, for the n inputs it supplies (all initial witnesses for a descriptor, a part's positions for a part).
-// part: the broadcast layout is allowed, and the plain shape's exemption from the alignment rule is not.
-static int import_spec_check(const acvm_batch *b, uint32_t encoding, uint32_t layout, const uint32_t *columns, uint32_t n, uint32_t n_columns, uint64_t stride,
-                             const void *d_values, bool part, ImportSpec *out) {
-    if (!export_enc_is_valid(encoding)) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(encoding));
-    if (layout >= EXPORT_N_LAYOUT && !(part && layout == EXPORT_LAYOUT_BROADCAST)) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(layout));
-    if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    if (n && !d_values) return set_err(ACVM_E_INVALID, "null values");
-    ImportSpec sp;
-    sp.encoding = encoding;
-    sp.layout = layout;
-    sp.elem_size = export_element_size(encoding);
-    sp.has_columns = columns != nullptr;
-    sp.n_columns = sp.has_columns ? n_columns : n;
-    if (sp.has_columns) {
-        sp.columns.assign(columns, columns + n);
-        for (uint32_t k = 0; k < n; k++)
-            if (sp.columns[k] >= sp.n_columns)
-                return set_err(ACVM_E_INVALID, "column " + std::to_string(sp.columns[k]) + " of initial witness " + std::to_string(k) + " is not below n_columns " + std::to_string(sp.n_columns));
-    }
-    if (layout == EXPORT_LAYOUT_BROADCAST) sp.stride = 1;  // (ignored: element c lies at c * size)
-    else {
-        const uint64_t dense = export_dense_stride(sp.layout, b->B, sp.n_columns);
-        sp.stride = stride ? stride : dense;
-        if (sp.stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
-        // (the byte offset of the last element fits 63 bits)
-        const unsigned __int128 rows = sp.layout == EXPORT_WITNESS_MAJOR ? sp.n_columns : b->B;
-        if (rows * sp.stride > ((unsigned __int128)1 << 57)) return set_err(ACVM_E_INVALID, "stride " + std::to_string(sp.stride) + " is beyond any device buffer");
-    }
-    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
-    sp.plain = !part && sp.encoding == EXPORT_ENC_BE32 && sp.layout == EXPORT_INSTANCE_MAJOR && !sp.has_columns && sp.stride == n_in;
-    // (the plain shape IS acvm_batch_set_initial_witness_device, which reads any pointer: import_witness_kernel<false>)
-    const uint32_t align = sp.elem_size < 16u ? sp.elem_size : 16u;
-    if (!sp.plain && ((uintptr_t)d_values & (align - 1u)))
-        return set_err(ACVM_E_INVALID, sp.elem_size == 32u ? std::string("d_values must be 16-byte aligned") : "d_values must be aligned to the element size, " + std::to_string(sp.elem_size) + " bytes");
-    *out = std::move(sp);
-    return 0;
-}
-int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out) {
-    if (!d) return set_err(ACVM_E_INVALID, "null argument");
-    // (encoding and layout are judged before the batch: import_spec_check)
-    return import_spec_check(b, d->encoding, d->layout, d->columns, b ? (uint32_t)b->plan().initial_ids.size() : 0u, d->n_columns, d->stride, d_values, false, out);
-}
-// One small host-to-device copy when the list differs from the last call's, none otherwise. The stream is waited for first: an import enqueued
-// behind the last solve may still be reading the old list.
-int import_columns_ready(acvm_batch *b, const ImportSpec &spec) {
-    if (!spec.has_columns || spec.columns.empty()) return 0;
-    if (b->d_import_cols && b->import_cols == spec.columns) return 0;
-    HIPCHK(hipSetDevice(b->device));
-    HIPCHK(hipStreamSynchronize(b->stream));
-    b->import_cols.clear();
-    if (spec.columns.size() > b->import_cols_cap) {
-        if (b->d_import_cols) { hipFree(b->d_import_cols); b->d_import_cols = nullptr; b->import_cols_cap = 0; }
-        HIPCHK(hipMalloc((void **)&b->d_import_cols, spec.columns.size() * 4));
-        b->import_cols_cap = spec.columns.size();
-    }
-    HIPCHK(hipMemcpy(b->d_import_cols, spec.columns.data(), spec.columns.size() * 4, hipMemcpyHostToDevice));
-    b->import_cols = spec.columns;
-    return 0;
-}
-bool batch_launch_import(acvm_batch *b, const ImportSpec &spec, const void *d_values, const uint32_t *gate) {
-    const uint32_t *rows = b->reuse() ? b->d_init_rows : b->d_init_ids;
-    const uint32_t n_in = (uint32_t)b->plan().initial_ids.size();
-    if (spec.plain) return launch_import(b->stream, b->d_W, b->Bp, b->B, (const uint8_t *)d_values, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
-    const ImportDevice x{spec.encoding, spec.layout, spec.has_columns ? b->d_import_cols : nullptr, spec.stride, d_values};
-    if (spec.elem_size != 32u) return launch_import_typed(b->stream, x, b->d_W, b->Bp, b->B, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
-    return launch_import_device(b->stream, x, b->d_W, b->Bp, b->B, rows, n_in, gate, b->d_byte_plane_of_input, b->d_byte_plane, b->d_event);
-}
-
-int batch_import_spec_async(acvm_batch *b, const ImportSpec &spec, const void *d_values, hipEvent_t imported) {
-    HIPCHK(hipSetDevice(b->device));
-    // (acvm_batch_solve_then_import(_ex) put exactly this import behind the previous solve, and it ran: the rows are there, in stream order)
-    const bool already = b->next_imported && b->next_inputs == d_values && b->next_spec == spec;
-    b->next_imported = false;
-    b->next_inputs = nullptr;
-    if (!already) b->events_fresh = batch_launch_import(b, spec, d_values, nullptr);
-    HIPCHK(hipGetLastError());
-    if (imported) HIPCHK(hipEventRecord(imported, b->stream));
-    b->inputs_set = true;
-    b->solved = false;
-    b->stepping = false;
-    clear_fc_store(b);
-    return 0;
-}
-int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported) { return batch_import_spec_async(b, import_spec_plain(b), d_values_be32, imported); }
-int acvm_batch_set_initial_witness_device(acvm_batch_t *b, const void *d_values_be32) try {
-    if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    const bool already = b->next_imported && b->next_inputs == d_values_be32 && b->next_spec == import_spec_plain(b);
-    if (int rc = batch_import_async(b, d_values_be32, nullptr)) return rc;
-    // the caller may reuse its buffer as soon as the call returns (an import that ran behind the previous solve left the buffer alone since)
-    if (!already) HIPCHK(hipStreamSynchronize(b->stream));
-    return 0;
-} ABI_CATCH
-// The import as the mirror image of acvm_batch_export_device: any encoding, layout, stride and column list (include/acvm_amd.h).
-int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values) try {
-    ImportSpec sp;
-    if (int rc = import_spec_of(b, d, d_values, &sp)) return rc;
-    const bool already = b->next_imported && b->next_inputs == d_values && b->next_spec == sp;
-    if (!already)
-        if (int rc = import_columns_ready(b, sp)) return rc;
-    if (int rc = batch_import_spec_async(b, sp, d_values, nullptr)) return rc;
-    if (!already) HIPCHK(hipStreamSynchronize(b->stream));
-    return 0;
-} ABI_CATCH
-
-// One import from several buffers (include/acvm_amd.h): every part is checked like a descriptor, then the parts are launched one after the
-// other through the launchers of batch_launch_import, each with the rows, planes and columns of ITS inputs. All lists of the call travel in one
-// buffer -- per part: rows, planes (circuits with byte planes), columns (parts with a list) -- which is copied only when it differs from the
-// last call's. The event reset is given to exactly one launch.
-int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts) try {
-    if (n_parts && !parts) return set_err(ACVM_E_INVALID, "null argument");
-    std::vector<ImportSpec> specs(n_parts);
-    for (uint32_t q = 0; q < n_parts; q++) {
-        const acvm_import_part_t &pt = parts[q];
-        if (int rc = import_spec_check(b, pt.encoding, pt.layout, pt.columns, pt.n, pt.n_columns, pt.stride, pt.d_values, true, &specs[q])) {
-            return set_err(rc, "part " + std::to_string(q) + ": " + acvm_last_error());
-        }
-        if (pt.n && !pt.positions) return set_err(ACVM_E_INVALID, "part " + std::to_string(q) + ": null positions");
-    }
-    if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    const Plan &p = b->plan();
-    const uint32_t n_in = (uint32_t)p.initial_ids.size();
-    std::vector<int32_t> owner(n_in, -1);
-    for (uint32_t q = 0; q < n_parts; q++)
-        for (uint32_t k = 0; k < parts[q].n; k++) {
-            const uint32_t pos = parts[q].positions[k];
-            if (pos >= n_in) return set_err(ACVM_E_INVALID, "part " + std::to_string(q) + ": position " + std::to_string(pos) + " is not below n_initial " + std::to_string(n_in));
-            if (owner[pos] >= 0) return set_err(ACVM_E_INVALID, "position " + std::to_string(pos) + " is supplied twice (parts " + std::to_string(owner[pos]) + " and " + std::to_string(q) + ")");
-            owner[pos] = (int32_t)q;
-        }
-    for (uint32_t pos = 0; pos < n_in; pos++)
-        if (owner[pos] < 0) return set_err(ACVM_E_INVALID, "position " + std::to_string(pos) + " (initial witness " + std::to_string(p.initial_ids[pos]) + ") is supplied by no part");
-    // every part has passed: the lists, then the launches
-    const bool planes = p.n_byte_planes != 0;
-    std::vector<uint32_t> lists;
-    std::vector<size_t> at(n_parts);
-    for (uint32_t q = 0; q < n_parts; q++) {
-        at[q] = lists.size();
-        for (uint32_t k = 0; k < parts[q].n; k++) {
-            const uint32_t id = p.initial_ids[parts[q].positions[k]];
-            lists.push_back(b->reuse() ? p.slot_of[id] : id);
-        }
-        if (planes)
-            for (uint32_t k = 0; k < parts[q].n; k++) lists.push_back(p.byte_plane_of[p.initial_ids[parts[q].positions[k]]]);
-        lists.insert(lists.end(), specs[q].columns.begin(), specs[q].columns.end());
-    }
-    HIPCHK(hipSetDevice(b->device));
-    if (!lists.empty() && !(b->d_import_lists && b->import_lists == lists)) {
-        HIPCHK(hipStreamSynchronize(b->stream));  // (an import enqueued behind the last solve may still be reading the old lists)
-        b->import_lists.clear();
-        if (lists.size() > b->import_lists_cap) {
-            if (b->d_import_lists) { hipFree(b->d_import_lists); b->d_import_lists = nullptr; b->import_lists_cap = 0; }
-            HIPCHK(hipMalloc((void **)&b->d_import_lists, lists.size() * 4));
-            b->import_lists_cap = lists.size();
-        }
-        HIPCHK(hipMemcpy(b->d_import_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
-        b->import_lists = lists;
-        b->n_import_list_copies++;
-    }
-    b->next_imported = false;
-    b->next_inputs = nullptr;
-    bool reset_given = false;
-    for (uint32_t q = 0; q < n_parts; q++) {
-        const uint32_t n = parts[q].n;
-        if (!n) continue;
-        const ImportSpec &sp = specs[q];
-        const uint32_t *d_rows = b->d_import_lists + at[q], *d_planes = planes ? d_rows + n : nullptr, *d_cols = sp.has_columns ? d_rows + (planes ? 2 : 1) * (size_t)n : nullptr;
-        const ImportDevice x{sp.encoding, sp.layout, d_cols, sp.stride, parts[q].d_values};
-        uint32_t *reset = reset_given ? nullptr : b->d_event;
-        const bool typed = sp.elem_size != 32u || sp.layout == EXPORT_LAYOUT_BROADCAST;
-        const bool did = (typed ? launch_import_typed : launch_import_device)(b->stream, x, b->d_W, b->Bp, b->B, d_rows, n, nullptr, d_planes, b->d_byte_plane, reset);
-        reset_given = reset_given || did;
-    }
-    b->events_fresh = reset_given;
-    HIPCHK(hipGetLastError());
-    b->inputs_set = true;
-    b->solved = false;
-    b->stepping = false;
-    clear_fc_store(b);
-    HIPCHK(hipStreamSynchronize(b->stream));
-    return 0;
-} ABI_CATCH
-uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b) { return b ? b->n_import_list_copies : 0; }
-
-int acvm_batch_set_initial_witness(acvm_batch_t *b, const uint8_t *values_be32) try {
-    if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    size_t bytes = (size_t)b->B * b->plan().initial_ids.size() * 32;
-    if (bytes && !values_be32) return set_err(ACVM_E_INVALID, "null values");
-    HIPCHK(hipSetDevice(b->device));
-    if (int rc = stage_reserve(b, bytes)) return rc;
-    if (bytes) HIPCHK(hipMemcpyAsync(b->d_stage, values_be32, bytes, hipMemcpyHostToDevice, b->stream));
-    return acvm_batch_set_initial_witness_device(b, b->d_stage);
-} ABI_CATCH
 
 int acvm_batch_set_force_slow_path(acvm_batch_t *b, int on) {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");

@@ -2,6 +2,7 @@
 // node-level driver: one handle per device). Internal to the library.
 #pragma once
 #include "../../include/acvm_amd.h"
+#include "import_plan.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "schedule.hpp"
@@ -61,25 +62,6 @@ struct acvm_circuit {
 // the plan of `c` for these options: from the circuit's cache, or built (and cached) now. Never null; a refused circuit's plan has `unsupported` set.
 std::shared_ptr<const Plan> plan_for(const acvm_circuit *c, const uint32_t *initial_ids, uint32_t n_initial, const acvm::PlanOpts &opts);
 
-// One import of initial witnesses from a device buffer, checked and normalised (batch.cpp import_spec_of): what acvm_batch_import_device and
-// acvm_batch_solve_then_import_ex describe by an acvm_import_desc_t, and -- `plain` -- the one shape of acvm_batch_set_initial_witness_device /
-// acvm_batch_solve_then_import: BE32, instance-major, dense, no column list (kernels.hip import_witness_kernel, any alignment). The handle keeps a
-// COPY of the one it enqueued behind a solve: the following import costs nothing only if pointer and spec are both the same. The narrow
-// encodings (elem_size < 32) take the kernels of kernels_typed_io.hip; a part of acvm_batch_import_device_parts is checked into the same struct
-// (layout may then be EXPORT_LAYOUT_BROADCAST, `columns` has one entry per position of the part, `plain` is never set).
-struct ImportSpec {
-    uint32_t encoding = 0, layout = 0;
-    uint32_t elem_size = 32;        // bytes per element: 32, or 1 .. 16 for the narrow encodings (export_encode.hpp export_element_size)
-    bool has_columns = false, plain = true;
-    std::vector<uint32_t> columns;  // (has_columns) one per initial witness
-    uint32_t n_columns = 0;
-    uint64_t stride = 0;            // as launched: never 0
-    bool operator==(const ImportSpec &o) const {
-        return encoding == o.encoding && layout == o.layout && elem_size == o.elem_size && has_columns == o.has_columns && plain == o.plain && columns == o.columns && n_columns == o.n_columns &&
-               stride == o.stride;
-    }
-};
-
 struct acvm_batch {
     // The static plan: immutable once built and shared -- by the handles of a node (node.cpp: one plan per circuit, not one per device) and
     // by every handle created for the same (circuit, initial ids, options, tuning) through the circuit's plan cache (batch.cpp plan_for).
@@ -106,7 +88,7 @@ struct acvm_batch {
     uint32_t *h_flag_count = nullptr;  // pinned, device-mapped: the same count where the host reads it after a synchronisation
     // The one rule of events_fresh: true only between an import that wrote the event words ("nobody flagged": kernels.hip import_witness_kernel, kernels_import.hip)
     // and the first thing enqueued behind it; the level solve that finds it set skips its reset launch. Set where launch_import says it launched
-    // (not for a circuit without initial witnesses); cleared by everything else that writes d_event or changes what it covers: the level
+    // (not for a circuit without initial witnesses; batch_import.cpp import_epilogue is the one writer on the import side); cleared by everything else that writes d_event or changes what it covers: the level
     // schedule's reset step, the fill of the exact-only solve and of solve_stepping, acvm_batch_reset, batch_set_live_count.
     bool events_fresh = false;
     std::vector<uint32_t> h_event;
@@ -172,16 +154,14 @@ struct acvm_batch {
     // the next tile's import behind this solve (acvm_batch_solve_then_import): the caller's device buffer, and whether the import ran
     const void *next_inputs = nullptr;
     bool next_imported = false;
-    ImportSpec next_spec;  // how next_inputs was read (acvm_batch_solve_then_import_ex; plain for acvm_batch_solve_then_import)
-    // the column list of the last import that had one, on the device: uploaded again only when it changes (batch.cpp import_columns_ready)
-    std::vector<uint32_t> import_cols;
-    uint32_t *d_import_cols = nullptr;
-    size_t import_cols_cap = 0;
-    // all lists of the last acvm_batch_import_device_parts -- per part its rows, planes and columns -- on the device: uploaded again only when they change
+    ImportPlan next_plan;  // how next_inputs was read (import_plan.hpp: a descriptor's plan, or the plain one)
+    // The one list buffer of the imports (batch_import.cpp import_lists_ready): all lists of the last plan that had any -- a descriptor's column
+    // list; per part of acvm_batch_import_device_parts its rows, planes and columns -- on the device, uploaded again only when they change
     std::vector<uint32_t> import_lists;
     uint32_t *d_import_lists = nullptr;
     size_t import_lists_cap = 0;
     uint64_t n_import_list_copies = 0;  // (acvm_debug_import_list_copies)
+    std::vector<uint32_t> init_rows, plane_of_input;  // host copies of d_init_rows (slot reuse) and d_byte_plane_of_input (byte planes): what a plan of parts picks from
     hipEvent_t ev_counted = nullptr;  // behind the event count of a solve: what the host waits for instead of the whole stream
     bool holds_tables = false;  // a reference on the device's lookup-table set (grumpkin_host.hpp device_tables_retain)
     // caller-supplied BlackBoxFunctionSolver
@@ -255,7 +235,6 @@ struct acvm_batch {
         if (d_ped_seed) hipFree(d_ped_seed);
         if (d_stage) hipFree(d_stage);
         if (d_fetch) hipFree(d_fetch);
-        if (d_import_cols) hipFree(d_import_cols);
         if (d_import_lists) hipFree(d_import_lists);
         if (stream_x) { hipStreamSynchronize(stream_x); hipStreamDestroy(stream_x); }
         if (ev_x_ready) hipEventDestroy(ev_x_ready);
@@ -291,8 +270,6 @@ int batch_set_live_count(acvm_batch *b, uint32_t n);
 // acvm_batch_set_initial_witness_device without the wait: the import is enqueued on the handle's stream and `imported` recorded behind it;
 // the caller keeps d_values_be32 untouched until that event has fired.
 int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported);
-// the same for any checked import (batch_import_async is this with the plain spec); a spec with a column list needs import_columns_ready first
-int batch_import_spec_async(acvm_batch *b, const ImportSpec &spec, const void *d_values, hipEvent_t imported);
 // waits for the exact job in flight (if any) and moves its outcome into *out (cleared first)
 int batch_finish_pending(acvm_batch *b, ExactOutcome *out);
 // the outcome of the previous solve's exact job, which the last acvm_batch_solve collected on its way (moved into *out; empty if none)

@@ -739,13 +739,13 @@ static int ensure_mont256_table(acvm_batch *b) {
 
 int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
     if (!d) return set_err(ACVM_E_INVALID, "null argument");
-    if (!export_enc_is_valid(d->encoding)) return set_err(ACVM_E_INVALID, "unknown encoding " + std::to_string(d->encoding));
-    if (d->layout >= EXPORT_N_LAYOUT) return set_err(ACVM_E_INVALID, "unknown layout " + std::to_string(d->layout));
+    // (the buffer checks of import_plan.hpp, shared with the imports)
+    std::string refusal = buffer_check_shape(d->encoding, d->layout, false);
+    if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
     if (!b || !d_values) return set_err(ACVM_E_INVALID, "null argument");
     const bool narrow = export_enc_is_narrow(d->encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
-    if (!narrow && ((uintptr_t)d_values & 15u)) return set_err(ACVM_E_INVALID, "d_values must be 16-byte aligned");
-    if (narrow && ((uintptr_t)d_values & (export_element_size(d->encoding) - 1u)))
-        return set_err(ACVM_E_INVALID, "d_values must be aligned to the element size, " + std::to_string(export_element_size(d->encoding)) + " bytes");
+    refusal = buffer_check_pointer(d->encoding, d_values);
+    if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
     if (b->pending)
         if (int rc = batch_finish_pending(b, &b->last_outcome)) return rc;
     if (!b->solved) return set_err(ACVM_E_STATE, "batch not solved");
@@ -754,8 +754,9 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
     const uint32_t nw = b->plan().n_witnesses;
     const bool whole = d->witnesses == nullptr;
     const uint32_t n_sel = whole ? nw : d->n_witnesses;
-    const uint64_t dense = export_dense_stride(d->layout, n, n_sel), stride = d->stride ? d->stride : dense;
-    if (stride < dense) return set_err(ACVM_E_INVALID, "stride " + std::to_string(stride) + " is below the dense stride " + std::to_string(dense) + " of the layout");
+    uint64_t stride = d->stride;
+    refusal = buffer_check_stride(d->layout, n, n_sel, &stride);
+    if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
     if (whole) {
         if (b->side()) return set_err(ACVM_E_STATE, "the batch recycles witness rows (ACVM_BATCH_REUSE_SLOTS) or solved its exact lanes in the side table: full maps are not kept; read the kept witnesses and the digest");
         if (int rc = refuse_if_next_imported(b, nullptr, 0, true)) return rc;

@@ -1,0 +1,135 @@
+// batch_import.cpp -- ACVM::new's initial WitnessMap (pwg/mod.rs:146-156) for the batch: every entry point that imports initial witnesses. Each
+// of them has its arguments checked into an ImportPlan (import_plan.cpp: pure host code) and hands the plan to batch_import_plan_async, which
+// sits on four helpers with one definition each: the list buffer (import_lists_ready), the launch (batch_launch_import), the question whether
+// the import already ran behind the last solve (import_is_behind_solve) and the handle's state afterwards (import_epilogue).
+#include "batch_internal.hpp"
+#include "export_encode.hpp"
+
+static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
+                  EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
+              "the kernels (export_encode.hpp) and the checks (import_plan.cpp: include/acvm_amd.h) number encodings and layouts alike");
+
+static ImportView import_view(const acvm_batch *b) {
+    const Plan &p = b->plan();
+    return ImportView{b->B, (uint32_t)p.initial_ids.size(), p.initial_ids.data(), b->reuse() ? b->init_rows.data() : p.initial_ids.data(),
+                      p.n_byte_planes ? b->plane_of_input.data() : nullptr};
+}
+int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out) {
+    const ImportView view = b ? import_view(b) : ImportView{};
+    std::string err;
+    const int rc = import_plan_desc(b ? &view : nullptr, d, d_values, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+
+// One small host-to-device copy when the plan's lists differ from the last upload's, none otherwise (or for a plan without lists). The stream is
+// waited for first: an import enqueued behind the last solve may still be reading the old lists.
+int import_lists_ready(acvm_batch *b, const ImportPlan &plan) {
+    const std::vector<uint32_t> &lists = plan.lists;
+    if (lists.empty() || (b->d_import_lists && b->import_lists == lists)) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    b->import_lists.clear();
+    if (lists.size() > b->import_lists_cap) {
+        if (b->d_import_lists) { hipFree(b->d_import_lists); b->d_import_lists = nullptr; b->import_lists_cap = 0; }
+        HIPCHK(hipMalloc((void **)&b->d_import_lists, lists.size() * 4));
+        b->import_lists_cap = lists.size();
+    }
+    HIPCHK(hipMemcpy(b->d_import_lists, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
+    b->import_lists = lists;
+    b->n_import_list_copies++;
+    return 0;
+}
+uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b) { return b ? b->n_import_list_copies : 0; }
+
+// The parts one after the other, each with the rows, planes and columns of ITS inputs: from the list buffer, or -- a descriptor -- the handle's
+// resident tables.
+bool batch_launch_import(acvm_batch *b, const ImportPlan &plan, const uint32_t *gate) {
+    bool reset_written = false;
+    for (const ImportPlanPart &pt : plan.parts) {
+        if (!pt.n) continue;
+        const uint32_t *lists = b->d_import_lists;
+        const uint32_t *rows = pt.resident ? (b->reuse() ? b->d_init_rows : b->d_init_ids) : lists + pt.rows_at;
+        const uint32_t *planes = pt.resident ? b->d_byte_plane_of_input : pt.planes_at != IMPORT_NO_LIST ? lists + pt.planes_at : nullptr;
+        const uint32_t *columns = pt.columns_at != IMPORT_NO_LIST ? lists + pt.columns_at : nullptr;
+        uint32_t *reset = reset_written ? nullptr : b->d_event;
+        bool did;
+        if (plan.plain) did = launch_import(b->stream, b->d_W, b->Bp, b->B, (const uint8_t *)pt.d_values, rows, pt.n, gate, planes, b->d_byte_plane, reset);
+        else {
+            const ImportDevice x{pt.encoding, pt.layout, columns, pt.stride, pt.d_values};
+            const bool typed = pt.elem_size != 32u || pt.layout == EXPORT_LAYOUT_BROADCAST;
+            did = (typed ? launch_import_typed : launch_import_device)(b->stream, x, b->d_W, b->Bp, b->B, rows, pt.n, gate, planes, b->d_byte_plane, reset);
+        }
+        reset_written = reset_written || did;
+    }
+    return reset_written;
+}
+
+// acvm_batch_solve_then_import(_ex) put exactly this import behind the previous solve, and it ran: the rows are there, in stream order. (Only a
+// plan of one resident part rides behind a solve: the plan of parts never compares equal to it.)
+static bool import_is_behind_solve(const acvm_batch *b, const ImportPlan &plan) {
+    return b->next_imported && plan.parts.size() == 1 && b->next_inputs == plan.parts[0].d_values && b->next_plan == plan;
+}
+// The handle's state after an import. enqueued: by this call, and reset_written is batch_launch_import's answer (events_fresh's rule: batch.hpp);
+// otherwise the import is the one behind the last solve, which set events_fresh itself.
+static void import_epilogue(acvm_batch *b, bool enqueued, bool reset_written) {
+    b->next_imported = false;
+    b->next_inputs = nullptr;
+    if (enqueued) b->events_fresh = reset_written;
+    b->inputs_set = true;
+    b->solved = false;
+    b->stepping = false;
+    clear_fc_store(b);
+}
+
+int batch_import_plan_async(acvm_batch *b, const ImportPlan &plan, hipEvent_t imported, bool *already) {
+    HIPCHK(hipSetDevice(b->device));
+    const bool behind = import_is_behind_solve(b, plan);
+    if (already) *already = behind;
+    if (!behind)
+        if (int rc = import_lists_ready(b, plan)) return rc;
+    const bool reset_written = !behind && batch_launch_import(b, plan, nullptr);
+    import_epilogue(b, !behind, reset_written);
+    HIPCHK(hipGetLastError());
+    if (imported) HIPCHK(hipEventRecord(imported, b->stream));
+    return 0;
+}
+int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported) {
+    return batch_import_plan_async(b, import_plan_plain((uint32_t)b->plan().initial_ids.size(), d_values_be32), imported, nullptr);
+}
+// the import and the wait of the public entry points: the caller may reuse its buffers as soon as the call returns (an import that ran behind
+// the previous solve left the buffer alone since: nothing to wait for)
+static int import_and_wait(acvm_batch *b, const ImportPlan &plan) {
+    bool already = false;
+    if (int rc = batch_import_plan_async(b, plan, nullptr, &already)) return rc;
+    if (!already) HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int acvm_batch_set_initial_witness_device(acvm_batch_t *b, const void *d_values_be32) try {
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    return import_and_wait(b, import_plan_plain((uint32_t)b->plan().initial_ids.size(), d_values_be32));
+} ABI_CATCH
+int acvm_batch_set_initial_witness(acvm_batch_t *b, const uint8_t *values_be32) try {
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    size_t bytes = (size_t)b->B * b->plan().initial_ids.size() * 32;
+    if (bytes && !values_be32) return set_err(ACVM_E_INVALID, "null values");
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = stage_reserve(b, bytes)) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(b->d_stage, values_be32, bytes, hipMemcpyHostToDevice, b->stream));
+    return acvm_batch_set_initial_witness_device(b, b->d_stage);
+} ABI_CATCH
+// The import as the mirror image of acvm_batch_export_device: any encoding, layout, stride and column list (include/acvm_amd.h).
+int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values) try {
+    ImportPlan plan;
+    if (int rc = import_plan_of(b, d, d_values, &plan)) return rc;
+    return import_and_wait(b, plan);
+} ABI_CATCH
+// One import from several buffers (include/acvm_amd.h): every part is checked like a descriptor, nothing is enqueued before all have passed. The
+// event reset is given to exactly one launch. A plan of parts never rides behind a solve, so this call always waits.
+int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts) try {
+    const ImportView view = b ? import_view(b) : ImportView{};
+    ImportPlan plan;
+    std::string err;
+    if (int rc = import_plan_parts(b ? &view : nullptr, parts, n_parts, &plan, &err)) return set_err(rc, err);
+    return import_and_wait(b, plan);
+} ABI_CATCH

@@ -1,4 +1,4 @@
-// batch_internal.hpp -- what the translation units of the batch handle share (batch.cpp, batch_schedule.cpp, batch_exact.cpp, batch_export.cpp,
+// batch_internal.hpp -- what the translation units of the batch handle share (batch.cpp, batch_import.cpp, batch_schedule.cpp, batch_exact.cpp, batch_export.cpp,
 // probes.cpp): staging, the exact path's building blocks, result formatting. Internal to the library; the node driver sees batch.hpp only.
 #pragma once
 #include "batch.hpp"
@@ -22,19 +22,24 @@ void plan_stats(const Plan &p, acvm_stats_t *out);
 // address of *h_flag_count, pinned and device-mapped, at event[-2..-1]); the words themselves are left for launch_event_reset
 int event_words_new(uint32_t B, uint32_t **base, uint32_t **event, uint32_t **h_flag_count);
 
-// the plain spec of this handle (what acvm_batch_set_initial_witness_device reads)
-ImportSpec import_spec_plain(const acvm_batch *b);
-// an acvm_import_desc_t checked against the handle and the pointer: 0 and *out, or ACVM_E_INVALID
-int import_spec_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportSpec *out);
-// the spec's column list is on the device (nothing to do for a spec without one, or for the list of the last call)
-int import_columns_ready(acvm_batch *b, const ImportSpec &spec);
-// THE launch of an import on the handle's stream, whatever the entry point: the old kernel for the plain spec, the import_device kernels otherwise.
-// gate: null, or the device word that must be zero for the import to happen. Returns whether the launch wrote the event words (events_fresh's rule).
-bool batch_launch_import(acvm_batch *b, const ImportSpec &spec, const void *d_values, const uint32_t *gate);
+// ---- batch_import.cpp
+// an acvm_import_desc_t checked against the handle and the pointer (import_plan.cpp import_plan_desc): 0 and *out, or ACVM_E_INVALID and the error text
+int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out);
+// the plan's lists are on the device, in the handle's one list buffer (nothing to do for a plan without lists, or for the lists of the last upload)
+int import_lists_ready(acvm_batch *b, const ImportPlan &plan);
+// THE launch of an import on the handle's stream, whatever the entry point, and the only place that chooses among launch_import (the plain plan),
+// launch_import_device and launch_import_typed and that hands out the event reset: exactly one launch of the call gets it. A plan with lists
+// needs import_lists_ready first. gate: null, or the device word that must be zero for the import to happen. Returns whether a launch wrote the
+// event words (events_fresh's rule).
+bool batch_launch_import(acvm_batch *b, const ImportPlan &plan, const uint32_t *gate);
+// any checked import without the wait (batch.hpp batch_import_async is this with the plain plan): lists, launches, the handle's state.
+// *already (may be null): the import had run behind the last solve and nothing was enqueued.
+int batch_import_plan_async(acvm_batch *b, const ImportPlan &plan, hipEvent_t imported, bool *already);
 
 // ---- batch_schedule.cpp
-// ACVM::solve for the batch; next_inputs: acvm_batch_solve_then_import(_ex), read as next_spec says (null: nothing is imported behind the solve)
-int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *next_spec);
+// ACVM::solve for the batch; next: the plan of acvm_batch_solve_then_import(_ex) -- one resident part, whose d_values is the next tile's buffer --
+// or null: nothing is imported behind the solve
+int batch_solve_impl(acvm_batch *b, const ImportPlan *next);
 
 // ---- batch_exact.cpp
 int ensure_slow_capacity(acvm_batch *b, uint32_t n);

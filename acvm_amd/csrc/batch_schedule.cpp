@@ -100,7 +100,8 @@ static int ensure_level_events(acvm_batch *b) {
 // padded to 64 lanes, the memory blocks beside it and -- for a job that runs beside the next tile's level kernels, which use the class
 // buffers meanwhile -- per-class scratch of its own. Grow-only. 0 = ready, negative = an error (ACVM_E_DEVICE: no room).
 
-int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *next_spec) {
+int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
+    const void *next_inputs = next ? next->parts[0].d_values : nullptr;
     if (!b->inputs_set && !b->plan().initial_ids.empty()) return set_err(ACVM_E_STATE, "initial witness not set");
     HIPCHK(hipSetDevice(b->device));
     const Plan &p = b->plan();
@@ -162,7 +163,7 @@ int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *n
             if (!b->ev_counted) HIPCHK(hipEventCreate(&b->ev_counted));
             HIPCHK(hipEventRecord(b->ev_counted, s));
             // gate: the device's count of flagged instances, in front of the event words; the import leaves the event words ready for the next solve
-            import_launched = batch_launch_import(b, *next_spec, next_inputs, b->d_event - 4);
+            import_launched = batch_launch_import(b, *next, b->d_event - 4);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventSynchronize(b->ev_counted));
         } else HIPCHK(hipStreamSynchronize(s));
@@ -245,7 +246,7 @@ int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *n
         HIPCHK(hipEventElapsedTime(&ms, b->ev_start, b->ev_counted));
         b->next_imported = true;
         b->next_inputs = next_inputs;
-        b->next_spec = *next_spec;
+        b->next_plan = *next;
         b->events_fresh = import_launched;  // (the gated import ran: it left the event words ready -- unless there is no initial witness to import)
     } else {
         HIPCHK(hipEventRecord(b->ev_end, s));
@@ -278,36 +279,33 @@ int batch_solve_impl(acvm_batch *b, const void *next_inputs, const ImportSpec *n
 // the solve, and -- under a caller-supplied BlackBoxFunctionSolver -- the rounds that answer the Brillig programs' internal black-box calls
 // (batch_exact.cpp resolve_internal_calls): every round answers all instances waiting at such a call and re-solves (a few lanes on the exact
 // kernels, a sizeable part of the batch through the level schedule again: batch_solve_impl's choice for resolved foreign calls)
-static int solve_with_internal_calls(acvm_batch *b, const void *next_inputs, const ImportSpec *next_spec) {
-    int rc = batch_solve_impl(b, next_inputs, next_spec);
+static int solve_with_internal_calls(acvm_batch *b, const ImportPlan *next) {
+    // (resumed foreign calls, stepping and a caller-supplied solver keep the plain solve: nothing is imported behind them)
+    if (next && (!next->parts[0].d_values || b->solved || b->stepping || b->has_solver || b->force_slow)) next = nullptr;
+    if (next)  // (before anything is enqueued: lists that differ from the last upload's wait for the stream)
+        if (int rc = import_lists_ready(b, *next)) return rc;
+    int rc = batch_solve_impl(b, next);
     while (rc >= 0) {
         const int answered = resolve_internal_calls(b);
         if (answered < 0) return answered;
         if (!answered) break;
-        rc = batch_solve_impl(b, nullptr, nullptr);
+        rc = batch_solve_impl(b, nullptr);
     }
     return rc;
 }
 int acvm_batch_solve(acvm_batch_t *b) try {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    return solve_with_internal_calls(b, nullptr, nullptr);
+    return solve_with_internal_calls(b, nullptr);
 } ABI_CATCH
 int acvm_batch_solve_then_import(acvm_batch_t *b, const void *d_next_values_be32) try {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    // (resumed foreign calls, stepping and a caller-supplied solver keep the plain solve: nothing is imported behind them)
-    const bool plain = !d_next_values_be32 || b->solved || b->stepping || b->has_solver || b->force_slow;
-    const ImportSpec sp = import_spec_plain(b);
-    return solve_with_internal_calls(b, plain ? nullptr : d_next_values_be32, plain ? nullptr : &sp);
+    const ImportPlan plan = import_plan_plain((uint32_t)b->plan().initial_ids.size(), d_next_values_be32);
+    return solve_with_internal_calls(b, &plan);
 } ABI_CATCH
 // the same with the next tile's buffer in any shape acvm_batch_import_device reads: the gated enqueue of its kernels behind the solve
 int acvm_batch_solve_then_import_ex(acvm_batch_t *b, const acvm_import_desc_t *d_next, const void *d_next_values) try {
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    ImportSpec sp;
-    if (int rc = import_spec_of(b, d_next, d_next_values, &sp)) return rc;
-    const bool plain = !d_next_values || b->solved || b->stepping || b->has_solver || b->force_slow;
-    if (!plain)  // (before anything is enqueued: a list that differs from the last call's waits for the stream)
-        if (int rc = import_columns_ready(b, sp)) return rc;
-    return solve_with_internal_calls(b, plain ? nullptr : d_next_values, plain ? nullptr : &sp);
+    ImportPlan plan;
+    if (int rc = import_plan_of(b, d_next, d_next_values, &plan)) return rc;
+    return solve_with_internal_calls(b, &plan);
 } ABI_CATCH
-
-

@@ -78,6 +78,12 @@ struct Unscale {
     const uint32_t *event;       // per instance: 0xFFFFFFFF = solved by the level kernels (its column is still scaled)
 };
 
+// gridDim.y is limited to 65535: launch(first, count) over [0, n) in chunks of at most that many
+template <class Launch>
+static inline void for_grid_y_chunks(uint32_t n, Launch launch) {
+    for (uint32_t done = 0; done < n; done += 65535u) launch(done, n - done > 65535u ? 65535u : n - done);
+}
+
 // plane_of_input / plane: per input its byte plane or NONE, and the planes (both null: the circuit has none)
 // event_reset: null, or the batch's event words: the import also leaves them "nobody flagged" (returns true when it did: the solve behind it needs no reset launch)
 bool launch_import(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint8_t *in, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,

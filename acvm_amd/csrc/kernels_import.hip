@@ -119,19 +119,10 @@ bool launch_import_device(hipStream_t s, const ImportDevice &x, uint4 *W, uint64
                           const uint32_t *plane_of_input, uint32_t *plane, uint32_t *event_reset) {
     if (!B || !n_in) return false;
     const ImportArgs a{W, Bp, B, n_in, (const uint4 *)x.in, ids, x.columns, x.encoding, x.stride, gate, plane_of_input, plane, event_reset};
-    // gridDim.y is limited to 65535
-    if (x.layout == EXPORT_WITNESS_MAJOR) {
-        for (uint32_t done = 0; done < n_in; done += 65535u) {
-            const uint32_t m = n_in - done > 65535u ? 65535u : n_in - done;
-            hipLaunchKernelGGL(import_device_wm_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done);
-        }
-    } else {
-        const uint32_t groups = (n_in + 3u) / 4u;
-        for (uint32_t done = 0; done < groups; done += 65535u) {
-            const uint32_t m = groups - done > 65535u ? 65535u : groups - done;
-            hipLaunchKernelGGL(import_device_im_kernel, dim3((B + 63u) / 64u, m), dim3(256), 0, s, a, done);
-        }
-    }
+    if (x.layout == EXPORT_WITNESS_MAJOR)
+        for_grid_y_chunks(n_in, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(import_device_wm_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done); });
+    else
+        for_grid_y_chunks((n_in + 3u) / 4u, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(import_device_im_kernel, dim3((B + 63u) / 64u, m), dim3(256), 0, s, a, done); });
     return event_reset != nullptr;
 }
 

@@ -121,20 +121,12 @@ bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_
                          const uint32_t *plane_of_input, uint32_t *plane, uint32_t *event_reset) {
     if (!B || !n_in) return false;
     const TypedImportArgs a{W, Bp, B, n_in, (const uint8_t *)x.in, ids, x.columns, x.encoding, export_element_size(x.encoding), x.stride, gate, plane_of_input, plane, event_reset};
-    // gridDim.y is limited to 65535
-    if (x.layout == EXPORT_INSTANCE_MAJOR) {
-        const uint32_t groups = (n_in + 3u) / 4u;
-        for (uint32_t done = 0; done < groups; done += 65535u) {
-            const uint32_t m = groups - done > 65535u ? 65535u : groups - done;
-            hipLaunchKernelGGL(import_narrow_im_kernel, dim3((B + 63u) / 64u, m), dim3(256), 0, s, a, done);
-        }
-    } else {
-        for (uint32_t done = 0; done < n_in; done += 65535u) {
-            const uint32_t m = n_in - done > 65535u ? 65535u : n_in - done;
-            if (x.layout == EXPORT_LAYOUT_BROADCAST) hipLaunchKernelGGL(import_broadcast_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done);
-            else hipLaunchKernelGGL(import_narrow_wm_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done);
-        }
-    }
+    if (x.layout == EXPORT_INSTANCE_MAJOR)
+        for_grid_y_chunks((n_in + 3u) / 4u, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(import_narrow_im_kernel, dim3((B + 63u) / 64u, m), dim3(256), 0, s, a, done); });
+    else if (x.layout == EXPORT_LAYOUT_BROADCAST)
+        for_grid_y_chunks(n_in, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(import_broadcast_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done); });
+    else
+        for_grid_y_chunks(n_in, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(import_narrow_wm_kernel, dim3((B + 255u) / 256u, m), dim3(256), 0, s, a, done); });
     return event_reset != nullptr;
 }
 
@@ -245,27 +237,20 @@ void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, 
     const uint32_t size = export_element_size(x.encoding);
     const NarrowExportArgs a{W, Bp, x.first, x.n, x.sel, x.n_sel, x.n_witnesses, row_of, producer, u.index, u.consts_plain, size, x.stride, (uint8_t *)x.out, x.mask};
     if (x.layout == EXPORT_WITNESS_MAJOR || x.n_sel < 4u) {
-        for (uint32_t done = 0; done < x.n_sel; done += 65535u) {  // gridDim.y is limited to 65535
-            const uint32_t m = x.n_sel - done > 65535u ? 65535u : x.n_sel - done;
-            hipLaunchKernelGGL(export_narrow_direct_kernel, dim3((x.n + 255u) / 256u, m), dim3(256), 0, s, a, x.layout, done);
-        }
+        for_grid_y_chunks(x.n_sel, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_narrow_direct_kernel, dim3((x.n + 255u) / 256u, m), dim3(256), 0, s, a, x.layout, done); });
         return;
     }
     const uint32_t T = narrow_tile_positions(size), tiles = (x.n_sel + T - 1u) / T;
     const uint32_t lds = 64u * (T * size + (size > 4u ? size : 4u)) + 64u * (T + 4u);  // 8.5 KiB (U8) .. 20.5 KiB (U32)
-    for (uint32_t done = 0; done < tiles; done += 65535u) {
-        const uint32_t m = tiles - done > 65535u ? 65535u : tiles - done;
-        hipLaunchKernelGGL(export_narrow_im_kernel, dim3((x.n + 63u) / 64u, m), dim3(256), lds, s, a, T, done * T);
-    }
+    for_grid_y_chunks(tiles, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_narrow_im_kernel, dim3((x.n + 63u) / 64u, m), dim3(256), lds, s, a, T, done * T); });
 }
 void launch_export_narrow_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow) {
     if (!n_lanes || !x.n_sel) return;
     const NarrowExportArgs a{W, Bp, x.first, x.n, x.sel, x.n_sel, x.n_witnesses, nullptr, nullptr, nullptr, nullptr, export_element_size(x.encoding), x.stride, (uint8_t *)x.out, x.mask};
-    for (uint32_t done = 0; done < x.n_sel; done += 65535u) {
-        const uint32_t m = x.n_sel - done > 65535u ? 65535u : x.n_sel - done;
+    for_grid_y_chunks(x.n_sel, [&](uint32_t done, uint32_t m) {
         hipLaunchKernelGGL(export_narrow_lanes_kernel, dim3((n_lanes + 255u) / 256u, m), dim3(256), 0, s, a, lanes, n_lanes, side, assigned_bits, n_slow, x.layout, done);
-    }
+    });
 }
 
 }  // namespace acvm
