@@ -98,7 +98,6 @@ int acvm_tuning_get(const char *key, long long *value) {
 }
 const char *acvm_tuning_key(unsigned index) { return tuning_key(index); }
 
-
 acvm_circuit_t *acvm_circuit_from_bytes(const uint8_t *bytes, size_t len) try {
     if (!bytes) { set_err(ACVM_E_INVALID, "null circuit bytes"); return nullptr; }
     if (!frh::self_check()) { set_err(ACVM_E_INVALID, "field constants self-check failed"); return nullptr; }
@@ -124,6 +123,46 @@ int acvm_circuit_opcode_kinds(const acvm_circuit_t *c, uint32_t first, uint32_t 
     }
     return 0;
 }
+int acvm_circuit_witness_set(const acvm_circuit_t *c, int which, uint32_t *out, uint32_t cap) try {
+    if (!c) return set_err(ACVM_E_INVALID, "null argument");
+    const Circuit &k = *c->c;
+    std::vector<uint32_t> v;
+    switch (which) {
+    case ACVM_SET_PRIVATE_PARAMETERS: v = k.private_parameters; break;
+    case ACVM_SET_PUBLIC_PARAMETERS: v = k.public_parameters; break;
+    case ACVM_SET_RETURN_VALUES: v = k.return_values; break;
+    case ACVM_SET_PUBLIC_INPUTS: v = k.public_parameters; v.insert(v.end(), k.return_values.begin(), k.return_values.end()); break;
+    case ACVM_SET_CIRCUIT_ARGUMENTS: v = k.private_parameters; v.insert(v.end(), k.public_parameters.begin(), k.public_parameters.end()); break;
+    default: return set_err(ACVM_E_INVALID, "unknown witness set");
+    }
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    for (uint32_t i = 0; i < v.size() && i < cap && out; i++) out[i] = v[i];
+    return (int)v.size();
+} ABI_CATCH
+
+// ---- the WitnessMap wire format (circuit.cpp witness_map_from_bytes / _to_bytes) for callers that hold no handle
+long long acvm_witness_map_decode(const uint8_t *bytes, size_t len, uint32_t *ids, uint8_t *values_be32, uint32_t cap) try {
+    if (!bytes) return set_err(ACVM_E_INVALID, "null argument");
+    std::vector<uint32_t> id;
+    std::vector<uint8_t> val;
+    std::string err;
+    if (!witness_map_from_bytes(bytes, len, id, val, err)) return set_err(ACVM_E_MALFORMED, err.c_str());
+    for (size_t i = 0; i < id.size() && i < cap; i++) {
+        if (ids) ids[i] = id[i];
+        if (values_be32) memcpy(values_be32 + 32 * i, val.data() + 32 * i, 32);
+    }
+    return (long long)id.size();
+} ABI_CATCH
+
+long long acvm_witness_map_encode(const uint32_t *ids, const uint8_t *values_be32, uint32_t n, uint8_t *out, size_t cap) try {
+    if (n && (!ids || !values_be32)) return set_err(ACVM_E_INVALID, "null argument");
+    std::vector<uint8_t> bytes;
+    std::string err;
+    if (!witness_map_to_bytes(ids, values_be32, n, bytes, err)) return set_err(ACVM_E_INVALID, err.c_str());
+    if (out && bytes.size() <= cap) memcpy(out, bytes.data(), bytes.size());
+    return (long long)bytes.size();
+} ABI_CATCH
 
 void plan_stats(const Plan &p, acvm_stats_t *out) {
     memset(out, 0, sizeof *out);
@@ -522,7 +561,6 @@ int acvm_batch_reset(acvm_batch_t *b) {
     return 0;
 }
 
-
 int acvm_batch_stats(acvm_batch_t *b, acvm_stats_t *out) {
     if (!b || !out) return set_err(ACVM_E_INVALID, "null argument");
     const Plan &p = b->plan();
@@ -542,5 +580,3 @@ int acvm_batch_stats(acvm_batch_t *b, acvm_stats_t *out) {
     }
     return 0;
 }
-
-

@@ -645,7 +645,8 @@ bool batch_generic_assigned(const acvm_batch *b, uint32_t w) { return w < b->pla
 int batch_enqueue_kept(acvm_batch *b, uint32_t n, const uint32_t *d_keep, uint32_t n_keep, uint8_t *d_out, uint8_t *h_out, hipStream_t copy_stream,
                        hipEvent_t exported, hipEvent_t arrived) {
     HIPCHK(hipSetDevice(b->device));
-    launch_export(b->stream, b->d_W, b->Bp, 0, n, d_keep, n_keep, d_out, b->unscale, b->d_slot_of);
+    const TableView t = level_table(b);
+    launch_export(b->stream, t.W, t.Bp, 0, n, d_keep, n_keep, d_out, t.u, t.row_of);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(exported, b->stream));
     HIPCHK(hipStreamWaitEvent(copy_stream, exported, 0));
@@ -654,51 +655,26 @@ int batch_enqueue_kept(acvm_batch *b, uint32_t n, const uint32_t *d_keep, uint32
     return 0;
 }
 
-// digests of lanes [first, first + n) of a witness table into host memory out32 ([n][32]), staged through the arena on stream s:
-// arena = (slow_index) | partial sums | digests. The per-instance lane of `assigned` comes from a device array (d_slow_index) or from the
-// batch's host vector (use_host_index: uploaded here); neither is needed when u.event is null (every lane read as an instance of the
-// level kernels).
-
+// results, kept witnesses and digests of the lanes of the side table (all of them at once)
 int side_table_outcome(acvm_batch *b, ExactOutcome *out) {
-    const Plan &p = b->plan();
     hipStream_t s = b->xstream();
     const uint32_t n_slow = (uint32_t)b->slow_ids.size(), n_keep = (uint32_t)b->async_keep.size();
     out->instance = b->slow_ids;
     out->results.resize(n_slow);
-    for (uint32_t t = 0; t < n_slow; t++) {
-        acvm_result_t &r = out->results[t];
-        memset(&r, 0, sizeof r);
-        const SlowResult &sr = b->slow_res[t];
-        r.status = sr.status; r.err = sr.err; r.opcode_index = sr.opcode_index; r.aux0 = sr.aux0; r.aux1 = sr.aux1;
-        r.n_call_stack = sr.n_call_stack > 16 ? 16 : sr.n_call_stack;
-        for (uint32_t k = 0; k < r.n_call_stack; k++) r.call_stack[k] = sr.call_stack[k];
-    }
-    const size_t sel_bytes = align256((size_t)std::max<uint32_t>(n_keep, 1) * 4), val_bytes = align256((size_t)n_slow * std::max<uint32_t>(n_keep, 1) * 32);
-    if (int rc = stage_reserve(b, sel_bytes + val_bytes)) return rc;
-    Unscale plain = b->unscale;
-    plain.event = b->d_slow_start;  // (opcode indices, never 0xFFFFFFFF = "solved by the level kernels": nothing in the side table is scaled)
+    for (uint32_t t = 0; t < n_slow; t++) result_head(b->slow_res[t], out->results[t]);
     if (n_keep) {
-        uint32_t *d_sel = (uint32_t *)b->d_stage;
-        uint8_t *d_val = b->d_stage + sel_bytes;
-        HIPCHK(hipMemcpyAsync(d_sel, b->async_keep.data(), (size_t)n_keep * 4, hipMemcpyHostToDevice, s));
-        launch_export(s, b->d_Wx, b->x_cap, 0, n_slow, d_sel, n_keep, d_val, plain);
         out->kept_values.resize((size_t)n_slow * n_keep * 32);
-        HIPCHK(hipMemcpyAsync(out->kept_values.data(), d_val, out->kept_values.size(), hipMemcpyDeviceToHost, s));
+        if (int rc = read_witnesses(b, s, side_table(b), 0, n_slow, b->async_keep.data(), n_keep, out->kept_values.data())) return rc;
         std::vector<uint32_t> bitmap((size_t)n_slow * b->n_words);
         HIPCHK(hipMemcpyAsync(bitmap.data(), b->d_assigned, bitmap.size() * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         out->kept_assigned.resize((size_t)n_slow * n_keep);
-        for (uint32_t t = 0; t < n_slow; t++)
-            for (uint32_t k = 0; k < n_keep; k++) {
-                const uint32_t w = b->async_keep[k];
-                const bool a = w < p.n_witnesses && ((bitmap[(size_t)(w >> 5) * n_slow + t] >> (w & 31)) & 1u);
-                out->kept_assigned[(size_t)t * n_keep + k] = a;
-                if (!a) memset(&out->kept_values[((size_t)t * n_keep + k) * 32], 0, 32);
-            }
+        AssignedView(b->plan().producer.data(), b->plan().n_witnesses, nullptr, n_slow, bitmap.data())  // (over the lanes themselves)
+            .fill(0, n_slow, b->async_keep.data(), n_keep, out->kept_assigned.data(), out->kept_values.data());
     }
     if (b->async_digest) {
         out->digests.resize((size_t)n_slow * 32);
-        if (int rc = digest_range(b, s, b->d_Wx, b->x_cap, 0, n_slow, plain, (const int32_t *)b->d_ids_x, false, n_slow, out->digests.data())) return rc;
+        if (int rc = digest_range(b, s, side_table(b), 0, n_slow, (const int32_t *)b->d_ids_x, false, n_slow, out->digests.data())) return rc;
     }
     return 0;
 }
@@ -733,7 +709,6 @@ int batch_finish_pending(acvm_batch *b, ExactOutcome *out) {
     b->pending = false;
     return rc;
 }
-
 
 // ---- ACVM::get_pending_foreign_call / resolve_pending_foreign_call (pwg/mod.rs:203-228) per instance
 static int fetch_pending(acvm_batch *b) {
@@ -953,5 +928,3 @@ int acvm_batch_resolve_foreign_call(acvm_batch_t *b, uint32_t instance, uint32_t
     ls.resolved_new = true;
     return 0;
 } ABI_CATCH
-
-

@@ -1,6 +1,7 @@
 // batch_internal.hpp -- what the translation units of the batch handle share (batch.cpp, batch_import.cpp, batch_schedule.cpp, batch_exact.cpp, batch_export.cpp,
-// probes.cpp): staging, the exact path's building blocks, result formatting. Internal to the library; the node driver sees batch.hpp only.
+// batch_messages.cpp, probes.cpp): staging, the exact path's building blocks, result formatting. Internal to the library; the node driver sees batch.hpp only.
 #pragma once
+#include "assigned_view.hpp"
 #include "batch.hpp"
 
 template <class T>
@@ -56,9 +57,44 @@ int solve_stepping(acvm_batch *b, bool one);
 int ensure_side_table(acvm_batch *b, uint32_t n_lanes, bool own_scratch);
 int side_table_outcome(acvm_batch *b, ExactOutcome *out);
 
+// ---- the table a host read or a digest is made from: where the values lie, how they are unscaled, witness -> row (null: row = witness index)
+struct TableView { const uint4 *W; uint64_t Bp; Unscale u; const uint32_t *row_of; };
+// the table of the level kernels: scaled columns leave through 1 / scale unless the lane's event word says it took the exact path
+static inline TableView level_table(const acvm_batch *b) { return {b->d_W, b->Bp, b->unscale, b->d_slot_of}; }
+// The side table (slot reuse, asynchronous exact jobs): lane t = the t-th flagged instance, row = witness index, nothing is scaled. The export and
+// digest kernels unscale a lane whose event word is 0xFFFFFFFF ("solved by the level kernels"); d_slow_start holds opcode indices, which never
+// are, so handing it over as the event words makes every lane read as "an instance of the exact path": plain values.
+static inline TableView side_table(const acvm_batch *b) {
+    Unscale plain = b->unscale;
+    plain.event = b->d_slow_start;
+    return {b->d_Wx, b->x_cap, plain, nullptr};
+}
+
+// ---- what every read-back entry point begins with: the exact job in flight is waited for (its outcome kept for the caller), an unsolved batch refused
+static inline int finish_pending_and_require_solved(acvm_batch *b) {
+    if (b->pending)
+        if (int rc = batch_finish_pending(b, &b->last_outcome)) return rc;
+    return b->solved ? 0 : set_err(ACVM_E_STATE, "batch not solved");
+}
+static inline int require_instance_range(const acvm_batch *b, uint32_t first, uint32_t n) {
+    return (uint64_t)first + n > b->B ? set_err(ACVM_E_INVALID, "instance range out of bounds") : 0;
+}
+
 // ---- batch_export.cpp
 int ensure_digest_tables(acvm_batch *b);
-int digest_range(acvm_batch *b, hipStream_t s, const uint4 *W, uint64_t Bp, uint32_t first, uint32_t n, const Unscale &u, const int32_t *d_slow_index,
-                 bool use_host_index, uint32_t n_slow, uint8_t *out32);
+int digest_range(acvm_batch *b, hipStream_t s, const TableView &t, uint32_t first, uint32_t n, const int32_t *d_slow_index, bool use_host_index, uint32_t n_slow,
+                 uint8_t *out32);
+// THE host read: witnesses sel[0 .. n_sel) (a host list) of lanes [first, first + n) of the table as canonical big-endian values into out_be32
+// ([n][n_sel][32], host), on stream s and waited for. Arena = the list | at most 64 MiB of values: a larger read takes several launches.
+int read_witnesses(acvm_batch *b, hipStream_t s, const TableView &t, uint32_t first, uint32_t n, const uint32_t *sel, uint32_t n_sel, uint8_t *out_be32);
+// one witness of one instance as 32 canonical big-endian bytes (message texts only; rare)
+bool fetch_one(acvm_batch *b, uint32_t j, uint32_t w, uint8_t out[32]);
+// the assigned set of the last solve (assigned_view.hpp) over the handle's bookkeeping; rows of the exact lanes' bitmap are copied when asked
+// for (the blocking copy: not while an exact job is pending), a failing copy leaves its error in *err (if given) and the row unassigned
+AssignedView batch_assigned(const acvm_batch *b, hipError_t *err = nullptr);
+
+// ---- batch_messages.cpp
+// status, error, opcode index, aux words and call stack of an exact lane's outcome (r zeroed first); the message text is format_message's
+void result_head(const SlowResult &sr, acvm_result_t &r);
 void format_message(acvm_batch *b, uint32_t j, const SlowResult &sr, acvm_result_t &r);
 void fill_result(acvm_batch *b, uint32_t j, acvm_result_t &r);
