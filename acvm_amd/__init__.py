@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
     "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
     "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
+    "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
 ]
 
 
@@ -346,6 +347,10 @@ def lib():
         L.acvm_batch_import_device_parts.argtypes = [C.c_void_p, C.POINTER(ImportPart), C.c_uint32]
         L.acvm_debug_import_list_copies.restype = C.c_uint64
         L.acvm_debug_import_list_copies.argtypes = [C.c_void_p]
+    if hasattr(L, "acvm_debug_table_read"):
+        L.acvm_debug_table_info.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+        L.acvm_debug_table_read.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.acvm_debug_batch_tables.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.acvm_batch_solve_opcode.argtypes = [C.c_void_p]
     L.acvm_bb_stubbed.restype = C.c_void_p
     L.acvm_bb_dummy.restype = C.c_void_p
@@ -516,6 +521,27 @@ def debug_grumpkin(what, param, inputs=()):
     data = b"".join(int(v).to_bytes(32, "big") for v in inputs)
     _check(lib().acvm_debug_grumpkin(what, param, data, len(inputs), out))
     return int.from_bytes(out.raw[:32], "big"), int.from_bytes(out.raw[32:], "big")
+
+
+# acvm_debug_table_info / _read: the lookup tables by number; acvm_debug_batch_tables: the bits of the mask
+TABLE_PED, TABLE_WIN, TABLE_SMALL, TABLE_SKEW, TABLE_PED2, TABLE_WIN16, TABLE_PEDW, TABLE_ECDSA_K1, TABLE_ECDSA_R1 = range(9)
+TABLE_BIT_PED2, TABLE_BIT_WIN16, TABLE_BIT_PEDW, TABLE_BIT_ECDSA = 1, 2, 4, 8
+
+
+def debug_table_info(table):
+    """(number of entries, whether the current device holds the table now) of one lookup table (see include/acvm_amd.h)"""
+    n, built = C.c_uint64(), C.c_int()
+    _check(lib().acvm_debug_table_info(table, C.byref(n), C.byref(built)))
+    return n.value, bool(built.value)
+
+
+def debug_table_read(table, entries):
+    """The raw 16 words of the given entries of one lookup table, as a uint32 array [n][16] (builds the table if the device does not hold it)"""
+    import numpy as np
+    idx = np.ascontiguousarray(entries, dtype=np.uint64).reshape(-1)
+    out = np.zeros((idx.size, 16), dtype=np.uint32)
+    _check(lib().acvm_debug_table_read(table, idx.ctypes.data, idx.size, out.ctypes.data))
+    return out
 
 
 SECP_PROBE_WORDS = ((2, 1), (1, 1), (2, 1), (2, 1), (1, 1), (1, 1), (3, 3), (5, 3), (1, 1), (2, 1), (2, 1), (1, 1))
@@ -837,6 +863,12 @@ class Batch:
         """host-to-device copies of the imports' lists -- a descriptor's column list, the lists of import_device_parts -- this handle has made
         (acvm_debug_import_list_copies)"""
         return lib().acvm_debug_import_list_copies(self._h)
+
+    def tables(self):
+        """the device-built lookup tables this handle's kernels read, as a mask of TABLE_BIT_* (acvm_debug_batch_tables)"""
+        m = C.c_uint32()
+        _check(lib().acvm_debug_batch_tables(self._h, C.byref(m)))
+        return m.value
 
     def reset(self):
         _check(lib().acvm_batch_reset(self._h))

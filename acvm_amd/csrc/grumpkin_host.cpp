@@ -453,6 +453,33 @@ size_t device_tables_missing_bytes(bool grumpkin, bool pedersen_level, bool wind
     return need;
 }
 
+uint64_t device_table_entries(uint32_t table) {
+    switch (table) {
+    case TABLE_PED: return (uint64_t)GRUMPKIN_N_GENERATORS * GRUMPKIN_PED_ENTRIES;
+    case TABLE_WIN: return (uint64_t)GRUMPKIN_N_WINDOW_BASES * GRUMPKIN_WIN_STRIDE;
+    case TABLE_SMALL: return 45;
+    case TABLE_SKEW: return 3;
+    case TABLE_PED2: return (uint64_t)30 << GRUMPKIN_PED2_LOG2;
+    case TABLE_WIN16: return (uint64_t)GRUMPKIN_N_WINDOW_BASES * GRUMPKIN_WIN16_STRIDE;
+    case TABLE_PEDW: return (uint64_t)2 * GRUMPKIN_PEDW_WINDOWS << GRUMPKIN_PEDW_BITS;
+    case TABLE_ECDSA_K1: case TABLE_ECDSA_R1: return ecdsa_gtable_bytes() / 2 / 64;
+    default: return 0;
+    }
+}
+bool device_table_built(uint32_t table) {
+    DeviceTableSet *S = current_set();
+    if (!S) return false;
+    std::lock_guard<std::mutex> lk(S->mu);
+    switch (table) {
+    case TABLE_PED: case TABLE_WIN: case TABLE_SMALL: case TABLE_SKEW: return S->base_built;
+    case TABLE_PED2: return S->t.ped2 != nullptr;
+    case TABLE_WIN16: return S->t.win16 != nullptr;
+    case TABLE_PEDW: return S->t.pedw != nullptr;
+    case TABLE_ECDSA_K1: case TABLE_ECDSA_R1: return S->ecdsa != nullptr;
+    default: return false;
+    }
+}
+
 // host copy of a table point (tests / self check): which = 0 ped, 1 win, 2 small, 3 skew
 bool grumpkin_host_point(uint32_t which, uint32_t index, uint8_t out_be[64]) {
     const HostTables &g_host = host_tables();

@@ -401,5 +401,18 @@ __global__ void grumpkin_probe_kernel(GrumpkinTables T, uint32_t what, uint32_t 
 void launch_grumpkin_probe(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_in, uint32_t *out) {
     hipLaunchKernelGGL(grumpkin_probe_kernel, dim3(1), dim3(64), 0, s, T, what, param, in, n_in, out);
 }
+// read-back of a lookup table (acvm_debug_table_read): one lane per requested entry, the raw 16 words as they lie in the table -- no arithmetic, no change of
+// form. The host has checked every index against the table's size.
+__global__ void __launch_bounds__(64) table_gather_kernel(const uint4 *__restrict__ table, const uint64_t *__restrict__ entries, uint32_t n, uint4 *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *p = table + entries[i] * 4;
+    uint4 *o = out + (uint64_t)i * 4;
+#pragma unroll
+    for (int k = 0; k < 4; k++) o[k] = p[k];
+}
+void launch_table_gather(hipStream_t s, const uint4 *table, const uint64_t *entries, uint32_t n, uint4 *out) {
+    if (n) hipLaunchKernelGGL(table_gather_kernel, dim3((n + 63) / 64), dim3(64), 0, s, table, entries, n, out);
+}
 
 }  // namespace acvm

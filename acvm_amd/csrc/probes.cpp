@@ -161,6 +161,81 @@ int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, u
     return 0;
 } ABI_CATCH
 
+// Read-back of the lookup tables (grumpkin_host.hpp: TABLE_*), entry by entry and in the form they are stored in. The table is built by the function the
+// product builds it with; the probe holds the device's set like acvm_debug_grumpkin.
+int acvm_debug_table_info(uint32_t table, uint64_t *n_entries, int *built) try {
+    const uint64_t n = device_table_entries(table);
+    if (!n || !n_entries || !built) return set_err(ACVM_E_INVALID, "no such table, or a null argument");
+    *n_entries = n;
+    *built = device_table_built(table) ? 1 : 0;
+    (void)hipGetLastError();  // (asked without a device: not an error of this call)
+    return 0;
+} ABI_CATCH
+
+int acvm_debug_table_read(uint32_t table, const uint64_t *entries, uint32_t n, uint32_t *out_words16) try {
+    static const char *const NAME[N_DEVICE_TABLES] = {"ped", "win", "small", "skew", "ped2", "win16", "pedw", "ECDSA secp256k1", "ECDSA secp256r1"};
+    const uint64_t n_entries = device_table_entries(table);
+    if (!n_entries) return set_err(ACVM_E_INVALID, "no such table");
+    if (n && (!entries || !out_words16)) return set_err(ACVM_E_INVALID, "null argument");
+    for (uint32_t i = 0; i < n; i++)
+        if (entries[i] >= n_entries)
+            return set_err(ACVM_E_INVALID, "entries[" + std::to_string(i) + "] = " + std::to_string(entries[i]) + " is outside the " + NAME[table] + " table (" +
+                                               std::to_string(n_entries) + " entries)");
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    struct Hold {
+        int d;
+        explicit Hold(int dev_) : d(dev_) { device_tables_retain(d); }
+        ~Hold() { device_tables_unref(d); }
+    } hold(dev);
+    GrumpkinTables tabs{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const uint4 *src = nullptr;
+    const char *why = "";
+    if (table == TABLE_ECDSA_K1 || table == TABLE_ECDSA_R1) {
+        const uint32_t *g = ecdsa_generator_tables();
+        if (g) src = (const uint4 *)(g + (table == TABLE_ECDSA_R1 ? n_entries * 16 : 0));
+    } else if (table == TABLE_PED2) {
+        if (grumpkin_pair_table(&tabs)) src = tabs.ped2;
+    } else if (table == TABLE_PEDW) {
+        if (grumpkin_window_table(&tabs)) src = tabs.pedw;
+        why = ": it needs its own bytes plus a quarter of the device's memory free";
+    } else if (grumpkin_tables(&tabs)) {
+        src = table == TABLE_PED ? tabs.ped : table == TABLE_WIN ? tabs.win : table == TABLE_SMALL ? tabs.small : table == TABLE_SKEW ? tabs.skew : tabs.win16;
+        why = ": it is built with the device's host tables, when tuning win16 is set and its 268 MB are free";
+    }
+    if (!src) {
+        (void)hipGetLastError();
+        return set_err(ACVM_E_DEVICE, std::string("could not build the ") + NAME[table] + " table on the device" + why);
+    }
+    if (!n) return 0;
+    uint64_t *d_idx = nullptr;
+    uint4 *d_out = nullptr;
+    HIPCHK(hipMalloc((void **)&d_idx, (size_t)n * 8));
+    if (hipMalloc((void **)&d_out, (size_t)n * 64) != hipSuccess) {
+        hipFree(d_idx);
+        return set_err(ACVM_E_DEVICE, "hipMalloc failed");
+    }
+    int rc = 0;
+    auto step = [&](hipError_t e, const char *what_) { if (!rc && e != hipSuccess) rc = set_err(ACVM_E_DEVICE, std::string(what_) + ": " + hipGetErrorString(e)); };
+    step(hipMemcpy(d_idx, entries, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy");
+    if (!rc) launch_table_gather(nullptr, src, d_idx, n, d_out);
+    step(hipGetLastError(), "table_gather_kernel");
+    step(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    step(hipMemcpy(out_words16, d_out, (size_t)n * 64, hipMemcpyDeviceToHost), "hipMemcpy");
+    hipFree(d_idx);
+    hipFree(d_out);
+    return rc;
+} ABI_CATCH
+
+// Which of the device-built tables the handle's device program reads (ACVM_TABLE_BIT_*): its kernels pick by these pointers alone (pedersen_walk takes
+// pedw when it is there and ped2 otherwise, fixed_base_mul takes win16 when it is there).
+int acvm_debug_batch_tables(const acvm_batch_t *b, uint32_t *mask) {
+    if (!b || !mask) return set_err(ACVM_E_INVALID, "null argument");
+    const GrumpkinTables &t = b->dp.grumpkin;
+    *mask = (t.ped2 && !t.pedw ? 1u : 0u) | (t.win16 ? 2u : 0u) | (t.pedw ? 4u : 0u) | (b->dp.ecdsa_g ? 8u : 0u);
+    return 0;
+}
+
 // One routine of the BN254-Fr device library per call, one device lane per item, raw limbs in and out (fr_probe.hpp).
 int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out) try {
     const uint32_t wi = fr_probe_words(what, false), wo = fr_probe_words(what, true);

@@ -212,6 +212,21 @@ int acvm_selftest(uint32_t n, uint64_t seed);
  * 8 / 9 = in[0] * (in[1], in[2]) for a 256-bit integer and an affine point: 8 through SchnorrVerify's GLV + window-table path, 9 by double-and-add.
  * in: n_in x 32 bytes big-endian; out: 64 bytes (x || y) big-endian. */
 int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, uint32_t n_in, uint8_t *out_be64);
+/* Read-back of the lookup tables of the Grumpkin and ECDSA kernels, entry by entry (tests/test_gpu_curve_tables.py compares every word with integers).
+ * table: 0 ped [30][512], 1 win [4][32][255], 2 small [3][15], 3 skew [3], 4 ped2 [30][512][512], 5 win16 [4][16][65535], 6 pedw [2][11][2^24],
+ * 7 / 8 the generator table [16][65536] of secp256k1 / secp256r1 (definitions and storage forms: acvm_amd/csrc/grumpkin_host.hpp). An entry is one affine
+ * point of 16 u32: x limbs 0..7, y limbs 0..7, little-endian.
+ * acvm_debug_table_info: the number of entries, and whether the current device holds the table right now (builds nothing; 0 without a device).
+ * acvm_debug_table_read: builds the table on the current device if it is missing -- with the functions a batch handle builds it with, under the same
+ * conditions (pedw: its 23.6 GB plus a quarter of the device's memory free; win16: tuning win16 set when the device's first Grumpkin table is built) --
+ * and copies the RAW 16 words of entries[0..n) to out_words16, one device lane per entry, without arithmetic or change of form. ACVM_E_INVALID for an
+ * unknown table or an index at or beyond the number of entries (checked on the host, nothing is launched); ACVM_E_DEVICE with the table's name when it
+ * cannot be built. */
+int acvm_debug_table_info(uint32_t table, uint64_t *n_entries, int *built);
+int acvm_debug_table_read(uint32_t table, const uint64_t *entries, uint32_t n, uint32_t *out_words16);
+/* Which device-built tables the kernels of this handle read: bit 0 ped2, bit 1 win16, bit 2 pedw, bit 3 the ECDSA generator tables (the level Pedersen
+ * kernel reads pedw when the handle has it and ped2 otherwise: never both bits). Reads the handle's device program; changes nothing. */
+int acvm_debug_batch_tables(const acvm_batch_t *b, uint32_t *mask);
 /* Component probes of the ECDSA kernels (secp_device.hpp run ON THE DEVICE against integers: k256 / p256 are the spec of blackbox_solver/src/lib.rs:66-210,
  * the tests compare with Python): curve 0 = secp256k1, 1 = secp256r1; one device lane per item. what: 0 a b -> a b; 1 a -> a^2; 2 a b -> a + b; 3 a b -> a - b;
  * 4 a -> 1 / a (0 for 0); 5 a -> a^((p + 1) / 4), all mod p; 6 X Y Z -> the Jacobian double; 7 X Y Z x y -> the Jacobian sum with the affine point (x, y);
