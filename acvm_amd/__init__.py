@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
     "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
     "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
+    "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
 ]
 
 
@@ -62,6 +63,12 @@ class ExportDesc(C.Structure):
     """acvm_export_desc_t"""
     _fields_ = [("encoding", C.c_uint32), ("layout", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32), ("witnesses", C.POINTER(C.c_uint32)),
                 ("n_witnesses", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class OutcomesDesc(C.Structure):
+    """acvm_outcomes_desc_t (the pointers are device addresses, 0 / None = NULL)"""
+    _fields_ = [("first", C.c_uint32), ("n", C.c_uint32), ("d_status", C.c_void_p), ("d_err", C.c_void_p), ("d_opcode_index", C.c_void_p),
+                ("select_mask", C.c_uint32), ("d_selected", C.c_void_p)]
 
 
 class ImportDesc(C.Structure):
@@ -347,6 +354,12 @@ def lib():
         L.acvm_batch_import_device_parts.argtypes = [C.c_void_p, C.POINTER(ImportPart), C.c_uint32]
         L.acvm_debug_import_list_copies.restype = C.c_uint64
         L.acvm_debug_import_list_copies.argtypes = [C.c_void_p]
+    if hasattr(L, "acvm_batch_outcomes_device"):
+        L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
+        L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.acvm_debug_export_h2d_bytes.restype = C.c_uint64
+        L.acvm_debug_export_h2d_bytes.argtypes = [C.c_void_p]
+        L.acvm_debug_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "acvm_debug_table_read"):
         L.acvm_debug_table_info.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.acvm_debug_table_read.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -589,6 +602,20 @@ def debug_inverse_batch(den, inv_chunk, slot_of=None):
     _check(lib().acvm_debug_inverse_batch(d.ctypes.data, n_jobs, B, inv_chunk, None if s is None else s.ctypes.data, inv.ctypes.data, ev.ctypes.data,
                                           C.byref(dc), C.byref(hc)))
     return inv, ev, dc.value, hc.value
+
+
+def debug_select(status, select_mask, out=None, want_list=True):
+    """The shipped selection kernels on a status array of the caller's (acvm_debug_select): status = uint8 [n]. Returns (list, count): list = uint32 [n],
+    of which [0, count) are the selected indices in ascending order and the rest is what `out` (default: zeros) held; None with want_list=False."""
+    import numpy as np
+    st = np.ascontiguousarray(status, dtype=np.uint8).reshape(-1)
+    n = st.shape[0]
+    lst = None
+    if want_list:
+        lst = np.zeros(n, dtype=np.uint32) if out is None else np.ascontiguousarray(out, dtype=np.uint32).reshape(n).copy()
+    count = C.c_uint32()
+    _check(lib().acvm_debug_select(st.ctypes.data if n else None, n, select_mask, lst.ctypes.data if lst is not None and n else None, C.byref(count)))
+    return lst, count.value
 
 
 def decompress_witness(data: bytes) -> dict:
@@ -953,6 +980,30 @@ class Batch:
             arr = (C.c_uint32 * max(len(ws), 1))(*ws)
             desc.witnesses, desc.n_witnesses = arr, len(ws)
         _check(lib().acvm_batch_export_device(self._h, C.byref(desc), d_ptr, d_assigned))
+
+    def export_device_list(self, d_instances: int, n: int, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, witnesses=None, stride=0, d_assigned=None):
+        """export_device for LISTED instances (acvm_batch_export_device_list): row i of the output is instance d_instances[i], a device array of n absolute
+        instance numbers (any order, repeats allowed; an entry beyond the batch reads as an instance that assigned nothing). Everything else as export_device."""
+        desc = ExportDesc(encoding=encoding, layout=layout, first=0, n=n, stride=stride)
+        if witnesses is not None:
+            ws = list(witnesses)
+            arr = (C.c_uint32 * max(len(ws), 1))(*ws)
+            desc.witnesses, desc.n_witnesses = arr, len(ws)
+        _check(lib().acvm_batch_export_device_list(self._h, C.byref(desc), d_instances, d_ptr, d_assigned))
+
+    def outcomes_device(self, first=0, n=None, d_status=None, d_err=None, d_opcode_index=None, select_mask=0, d_selected=None, count=True):
+        """The outcomes of instances [first, first + n) as device columns (acvm_batch_outcomes_device): d_status / d_err uint8 [n], d_opcode_index uint32 [n],
+        each a device pointer or None; d_selected: device pointer of uint32 [n] that receives the ascending absolute numbers of the instances whose
+        status has its bit set in select_mask (1 << STATUS_SOLVED ...). Returns the number selected (None with count=False)."""
+        n = self.B - first if n is None else n
+        desc = OutcomesDesc(first=first, n=n, d_status=d_status, d_err=d_err, d_opcode_index=d_opcode_index, select_mask=select_mask, d_selected=d_selected)
+        got = C.c_uint32()
+        _check(lib().acvm_batch_outcomes_device(self._h, C.byref(desc), C.byref(got) if count else None))
+        return got.value if count else None
+
+    def export_h2d_bytes(self) -> int:
+        """bytes the device exports and outcomes_device have copied host-to-device for this handle so far (acvm_debug_export_h2d_bytes)"""
+        return lib().acvm_debug_export_h2d_bytes(self._h)
 
     def digest(self, first=0, n=None):
         """Per-instance 32-byte digest of the witness map (acvm_batch_digest): uint8 array [n][32]."""

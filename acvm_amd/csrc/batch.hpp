@@ -161,6 +161,12 @@ struct acvm_batch {
     uint32_t *d_import_lists = nullptr;
     size_t import_lists_cap = 0;
     uint64_t n_import_list_copies = 0;  // (acvm_debug_import_list_copies)
+    // The instance -> exact-lane map of acvm_batch_export_device_list on the device: slow_index as the kernels read it (-1: generic), one word per
+    // instance of the handle. slow_epoch counts the changes of slow_index (batch_schedule.cpp, batch_exact.cpp solve_stepping); the map is rebuilt ON the device
+    // (a fill, then a scatter of slow_ids) when a list export finds it older than that, so nothing per instance is uploaded while events_clean holds
+    int32_t *d_lane_map = nullptr;
+    uint64_t slow_epoch = 0, lane_map_epoch = 0;
+    uint64_t n_export_h2d_bytes = 0;  // (acvm_debug_export_h2d_bytes)
     std::vector<uint32_t> init_rows, plane_of_input;  // host copies of d_init_rows (slot reuse) and d_byte_plane_of_input (byte planes): what a plan of parts picks from
     hipEvent_t ev_counted = nullptr;  // behind the event count of a solve: what the host waits for instead of the whole stream
     bool holds_tables = false;  // a reference on the device's lookup-table set (grumpkin_host.hpp device_tables_retain)
@@ -236,6 +242,7 @@ struct acvm_batch {
         if (d_stage) hipFree(d_stage);
         if (d_fetch) hipFree(d_fetch);
         if (d_import_lists) hipFree(d_import_lists);
+        if (d_lane_map) hipFree(d_lane_map);
         if (stream_x) { hipStreamSynchronize(stream_x); hipStreamDestroy(stream_x); }
         if (ev_x_ready) hipEventDestroy(ev_x_ready);
         for (int k = 0; k < (int)N_CLS; k++)

@@ -454,6 +454,7 @@ int solve_stepping(acvm_batch *b, bool one) {
     if (!b->stepping) {
         b->slow_ids.resize(n_slow);
         b->events_clean = false;
+        b->slow_epoch++;
         for (uint32_t j = 0; j < n_slow; j++) { b->slow_ids[j] = j; b->slow_index[j] = (int32_t)j; }
         b->slow_start.assign(n_slow, 0);
         std::fill(b->h_event.begin(), b->h_event.end(), 0u);

@@ -334,23 +334,25 @@ static int ensure_mont256_table(acvm_batch *b) {
     return upload(&b->d_unscale_m256, uc);
 }
 
-int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
+// What the range export and the list export check alike, in one order: the descriptor's shape, the pointers, the batch's state, the range (list: the
+// list's length against nothing -- its entries are the device's to judge), the stride, what the batch kept. 0 and *n_sel / *stride, or the refusal.
+static int export_device_checks(acvm_batch *b, const acvm_export_desc_t *d, const void *d_values, const uint32_t *d_instances, bool list, uint32_t *n_sel_out,
+                                uint64_t *stride_out) {
     if (!d) return set_err(ACVM_E_INVALID, "null argument");
     // (the buffer checks of import_plan.hpp, shared with the imports)
     std::string refusal = buffer_check_shape(d->encoding, d->layout, false);
     if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
-    if (!b || !d_values) return set_err(ACVM_E_INVALID, "null argument");
-    const bool narrow = export_enc_is_narrow(d->encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
+    if (list && d->first != 0) return set_err(ACVM_E_INVALID, "first must be 0 for a list export: the list holds absolute instance numbers");
+    if (!b || !d_values || (list && d->n && !d_instances)) return set_err(ACVM_E_INVALID, "null argument");
     refusal = buffer_check_pointer(d->encoding, d_values);
     if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
     if (int rc = finish_pending_and_require_solved(b)) return rc;
-    const uint32_t first = d->first, n = d->n;
-    if (int rc = require_instance_range(b, first, n)) return rc;
-    const uint32_t nw = b->plan().n_witnesses;
+    if (!list)
+        if (int rc = require_instance_range(b, d->first, d->n)) return rc;
     const bool whole = d->witnesses == nullptr;
-    const uint32_t n_sel = whole ? nw : d->n_witnesses;
+    const uint32_t n_sel = whole ? b->plan().n_witnesses : d->n_witnesses;
     uint64_t stride = d->stride;
-    refusal = buffer_check_stride(d->layout, n, n_sel, &stride);
+    refusal = buffer_check_stride(d->layout, d->n, n_sel, &stride);
     if (!refusal.empty()) return set_err(ACVM_E_INVALID, refusal);
     if (whole) {
         if (b->side()) return set_err(ACVM_E_STATE, "the batch recycles witness rows (ACVM_BATCH_REUSE_SLOTS) or solved its exact lanes in the side table: full maps are not kept; read the kept witnesses and the digest");
@@ -359,6 +361,19 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
         if (int rc = refuse_if_next_imported(b, d->witnesses, n_sel, false)) return rc;
         if (int rc = reuse_check_kept(b, d->witnesses, n_sel)) return rc;
     }
+    *n_sel_out = n_sel;
+    *stride_out = stride;
+    return 0;
+}
+
+int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
+    uint32_t n_sel = 0;
+    uint64_t stride = 0;
+    if (int rc = export_device_checks(b, d, d_values, nullptr, false, &n_sel, &stride)) return rc;
+    const bool narrow = export_enc_is_narrow(d->encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
+    const uint32_t first = d->first, n = d->n;
+    const uint32_t nw = b->plan().n_witnesses;
+    const bool whole = d->witnesses == nullptr;
     if (!n || !n_sel) return 0;
     HIPCHK(hipSetDevice(b->device));
     if (d->encoding == EXPORT_ENC_MONT256_LE)
@@ -375,6 +390,7 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
     uint32_t *d_sel = whole ? nullptr : (uint32_t *)b->d_stage, *d_lanes = (uint32_t *)(b->d_stage + sel_bytes);
     if (!whole) HIPCHK(hipMemcpyAsync(d_sel, d->witnesses, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
     if (n_lanes) HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
+    b->n_export_h2d_bytes += (whole ? 0 : (uint64_t)n_sel * 4) + (uint64_t)lanes.size() * 4;
     const ExportDevice x{d->encoding, d->layout, first, n, d_sel, n_sel, nw, stride, d_values, d_assigned};
     // every lane as a generic instance (scaled columns, the planner's assigned set) ...
     if (n_lanes < n) {
@@ -387,6 +403,108 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
                                                                            (uint32_t)b->slow_ids.size());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));  // (also what keeps `lanes` and the caller's list alive for their copies)
+    return 0;
+} ABI_CATCH
+
+// ---- the map of LISTED instances (include/acvm_amd.h acvm_batch_export_device_list). The list lives on the device, so which of its rows are exact lanes
+// is the kernels' to find out: through the handle's instance -> lane map, which is made on the device from slow_ids (n_slow words go up, once per change
+// of slow_index; none while no instance left the generic path). ids_stage: room for those words in the arena the caller reserved.
+static int lane_map_ready(acvm_batch *b, hipStream_t s, uint32_t *ids_stage) {
+    if (b->d_lane_map && b->lane_map_epoch == b->slow_epoch) return 0;
+    if (!b->d_lane_map) HIPCHK(hipMalloc((void **)&b->d_lane_map, (size_t)std::max<uint32_t>(b->capacity, 1) * 4));
+    launch_fill_u32(s, (uint32_t *)b->d_lane_map, 0xFFFFFFFFu, b->capacity);
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size();
+    if (n_slow) {
+        HIPCHK(hipMemcpyAsync(ids_stage, b->slow_ids.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
+        b->n_export_h2d_bytes += (uint64_t)n_slow * 4;
+        launch_lane_map_scatter(s, b->d_lane_map, b->capacity, ids_stage, n_slow);
+    }
+    HIPCHK(hipGetLastError());
+    b->lane_map_epoch = b->slow_epoch;
+    return 0;
+}
+
+int acvm_batch_export_device_list(acvm_batch_t *b, const acvm_export_desc_t *d, const uint32_t *d_instances, void *d_values, uint8_t *d_assigned) try {
+    uint32_t n_sel = 0;
+    uint64_t stride = 0;
+    if (int rc = export_device_checks(b, d, d_values, d_instances, true, &n_sel, &stride)) return rc;
+    const uint32_t n = d->n, nw = b->plan().n_witnesses;
+    const bool whole = d->witnesses == nullptr;
+    if (!n || !n_sel) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (d->encoding == EXPORT_ENC_MONT256_LE)
+        if (int rc = ensure_mont256_table(b)) return rc;
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size();
+    const bool map_stale = !(b->d_lane_map && b->lane_map_epoch == b->slow_epoch);
+    const size_t sel_bytes = whole ? 0 : align256((size_t)n_sel * 4), ids_bytes = map_stale ? (size_t)n_slow * 4 : 0;
+    if (sel_bytes + ids_bytes)
+        if (int rc = stage_reserve(b, sel_bytes + ids_bytes)) return rc;
+    hipStream_t s = b->stream;
+    uint32_t *d_sel = whole ? nullptr : (uint32_t *)b->d_stage;
+    if (!whole) {
+        HIPCHK(hipMemcpyAsync(d_sel, d->witnesses, (size_t)n_sel * 4, hipMemcpyHostToDevice, s));
+        b->n_export_h2d_bytes += (uint64_t)n_sel * 4;
+    }
+    if (int rc = lane_map_ready(b, s, (uint32_t *)(b->d_stage + sel_bytes))) return rc;
+    const ExportDevice x{d->encoding, d->layout, 0u, n, d_sel, n_sel, nw, stride, d_values, d_assigned};
+    const ExportListSource src{d_instances, b->B, b->d_lane_map, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), b->d_assigned, n_slow};
+    if (export_enc_is_narrow(d->encoding)) launch_export_narrow_list(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, src);
+    else launch_export_device_list(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, d->encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain, src);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps the caller's witness list and slow_ids alive for their copies)
+    return 0;
+} ABI_CATCH
+
+uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b) { return b ? b->n_export_h2d_bytes : 0; }
+
+// ---- per-instance outcomes where the witnesses are (include/acvm_amd.h acvm_batch_outcomes_device). The host's slow_res is the authority (Brillig retries
+// and host callbacks finalise lanes there): every instance of the range is written as a generic one -- Solved -- and the records of the exact lanes of
+// the range go over them, one small list like the range export's `lanes`. The selection runs on the status column (a scratch one when the caller wants none).
+int acvm_batch_outcomes_device(acvm_batch_t *b, const acvm_outcomes_desc_t *d, uint32_t *n_selected) try {
+    if (!d) return set_err(ACVM_E_INVALID, "null argument");
+    if (!d->d_status && !d->d_err && !d->d_opcode_index && !d->d_selected && !n_selected)
+        return set_err(ACVM_E_INVALID, "nothing to write: every column, the selection and its count are null");
+    if (!b) return set_err(ACVM_E_INVALID, "null argument");
+    if (int rc = finish_pending_and_require_solved(b)) return rc;
+    const uint32_t first = d->first, n = d->n;
+    if (int rc = require_instance_range(b, first, n)) return rc;
+    if (n_selected) *n_selected = 0;
+    if (!n) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    // {status, err, opcode index, index in the range} of the exact lanes of the range (slow_ids ascends with the instance); fill_result's rule
+    std::vector<uint32_t> records;
+    if (b->plan().n_opcodes != 0) {
+        const auto lo = std::lower_bound(b->slow_ids.begin(), b->slow_ids.end(), first);
+        for (auto it = lo; it != b->slow_ids.end() && (uint64_t)*it < (uint64_t)first + n; ++it) {
+            const SlowResult &sr = b->slow_res[(size_t)(it - b->slow_ids.begin())];
+            records.insert(records.end(), {sr.status, sr.err, sr.opcode_index, *it - first});
+        }
+    }
+    const uint32_t n_lanes = (uint32_t)(records.size() / 4);
+    const bool select = d->d_selected || n_selected;
+    const size_t rec_bytes = align256(records.size() * 4), status_bytes = select && !d->d_status ? align256(n) : 0;
+    const size_t scan_bytes = select ? align256((select_scratch_words(n) + 1) * 4) : 0;
+    if (rec_bytes + status_bytes + scan_bytes)
+        if (int rc = stage_reserve(b, rec_bytes + status_bytes + scan_bytes)) return rc;
+    hipStream_t s = b->stream;
+    uint32_t *d_records = (uint32_t *)b->d_stage;
+    uint8_t *d_status = d->d_status ? d->d_status : select ? b->d_stage + rec_bytes : nullptr;
+    uint32_t *d_scan = (uint32_t *)(b->d_stage + rec_bytes + status_bytes), *d_count = d_scan + select_scratch_words(n);
+    if (n_lanes) {
+        HIPCHK(hipMemcpyAsync(d_records, records.data(), records.size() * 4, hipMemcpyHostToDevice, s));
+        b->n_export_h2d_bytes += (uint64_t)records.size() * 4;
+    }
+    launch_outcomes_fill(s, n, d_status, d->d_err, d->d_opcode_index);
+    launch_outcomes_lanes(s, d_records, n_lanes, n, d_status, d->d_err, d->d_opcode_index);
+    uint32_t count = 0;
+    if (select) {
+        launch_select(s, d_status, first, n, d->select_mask, d_scan, d->d_selected, d_count);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&count, d_count, 4, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps `records` and `count` alive for their copies)
+    if (n_selected) *n_selected = count;
     return 0;
 } ABI_CATCH
 

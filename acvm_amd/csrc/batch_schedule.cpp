@@ -176,6 +176,7 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
             HIPCHK(hipStreamSynchronize(s));
         } else std::fill(b->h_event.begin(), b->h_event.end(), 0xFFFFFFFFu);
         b->slow_ids.clear();
+        b->slow_epoch++;
         std::fill(b->slow_index.begin(), b->slow_index.end(), -1);
         for (uint32_t j = 0; j < b->B; j++)
             if (b->h_event[j] != 0xFFFFFFFFu) {

@@ -251,6 +251,78 @@ __global__ void __launch_bounds__(256) export_device_lanes_kernel(const ExportAr
     export_store_nt(a.out + 2 * at + 1, e.hi);
     if (a.mask) a.mask[at] = assigned;
 }
+// acvm_batch_export_device_list: the same two shapes with the instance of output row i read from a list (kernels.hpp ExportListSource). What
+// a row holds is decided per lane: an entry beyond the batch is an instance that assigned nothing, an instance of the exact path is read like
+// export_device_lanes_kernel reads it, every other like export_generic_element. Exact lanes are few: the divergence between the two is theirs alone.
+struct ExportListRow {
+    uint32_t j;    // the instance; >= B: no instance
+    int32_t lane;  // its lane of the exact path, or -1
+};
+__device__ __forceinline__ ExportListRow export_list_row(const ExportListSource &L, uint64_t i) {
+    ExportListRow r;
+    r.j = L.list[i];
+    r.lane = r.j < L.B ? L.lane_of[r.j] : -1;
+    return r;
+}
+__device__ __forceinline__ ExportElement export_list_element(const ExportArgs &a, const ExportListSource &L, uint32_t k, const ExportListRow &r, bool &assigned) {
+    if (r.j >= L.B) {
+        assigned = false;
+        return export_encode(fr_zero(), fr_zero(), a.encoding, false);
+    }
+    if (r.lane < 0) return export_generic_element(a, k, r.j, assigned);
+    const uint32_t w = a.sel ? a.sel[k] : k;
+    assigned = w < a.n_witnesses && ((L.assigned_bits[(uint64_t)(w >> 5) * L.n_slow + (uint32_t)r.lane] >> (w & 31u)) & 1u) != 0u;
+    if (!assigned) return export_encode(fr_zero(), fr_zero(), a.encoding, false);
+    return export_encode(fr_load(L.Wx, w, L.Bpx, L.side ? (uint64_t)(uint32_t)r.lane : (uint64_t)r.j), export_plain_factor(a.encoding), a.encoding, true);
+}
+__global__ void __launch_bounds__(256) export_list_direct_kernel(const ExportArgs a, const ExportListSource L, uint32_t layout, uint32_t k0) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t k = k0 + blockIdx.y;
+    if (i >= a.n) return;
+    bool assigned;
+    const ExportElement e = export_list_element(a, L, k, export_list_row(L, i), assigned);
+    const uint64_t at = export_element_index(layout, a.stride, i, k);
+    export_store_nt(a.out + 2 * at, e.lo);
+    export_store_nt(a.out + 2 * at + 1, e.hi);
+    if (a.mask) a.mask[at] = assigned;
+}
+// (export_device_im_kernel with the source column of each tile lane taken from the list; the LDS transpose is the same)
+template <uint32_t T>
+__global__ void __launch_bounds__(EXPORT_THREADS) export_list_im_kernel(const ExportArgs a, const ExportListSource L, uint32_t k0) {
+    static_assert(T % EXPORT_WAVES == 0 && (EXPORT_TILE_I * 2u * T) % EXPORT_THREADS == 0, "four waves share the positions; whole steps");
+    __shared__ uint4 tile[T][2][65];
+    __shared__ uint8_t tile_assigned[T][64];
+    const uint32_t t = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * EXPORT_TILE_I;
+    const uint32_t kb = k0 + blockIdx.y * T;
+    {
+        const uint32_t ji = export_tile_lane(t);
+        const uint64_t i = i0 + ji;
+        ExportListRow r{0xFFFFFFFFu, -1};
+        if (i < a.n) r = export_list_row(L, i);
+#pragma unroll 1
+        for (uint32_t kk = export_tile_first_position(t); kk < T; kk += EXPORT_WAVES) {
+            const uint32_t k = kb + kk;
+            if (k >= a.n_sel || i >= a.n) continue;
+            bool assigned;
+            const ExportElement e = export_list_element(a, L, k, r, assigned);
+            tile[kk][0][ji] = e.lo;
+            tile[kk][1][ji] = e.hi;
+            tile_assigned[kk][ji] = assigned;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t step = 0; step < export_tile_steps(T); step++) {
+        const ExportTileUnit q = export_tile_unit(T, t, step);
+        const uint64_t i = i0 + q.ji;
+        const uint32_t k = kb + q.kk;
+        if (i >= a.n || k >= a.n_sel) continue;
+        const uint64_t at = export_element_index(EXPORT_INSTANCE_MAJOR, a.stride, i, k);
+        export_store_nt(a.out + 2 * at + q.half, tile[q.kk][q.half][q.ji]);
+        if (a.mask && q.half == 0) a.mask[at] = tile_assigned[q.kk][q.ji];
+    }
+}
 // columns of the instances that continue on the exact path: every scaled witness the lane keeps back to its plain Montgomery value. The lane keeps
 // what init_assigned_kernel marks -- outputs of opcodes in front of its event; the rows behind it are written by the exact kernels before anything
 // reads them, so an instance that fails early costs next to nothing here (with relaxed rows nearly every gate output is "scaled").
@@ -568,6 +640,20 @@ void launch_export_device(hipStream_t s, const ExportDevice &x, const uint4 *W, 
         const uint32_t m = tiles - done > 65535u ? 65535u : tiles - done;
         hipLaunchKernelGGL(export_device_im_kernel<EXPORT_TILE_T>, dim3((x.n + EXPORT_TILE_I - 1u) / EXPORT_TILE_I, m), dim3(EXPORT_THREADS), 0, s, a, done * EXPORT_TILE_T);
     }
+}
+// (the same choice between the two kernels as launch_export_device)
+void launch_export_device_list(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                               const uint32_t *u_factor, const ExportListSource &src) {
+    if (!x.n || !x.n_sel) return;
+    const ExportArgs a{W, Bp, 0u, x.n, x.sel, x.n_sel, x.n_witnesses, row_of, producer, u.index, u_factor, x.encoding, x.stride, (uint4 *)x.out, x.mask};
+    if (x.layout == EXPORT_WITNESS_MAJOR || x.n_sel < EXPORT_WAVES) {
+        for_grid_y_chunks(x.n_sel, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_list_direct_kernel, dim3((x.n + 255u) / 256u, m), dim3(256), 0, s, a, src, x.layout, done); });
+        return;
+    }
+    const uint32_t tiles = (x.n_sel + EXPORT_TILE_T - 1u) / EXPORT_TILE_T;
+    for_grid_y_chunks(tiles, [&](uint32_t done, uint32_t m) {
+        hipLaunchKernelGGL(export_list_im_kernel<EXPORT_TILE_T>, dim3((x.n + EXPORT_TILE_I - 1u) / EXPORT_TILE_I, m), dim3(EXPORT_THREADS), 0, s, a, src, done * EXPORT_TILE_T);
+    });
 }
 void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow) {

@@ -125,6 +125,32 @@ bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_
 void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u);
 void launch_export_narrow_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow);
+// ---- acvm_batch_export_device_list: row i of the output is instance list[i] of the batch (ExportDevice::first is 0, n the list's length). The host
+// cannot see the list, so the kernels tell a generic instance from one of the exact path themselves: lane_of[j] is the instance's lane or -1.
+struct ExportListSource {
+    const uint32_t *list;           // device, n absolute instance numbers; an entry >= B reads as an instance that assigned nothing
+    uint32_t B;                     // live instances
+    const int32_t *lane_of;         // device, one word per instance of the handle
+    const uint4 *Wx;                // the exact lanes' values: column `lane` of the side table (side), or the instance's own column of the level table
+    uint64_t Bpx;
+    bool side;
+    const uint32_t *assigned_bits;  // bit w of lane t at assigned_bits[(w >> 5) * n_slow + t]
+    uint32_t n_slow;
+};
+void launch_export_device_list(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                               const uint32_t *u_factor, const ExportListSource &src);
+void launch_export_narrow_list(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                               const ExportListSource &src);
+// ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
+// {status, err, opcode index, index in the range} over them; any column may be null
+void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);
+void launch_outcomes_lanes(hipStream_t s, const uint32_t *records, uint32_t n_lanes, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);
+// lane_of[ids[t]] = t for t < n_slow (the map filled with -1 before: launch_fill_u32)
+void launch_lane_map_scatter(hipStream_t s, int32_t *lane_of, uint32_t n_instances, const uint32_t *ids, uint32_t n_slow);
+// The ordered selection (select_scan.hpp): out[0 .. *count) = first + i for the i < n, ascending, whose status byte has its bit set in select_mask; what lies
+// behind *count is not written. scratch: select_scratch_words(n) words; out may be null (the count alone); count: one device word.
+size_t select_scratch_words(uint32_t n);
+void launch_select(hipStream_t s, const uint8_t *status, uint32_t first, uint32_t n, uint32_t select_mask, uint32_t *scratch, uint32_t *out, uint32_t *count);
 void launch_gather_initial(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *W, uint64_t Bp, const uint32_t *init_ids, const uint32_t *init_rows, uint32_t n_init,
                            const uint32_t *slow_ids, uint32_t n_slow);
 void launch_gather_columns(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *W, uint64_t Bp, uint32_t n_rows, const uint32_t *slow_ids, uint32_t n_slow,

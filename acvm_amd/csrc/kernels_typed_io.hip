@@ -228,9 +228,66 @@ __global__ void __launch_bounds__(256) export_narrow_lanes_kernel(const NarrowEx
     narrow_write(a.out + at * a.size, e.lo, a.size);
     if (a.mask) a.mask[at] = (uint8_t)e.mask;
 }
+// acvm_batch_export_device_list in the narrow encodings (kernels.hip export_list_*_kernel): the instance of output row i comes from the list,
+// and the lane decides how it is read -- no instance, an instance of the exact path, a generic one
+__device__ __forceinline__ ExportNarrow narrow_list_element(const NarrowExportArgs &a, const ExportListSource &L, uint32_t k, uint32_t j, int32_t lane) {
+    if (j >= L.B) return export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
+    if (lane < 0) return narrow_generic_element(a, k, j);
+    const uint32_t w = a.sel ? a.sel[k] : k;
+    const bool assigned = w < a.n_witnesses && ((L.assigned_bits[(uint64_t)(w >> 5) * L.n_slow + (uint32_t)lane] >> (w & 31u)) & 1u) != 0u;
+    if (!assigned) return export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
+    return export_encode_narrow(fr_load(L.Wx, w, L.Bpx, L.side ? (uint64_t)(uint32_t)lane : (uint64_t)j), export_plain_factor(EXPORT_ENC_LE32), a.size, true);
+}
+__global__ void __launch_bounds__(256) export_narrow_list_direct_kernel(const NarrowExportArgs a, const ExportListSource L, uint32_t layout, uint32_t k0) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t k = k0 + blockIdx.y;
+    if (i >= a.n) return;
+    const uint32_t j = L.list[i];
+    const ExportNarrow e = narrow_list_element(a, L, k, j, j < L.B ? L.lane_of[j] : -1);
+    const uint64_t at = export_element_index(layout, a.stride, i, k);
+    narrow_write(a.out + at * a.size, e.lo, a.size);
+    if (a.mask) a.mask[at] = (uint8_t)e.mask;
+}
+// (export_narrow_im_kernel with the source column of each tile lane taken from the list)
+__global__ void __launch_bounds__(256) export_narrow_list_im_kernel(const NarrowExportArgs a, const ExportListSource L, uint32_t T, uint32_t k0) {
+    extern __shared__ uint4 narrow_list_tile[];  // 64 x pitch bytes of elements, then 64 x (T + 4) mask bytes
+    uint8_t *tile = (uint8_t *)narrow_list_tile;
+    const uint32_t size = a.size, pitch = T * size + (size > 4u ? size : 4u), mpitch = T + 4u;
+    uint8_t *tile_mask = tile + 64u * pitch;
+    const uint32_t t = threadIdx.x;
+    const uint64_t i0 = (uint64_t)blockIdx.x * 64u;
+    const uint32_t kb = k0 + blockIdx.y * T;
+    {
+        const uint32_t ji = t & 63u;
+        const uint64_t i = i0 + ji;
+        const uint32_t j = i < a.n ? L.list[i] : 0xFFFFFFFFu;
+        const int32_t lane = j < L.B ? L.lane_of[j] : -1;
+#pragma unroll 1
+        for (uint32_t kk = t >> 6; kk < T; kk += 4u) {
+            const uint32_t k = kb + kk;
+            if (k >= a.n_sel || i >= a.n) continue;
+            const ExportNarrow e = narrow_list_element(a, L, k, j, lane);
+            narrow_write(tile + ji * pitch + kk * size, e.lo, size);
+            tile_mask[ji * mpitch + kk] = (uint8_t)e.mask;
+        }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t g = t; g < 64u * T; g += 256u) {
+        const uint32_t ji = g / T, kk = g % T;
+        const uint64_t i = i0 + ji;
+        const uint32_t k = kb + kk;
+        if (i >= a.n || k >= a.n_sel) continue;
+        const uint64_t at = export_element_index(EXPORT_INSTANCE_MAJOR, a.stride, i, k);
+        narrow_write(a.out + at * size, import_narrow_read(tile + ji * pitch + kk * size, size), size);
+        if (a.mask) a.mask[at] = tile_mask[ji * mpitch + kk];
+    }
+}
 
 // positions per tile of the instance-major kernel: runs of 64 elements up to 4 bytes wide (64 .. 256 bytes), of 16 for the wider ones (128 / 256 bytes)
 static uint32_t narrow_tile_positions(uint32_t size) { return size <= 4u ? 64u : 16u; }
+// LDS of one tile of either instance-major kernel (range or list): 64 runs of T elements at the padded pitch, then 64 x (T + 4) mask bytes
+static uint32_t narrow_tile_lds_bytes(uint32_t T, uint32_t size) { return 64u * (T * size + (size > 4u ? size : 4u)) + 64u * (T + 4u); }
 
 void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u) {
     if (!x.n || !x.n_sel) return;
@@ -241,8 +298,21 @@ void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, 
         return;
     }
     const uint32_t T = narrow_tile_positions(size), tiles = (x.n_sel + T - 1u) / T;
-    const uint32_t lds = 64u * (T * size + (size > 4u ? size : 4u)) + 64u * (T + 4u);  // 8.5 KiB (U8) .. 20.5 KiB (U32)
+    const uint32_t lds = narrow_tile_lds_bytes(T, size);  // 8.5 KiB (U8) .. 20.5 KiB (U32)
     for_grid_y_chunks(tiles, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_narrow_im_kernel, dim3((x.n + 63u) / 64u, m), dim3(256), lds, s, a, T, done * T); });
+}
+void launch_export_narrow_list(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
+                               const ExportListSource &src) {
+    if (!x.n || !x.n_sel) return;
+    const uint32_t size = export_element_size(x.encoding);
+    const NarrowExportArgs a{W, Bp, 0u, x.n, x.sel, x.n_sel, x.n_witnesses, row_of, producer, u.index, u.consts_plain, size, x.stride, (uint8_t *)x.out, x.mask};
+    if (x.layout == EXPORT_WITNESS_MAJOR || x.n_sel < 4u) {
+        for_grid_y_chunks(x.n_sel, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_narrow_list_direct_kernel, dim3((x.n + 255u) / 256u, m), dim3(256), 0, s, a, src, x.layout, done); });
+        return;
+    }
+    const uint32_t T = narrow_tile_positions(size), tiles = (x.n_sel + T - 1u) / T;
+    const uint32_t lds = narrow_tile_lds_bytes(T, size);
+    for_grid_y_chunks(tiles, [&](uint32_t done, uint32_t m) { hipLaunchKernelGGL(export_narrow_list_im_kernel, dim3((x.n + 63u) / 64u, m), dim3(256), lds, s, a, src, T, done * T); });
 }
 void launch_export_narrow_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow) {

@@ -321,3 +321,31 @@ int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, u
         }
     return 0;
 } ABI_CATCH
+
+// The shipped selection kernels through their launcher on a status array of the caller's (kernels_select.hip launch_select). The device's list starts as the
+// caller's out_list, so that what the kernels leave alone comes back as it went in.
+int acvm_debug_select(const uint8_t *status, uint32_t n, uint32_t select_mask, uint32_t *out_list, uint32_t *n_selected) try {
+    if (!n_selected || (n && !status)) return set_err(ACVM_E_INVALID, "null argument");
+    struct Mem {
+        uint8_t *status = nullptr;
+        uint32_t *list = nullptr, *scratch = nullptr;
+        ~Mem() {
+            for (void *p : {(void *)status, (void *)list, (void *)scratch})
+                if (p) hipFree(p);
+        }
+    } m;
+    const size_t words = select_scratch_words(n);
+    HIPCHK(hipMalloc((void **)&m.status, n ? n : 1));
+    HIPCHK(hipMalloc((void **)&m.scratch, (words + 1) * 4));
+    if (n) HIPCHK(hipMemcpy(m.status, status, n, hipMemcpyHostToDevice));
+    if (out_list && n) {
+        HIPCHK(hipMalloc((void **)&m.list, (size_t)n * 4));
+        HIPCHK(hipMemcpy(m.list, out_list, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    launch_select(nullptr, m.status, 0, n, select_mask, m.scratch, m.list, m.scratch + words);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(n_selected, m.scratch + words, 4, hipMemcpyDeviceToHost));
+    if (m.list) HIPCHK(hipMemcpy(out_list, m.list, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
+} ABI_CATCH

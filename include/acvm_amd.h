@@ -255,6 +255,10 @@ int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uin
  * front of the event words), *host_count = the host-mapped counter the same kernels keep. */
 int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
                              uint32_t *event_out, uint32_t *device_count, uint32_t *host_count);
+/* The ordered selection of acvm_batch_outcomes_device (the shipped kernels through their launcher) on a status array of the caller's, host in and host
+ * out: out_list[0 .. *n_selected) = the i < n, ascending, with bit status[i] of select_mask set (a status byte of 32 or more is never selected); what
+ * lies behind *n_selected in out_list ([n] capacity) keeps the caller's bytes. out_list may be NULL: the count alone. */
+int acvm_debug_select(const uint8_t *status, uint32_t n, uint32_t select_mask, uint32_t *out_list, uint32_t *n_selected);
 
 /* Peak of the ALU roofline of the integer-bound kernels: back-to-back Montgomery products (fr29_mul, the product every
  * kernel uses) on every SIMD, waves_per_simd dependent chains of 2 * iters products interleaved per SIMD; the best of three timed
@@ -528,6 +532,47 @@ typedef struct {
     uint64_t stride;
 } acvm_export_desc_t;
 int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned);
+/*
+ * Which instances are usable, where the witnesses already are: the outcome of every instance of [first, first + n) as device columns, and the ascending
+ * list of those whose status is one of select_mask -- what a GPU consumer needs of acvm_batch_results (300 bytes per instance on the host) between
+ * one tile and the next.
+ *   - d_status[i] / d_err[i] / d_opcode_index[i] equal the fields of the same names of acvm_batch_results for instance first + i (a Solved instance:
+ *     0 / ACVM_ERR_NONE / 0). Each column may be NULL. The message text, the aux words and the call stack stay host-only: acvm_batch_results.
+ *   - select_mask: bit s set = instances whose status is s (ACVM_STATUS_*) are selected. d_selected[0 .. *n_selected) receives their ABSOLUTE instance
+ *     numbers in ascending order; it needs room for n entries, and what lies behind *n_selected is not written. d_selected may be NULL with n_selected
+ *     given: the count alone. Both NULL: no selection is made.
+ *   - Answers in every state in which acvm_batch_results answers (after acvm_batch_solve_opcode steps, with the forced slow path, with
+ *     ACVM_BATCH_REUSE_SLOTS, with instances waiting at a foreign call, after acvm_batch_solve_then_import), waits for a pending exact job like it and
+ *     refuses like it. ACVM_E_INVALID: a null descriptor; a descriptor with nothing to write (the four pointers and n_selected all NULL); a range
+ *     beyond the live instances.
+ *   - The call enqueues on the batch's stream and returns after that stream is synchronised. Going up: 16 bytes per instance of the exact path in the
+ *     range. Coming back: the count, four bytes. Nothing proportional to n crosses PCIe.
+ * Not here: a form for acvm_node_solve, an asynchronous variant; acvm_batch_results is unchanged.
+ */
+typedef struct {
+    uint32_t first, n;          /* instances [first, first + n) */
+    uint8_t  *d_status;         /* [n] ACVM_STATUS_*            (may be NULL) */
+    uint8_t  *d_err;            /* [n] ACVM_ERR_*               (may be NULL) */
+    uint32_t *d_opcode_index;   /* [n] acvm_result_t.opcode_index (may be NULL) */
+    uint32_t select_mask;       /* bit s set: instances whose status is s are selected */
+    uint32_t *d_selected;       /* [n] capacity; ascending ABSOLUTE instance numbers (may be NULL) */
+} acvm_outcomes_desc_t;
+int acvm_batch_outcomes_device(acvm_batch_t *b, const acvm_outcomes_desc_t *d, uint32_t *n_selected);
+/*
+ * acvm_batch_export_device for LISTED instances: row i of the output is instance d_instances[i] -- with the list acvm_batch_outcomes_device wrote, the
+ * map of exactly the solved instances, dense, in the consumer's encoding and layout.
+ *   - d is read as by acvm_batch_export_device, except that d->n is the length of the list and d->first must be 0 (else ACVM_E_INVALID).
+ *   - d_instances: DEVICE array of d->n absolute instance numbers, any order, repeats allowed. An entry at or beyond the live instance count is not an
+ *     error (the host never reads the list): its row is that of an instance that assigned nothing -- zero bytes, mask 0 -- and nothing is read for it.
+ *   - Every encoding, both layouts, stride, witness list or whole map, optional mask: as for the range export, with the same checks (n = the list's
+ *     length) and the same refusals.
+ *   - Host-to-device traffic per call: the witness list, and 4 bytes per instance of the exact path when the set of those instances changed since the
+ *     last list export of the handle. Never anything per instance of the batch or per list entry (acvm_debug_export_h2d_bytes: the cumulative bytes
+ *     the three device-outcome entry points -- range export, list export, outcomes -- have copied to the device for this handle).
+ * Not here: a form for acvm_node_solve, an asynchronous variant.
+ */
+int acvm_batch_export_device_list(acvm_batch_t *b, const acvm_export_desc_t *d, const uint32_t *d_instances, void *d_values, uint8_t *d_assigned);
+uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b);
 /*
  * The way in as the mirror image of that way out: ACVM::new's initial WitnessMap (pwg/mod.rs:146-156) read from DEVICE memory of the caller in
  * the encoding and layout its producer writes -- a prover's wire columns (ACVM_ENC_MONT256_LE, ACVM_LAYOUT_WITNESS_MAJOR), or the buffer
