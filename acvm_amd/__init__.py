@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
     "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
     "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
+    "acvm_node_solve_device", "acvm_debug_node_io_bytes",
 ]
 
 
@@ -80,6 +81,14 @@ class ImportPart(C.Structure):
     """acvm_import_part_t"""
     _fields_ = [("d_values", C.c_void_p), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("positions", C.POINTER(C.c_uint32)),
                 ("columns", C.POINTER(C.c_uint32)), ("n", C.c_uint32), ("n_columns", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class NodeLaneIo(C.Structure):
+    """acvm_node_lane_io_t (the d_* fields are device addresses, 0 / None = NULL)"""
+    _fields_ = [("n", C.c_uint64), ("d_values", C.c_void_p), ("in_", ImportDesc), ("d_kept", C.c_void_p), ("d_kept_assigned", C.c_void_p),
+                ("kept_encoding", C.c_uint32), ("kept_layout", C.c_uint32), ("kept_stride", C.c_uint64), ("d_status", C.c_void_p), ("d_err", C.c_void_p),
+                ("d_opcode_index", C.c_void_p), ("d_digests32", C.c_void_p), ("select_mask", C.c_uint32), ("d_selected", C.c_void_p),
+                ("n_selected", C.c_uint64), ("not_solved", C.c_uint64)]
 
 
 def element_size(encoding):
@@ -360,6 +369,10 @@ def lib():
         L.acvm_debug_export_h2d_bytes.restype = C.c_uint64
         L.acvm_debug_export_h2d_bytes.argtypes = [C.c_void_p]
         L.acvm_debug_select.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "acvm_node_solve_device"):
+        L.acvm_node_solve_device.restype = C.c_longlong
+        L.acvm_node_solve_device.argtypes = [C.c_void_p, C.POINTER(NodeLaneIo), C.c_uint32]
+        L.acvm_debug_node_io_bytes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     if hasattr(L, "acvm_debug_table_read"):
         L.acvm_debug_table_info.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.acvm_debug_table_read.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -778,6 +791,37 @@ class Node:
                                    kv.ctypes.data if kv is not None else None, ka.ctypes.data if ka is not None else None, dg.ctypes.data if dg is not None else None)
         _check(rc)
         return rc, res, kv, ka, dg
+
+    def solve_device(self, lanes):
+        """acvm_node_solve_device: one dict per handle of the node with the fields of acvm_node_lane_io_t -- n, d_values, encoding, layout, columns,
+        n_columns, stride (the inputs, as import_device's keywords), d_kept, d_kept_assigned, kept_encoding, kept_layout, kept_stride, d_status,
+        d_err, d_opcode_index, d_digests32, select_mask, d_selected; device addresses, absent / 0 / None = NULL. Returns one
+        (not_solved, n_selected) per lane; last_not_solved holds their total as the call returned it."""
+        arr = (NodeLaneIo * max(len(lanes), 1))()
+        keep = []
+        for q, lane in enumerate(lanes):
+            io = arr[q]
+            io.n, io.d_values = lane.get("n", 0), lane.get("d_values") or None
+            io.in_.encoding, io.in_.layout, io.in_.stride = lane.get("encoding", ENC_BE32), lane.get("layout", LAYOUT_INSTANCE_MAJOR), lane.get("stride", 0)
+            if lane.get("columns") is not None:
+                cols = list(lane["columns"])
+                if len(cols) != len(self.ids):
+                    raise ValueError("columns needs one entry per initial witness")
+                c_arr = (C.c_uint32 * max(len(cols), 1))(*cols)
+                keep.append(c_arr)
+                io.in_.columns, io.in_.n_columns = c_arr, lane["n_columns"] if lane.get("n_columns") is not None else len(cols)
+            io.kept_encoding, io.kept_layout, io.kept_stride = lane.get("kept_encoding", ENC_BE32), lane.get("kept_layout", LAYOUT_INSTANCE_MAJOR), lane.get("kept_stride", 0)
+            for f in ("d_kept", "d_kept_assigned", "d_status", "d_err", "d_opcode_index", "d_digests32", "d_selected"):
+                setattr(io, f, lane.get(f) or None)
+            io.select_mask = lane.get("select_mask", 0)
+        self.last_not_solved = _check(lib().acvm_node_solve_device(self._h, arr, len(lanes)))  # (the call's own return value: the total)
+        return [(arr[q].not_solved, arr[q].n_selected) for q in range(len(lanes))]
+
+    def io_bytes(self, lane: int):
+        """(host-to-device, device-to-host) bytes the device form has copied for this lane so far (acvm_debug_node_io_bytes)"""
+        h2d, d2h = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().acvm_debug_node_io_bytes(self._h, lane, C.byref(h2d), C.byref(d2h)))
+        return h2d.value, d2h.value
 
     def stats(self):
         st = NodeStats()

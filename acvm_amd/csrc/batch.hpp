@@ -40,6 +40,23 @@ struct ExactOutcome {
     void clear() { instance.clear(); results.clear(); kept_values.clear(); kept_assigned.clear(); digests.clear(); }
 };
 
+// Where the outcomes of instances [0, n) of ONE solve go when the caller's buffers are on the handle's device (node.cpp, the device form): the view
+// of one tile of a lane (node_io_plan.hpp NodeTileIo), every pointer a device address or null. The instances the level kernels solved are
+// written by batch_enqueue_tile_outcomes behind the solve; those of a pending exact job when its outcome is collected (batch_set_exact_sink).
+struct TileSink {
+    uint32_t n = 0;                                 // live instances of the tile
+    uint32_t encoding = 0, layout = 0;              // of d_kept: ACVM_ENC_*, ACVM_LAYOUT_*
+    const uint32_t *d_keep = nullptr;               // the kept witnesses, a device list (0xFFFFFFFF: no such witness)
+    uint32_t n_keep = 0;
+    uint64_t stride = 0;                            // in elements, as launched
+    void *d_kept = nullptr;                         // null: no kept witnesses are written
+    uint8_t *d_kept_assigned = nullptr;
+    uint8_t *d_status = nullptr, *d_err = nullptr;
+    uint32_t *d_opcode_index = nullptr;
+    uint8_t *d_digests = nullptr;                   // [n][32]
+    uint64_t *h2d = nullptr;                        // where the bytes copied to the device for this are counted (may be null)
+};
+
 // One plan per (initial witness ids, options, tuning) of a circuit: planning a 10^6-opcode circuit takes seconds and its plan hundreds of MB,
 // and the reference's callers build their opcode list once per circuit for any number of executions (acvm_js/src/execute.rs:60-119).
 struct PlanKey {
@@ -167,6 +184,15 @@ struct acvm_batch {
     int32_t *d_lane_map = nullptr;
     uint64_t slow_epoch = 0, lane_map_epoch = 0;
     uint64_t n_export_h2d_bytes = 0;  // (acvm_debug_export_h2d_bytes)
+    // The tile sinks of the node's device form (batch_export.cpp). Two small grow-only arenas for the lists of the exact lanes -- [0] read on
+    // the handle's stream behind a solve, [1] on the exact job's stream when its outcome is collected, beside the NEXT solve: they must not
+    // share the staging arena -- and the host lists [0] is copied from, which live until the next solve has waited for the stream.
+    uint8_t *d_sink[2] = {nullptr, nullptr};
+    size_t sink_cap[2] = {0, 0};
+    std::vector<uint32_t> sink_lanes, sink_records;
+    hipEvent_t ev_sink = nullptr;     // behind what batch_enqueue_tile_outcomes enqueued: the exact job's rows go over the leftovers it wrote there
+    bool exact_sink_set = false;      // the pending job's outcome goes to exact_sink (cleared when it is collected)
+    TileSink exact_sink;
     std::vector<uint32_t> init_rows, plane_of_input;  // host copies of d_init_rows (slot reuse) and d_byte_plane_of_input (byte planes): what a plan of parts picks from
     hipEvent_t ev_counted = nullptr;  // behind the event count of a solve: what the host waits for instead of the whole stream
     bool holds_tables = false;  // a reference on the device's lookup-table set (grumpkin_host.hpp device_tables_retain)
@@ -243,6 +269,9 @@ struct acvm_batch {
         if (d_fetch) hipFree(d_fetch);
         if (d_import_lists) hipFree(d_import_lists);
         if (d_lane_map) hipFree(d_lane_map);
+        for (uint8_t *q : d_sink)
+            if (q) hipFree(q);
+        if (ev_sink) hipEventDestroy(ev_sink);
         if (stream_x) { hipStreamSynchronize(stream_x); hipStreamDestroy(stream_x); }
         if (ev_x_ready) hipEventDestroy(ev_x_ready);
         for (int k = 0; k < (int)N_CLS; k++)
@@ -297,6 +326,17 @@ int batch_export_tile(acvm_batch *b, uint32_t n, const uint32_t *keep, uint32_t 
 // the solve, in front of the next import), the copy into h_out on `copy_stream` behind it; `arrived` is recorded behind the copy.
 int batch_enqueue_kept(acvm_batch *b, uint32_t n, const uint32_t *d_keep, uint32_t n_keep, uint8_t *d_out, uint8_t *h_out, hipStream_t copy_stream,
                        hipEvent_t exported, hipEvent_t arrived);
+// ---- the device form of the node driver: a tile's inputs and outcomes without a wait and without a value on the host
+// acvm_batch_import_device without the wait: the descriptor is checked against the handle (its live count) and the import enqueued
+int batch_import_desc_async(acvm_batch *b, const acvm_import_desc_t *d, const void *d_values);
+// Kept witnesses, outcome columns and digests of instances [0, sink->n) of the last solve into the sink, enqueued on the handle's stream and not
+// waited for. While an exact job is pending its instances are written as the level kernels left them (Solved, leftovers) and come with the
+// job's outcome; the lanes of a synchronous exact path are final and written here.
+int batch_enqueue_tile_outcomes(acvm_batch *b, const TileSink *sink);
+// The pending exact job's outcome goes into *sink (copied) on the device when it is collected -- by the next acvm_batch_solve or by
+// batch_finish_pending, whose ExactOutcome then carries the instances and the heads of their results only. No-op without a pending job.
+void batch_set_exact_sink(acvm_batch *b, const TileSink *sink);
+int batch_stream_synchronize(acvm_batch *b);
 // device bytes a handle of `instances` instances of this plan allocates (tables, class scratch, inverse rows, the first side table)
 size_t batch_device_bytes(const acvm::Plan &p, const acvm::PlanOpts &opts, uint64_t instances, bool async_exact);
 }  // extern "C"

@@ -702,12 +702,14 @@ int batch_finish_pending(acvm_batch *b, ExactOutcome *out) {
     HIPCHK(hipMemcpyAsync(b->slow_res.data(), b->d_slow_res, (size_t)n_slow * sizeof(SlowResult), hipMemcpyDeviceToHost, b->stream_x));
     HIPCHK(hipStreamSynchronize(b->stream_x));
     int rc = retry_device_limits(b, n_slow, true, 0xFFFFFFFFu);
-    if (!rc && out) {
+    if (!rc && b->exact_sink_set) rc = side_table_to_sink(b, out);  // (the device form of the node driver: nothing of the lanes visits the host)
+    else if (!rc && out) {
         rc = side_table_outcome(b, out);
         for (uint32_t t = 0; t < n_slow && !rc; t++)  // message texts
             if (b->slow_res[t].status == ACVM_STATUS_FAILURE && b->slow_res[t].msg) format_message(b, b->slow_ids[t], b->slow_res[t], out->results[t]);
     }
     b->pending = false;
+    b->exact_sink_set = false;
     return rc;
 }
 

@@ -366,18 +366,33 @@ static int export_device_checks(acvm_batch *b, const acvm_export_desc_t *d, cons
     return 0;
 }
 
+// The launches of a range export without the wait (as batch_enqueue_kept stands to read_witnesses): every lane of the range as a generic
+// instance (scaled columns, the planner's assigned set), then the exact lanes -- d_lanes: n_lanes device pairs (lane, index in the range) --
+// from where they live (their own columns of the level table, or the side table), scattered into their elements.
+static int enqueue_export_device(acvm_batch *b, hipStream_t s, const ExportDevice &x, const uint32_t *d_lanes, uint32_t n_lanes) {
+    const bool narrow = export_enc_is_narrow(x.encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
+    if (x.encoding == EXPORT_ENC_MONT256_LE)
+        if (int rc = ensure_mont256_table(b)) return rc;
+    if (n_lanes < x.n) {
+        if (narrow) launch_export_narrow(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale);
+        else launch_export_device(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, x.encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain);
+    }
+    if (n_lanes)
+        (narrow ? launch_export_narrow_lanes : launch_export_device_lanes)(s, x, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), d_lanes, n_lanes, b->d_assigned,
+                                                                           (uint32_t)b->slow_ids.size());
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void *d_values, uint8_t *d_assigned) try {
     uint32_t n_sel = 0;
     uint64_t stride = 0;
     if (int rc = export_device_checks(b, d, d_values, nullptr, false, &n_sel, &stride)) return rc;
-    const bool narrow = export_enc_is_narrow(d->encoding);  // elements of 1 .. 16 bytes, aligned to their size; mask bytes 0 / 1 / 2
     const uint32_t first = d->first, n = d->n;
     const uint32_t nw = b->plan().n_witnesses;
     const bool whole = d->witnesses == nullptr;
     if (!n || !n_sel) return 0;
     HIPCHK(hipSetDevice(b->device));
-    if (d->encoding == EXPORT_ENC_MONT256_LE)
-        if (int rc = ensure_mont256_table(b)) return rc;
     // the instances of the exact path among the range: (lane, index in the range) pairs for the second launch
     std::vector<uint32_t> lanes;
     for (uint32_t i = 0; i < n; i++)
@@ -392,16 +407,7 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
     if (n_lanes) HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
     b->n_export_h2d_bytes += (whole ? 0 : (uint64_t)n_sel * 4) + (uint64_t)lanes.size() * 4;
     const ExportDevice x{d->encoding, d->layout, first, n, d_sel, n_sel, nw, stride, d_values, d_assigned};
-    // every lane as a generic instance (scaled columns, the planner's assigned set) ...
-    if (n_lanes < n) {
-        if (narrow) launch_export_narrow(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale);
-        else launch_export_device(s, x, b->d_W, b->Bp, b->d_slot_of, b->d_producer, b->unscale, d->encoding == EXPORT_ENC_MONT256_LE ? b->d_unscale_m256 : b->unscale.consts_plain);
-    }
-    // ... then the exact lanes from where they live (their own columns of the level table, or the side table), scattered into their elements
-    if (n_lanes)
-        (narrow ? launch_export_narrow_lanes : launch_export_device_lanes)(s, x, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), d_lanes, n_lanes, b->d_assigned,
-                                                                           (uint32_t)b->slow_ids.size());
-    HIPCHK(hipGetLastError());
+    if (int rc = enqueue_export_device(b, s, x, d_lanes, n_lanes)) return rc;
     HIPCHK(hipStreamSynchronize(s));  // (also what keeps `lanes` and the caller's list alive for their copies)
     return 0;
 } ABI_CATCH
@@ -460,6 +466,152 @@ uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b) { return b ? b->n_ex
 // ---- per-instance outcomes where the witnesses are (include/acvm_amd.h acvm_batch_outcomes_device). The host's slow_res is the authority (Brillig retries
 // and host callbacks finalise lanes there): every instance of the range is written as a generic one -- Solved -- and the records of the exact lanes of
 // the range go over them, one small list like the range export's `lanes`. The selection runs on the status column (a scratch one when the caller wants none).
+// the two launches of the columns without the wait: n instances Solved, then n_lanes records (device) over them
+static void enqueue_outcomes(hipStream_t s, uint32_t n, const uint32_t *d_records, uint32_t n_lanes, uint8_t *d_status, uint8_t *d_err, uint32_t *d_opcode_index) {
+    launch_outcomes_fill(s, n, d_status, d_err, d_opcode_index);
+    launch_outcomes_lanes(s, d_records, n_lanes, n, d_status, d_err, d_opcode_index);
+}
+
+// ---- the tile sinks of the node's device form (batch.hpp TileSink)
+static int sink_reserve(acvm_batch *b, int which, size_t bytes) {
+    if (bytes <= b->sink_cap[which]) return 0;
+    if (b->d_sink[which]) { hipFree(b->d_sink[which]); b->d_sink[which] = nullptr; b->sink_cap[which] = 0; }
+    const size_t cap = std::max<size_t>(bytes + bytes / 4, (size_t)64 << 10);
+    HIPCHK(hipMalloc((void **)&b->d_sink[which], cap));
+    b->sink_cap[which] = cap;
+    return 0;
+}
+// digests of ALL lanes of the side table (lane t = the t-th flagged instance) into the rows of the pairs' instances: out[i] for the pairs (t, i).
+// d_part / d_rows: digest_chunks x n_slow x 32 and n_slow x 32 bytes of scratch the caller reserved
+static void enqueue_side_digests(acvm_batch *b, hipStream_t s, const uint32_t *d_lanes, uint32_t n_lanes, uint32_t n, uint4 *d_part, uint8_t *d_rows, uint8_t *out) {
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size();
+    const TableView t = side_table(b);
+    launch_digest(s, t.W, t.Bp, 0, n_slow, b->plan().n_witnesses, b->d_producer, t.u, b->fp, (const int32_t *)b->d_ids_x, b->d_assigned, n_slow, d_part, d_rows);
+    launch_scatter_rows32(s, (const uint32_t *)d_rows, d_lanes, n_lanes, n, out);
+}
+static size_t side_digest_bytes(const acvm_batch *b, uint32_t n_slow) { return align256((size_t)digest_chunks(b->plan().n_witnesses) * n_slow * 32) + align256((size_t)n_slow * 32); }
+
+int batch_enqueue_tile_outcomes(acvm_batch *b, const TileSink *k) try {
+    if (!b || !k) return set_err(ACVM_E_INVALID, "null argument");
+    if (!b->solved || k->n != b->B) return set_err(ACVM_E_STATE, "batch not solved");
+    HIPCHK(hipSetDevice(b->device));
+    const Plan &p = b->plan();
+    hipStream_t s = b->stream;
+    const uint32_t n = k->n, n_slow = (uint32_t)b->slow_ids.size();
+    const bool defer = b->pending;  // the instances of the exact path arrive with the job's outcome (side_table_to_sink)
+    // the lanes of a synchronous exact path are final: their (lane, instance) pairs and their records {status, err, opcode index, instance}
+    std::vector<uint32_t> &lanes = b->sink_lanes, &records = b->sink_records;
+    lanes.clear();
+    records.clear();
+    if (!defer)
+        for (uint32_t t = 0; t < n_slow; t++) {
+            const uint32_t j = b->slow_ids[t];
+            if (j >= n) continue;
+            lanes.insert(lanes.end(), {t, j});
+            if (p.n_opcodes != 0 && t < b->slow_res.size()) records.insert(records.end(), {b->slow_res[t].status, b->slow_res[t].err, b->slow_res[t].opcode_index, j});
+        }
+    const uint32_t n_lanes = (uint32_t)(lanes.size() / 2);
+    const bool side_digests = k->d_digests && n_lanes && b->side(), map_digests = k->d_digests && n_lanes && !b->side();
+    const bool map_stale = map_digests && !(b->d_lane_map && b->lane_map_epoch == b->slow_epoch);
+    const size_t lanes_bytes = align256(lanes.size() * 4), rec_bytes = align256(records.size() * 4), ids_bytes = map_stale ? align256((size_t)n_slow * 4) : 0;
+    if (int rc = sink_reserve(b, 0, lanes_bytes + rec_bytes + ids_bytes + (side_digests ? side_digest_bytes(b, n_slow) : 0))) return rc;
+    uint32_t *d_lanes = (uint32_t *)b->d_sink[0], *d_records = (uint32_t *)(b->d_sink[0] + lanes_bytes), *d_ids = (uint32_t *)(b->d_sink[0] + lanes_bytes + rec_bytes);
+    uint8_t *d_digest_scratch = b->d_sink[0] + lanes_bytes + rec_bytes + ids_bytes;
+    // (the host lists are the handle's: they live until the next solve has waited for this stream)
+    if (n_lanes) HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
+    if (!records.empty()) HIPCHK(hipMemcpyAsync(d_records, records.data(), records.size() * 4, hipMemcpyHostToDevice, s));
+    if (k->h2d) *k->h2d += (uint64_t)(lanes.size() + records.size()) * 4;
+    if (k->d_kept && k->n_keep) {
+        const ExportDevice x{k->encoding, k->layout, 0u, n, k->d_keep, k->n_keep, p.n_witnesses, k->stride, k->d_kept, k->d_kept_assigned};
+        if (int rc = enqueue_export_device(b, s, x, d_lanes, n_lanes)) return rc;
+    }
+    enqueue_outcomes(s, n, d_records, (uint32_t)(records.size() / 4), k->d_status, k->d_err, k->d_opcode_index);
+    if (k->d_digests) {
+        if (int rc = ensure_digest_tables(b)) return rc;
+        const bool folded = p.n_digest_segments && b->d_leaves;
+        // every lane read as a generic instance (batch_export_tile's rule: an event word that is set would send the kernel to the assigned
+        // bitmap of a job that is still running; the exact lanes' rows are leftovers and are overwritten)
+        auto generic = [&]() -> int {
+            const size_t part_bytes = align256((size_t)digest_chunks(p.n_witnesses) * n * 32);
+            if (int rc = stage_reserve(b, part_bytes)) return rc;
+            TableView t = level_table(b);
+            t.u.event = nullptr;
+            launch_digest(s, t.W, t.Bp, 0, n, p.n_witnesses, b->d_producer, t.u, b->fp, nullptr, b->d_assigned, 0, (uint4 *)b->d_stage, k->d_digests);
+            return 0;
+        };
+        if (map_digests) {
+            // a plain table with final exact lanes: the table-wide kernel serves generic and exact lanes alike (acvm_batch_digest) through the
+            // instance -> lane map, which is made on the device
+            const size_t part_bytes = align256((size_t)digest_chunks(p.n_witnesses) * n * 32);
+            if (int rc = stage_reserve(b, part_bytes)) return rc;
+            const uint64_t before = b->n_export_h2d_bytes;
+            if (int rc = lane_map_ready(b, s, d_ids)) return rc;
+            if (k->h2d) *k->h2d += b->n_export_h2d_bytes - before;
+            const TableView t = level_table(b);
+            launch_digest(s, t.W, t.Bp, 0, n, p.n_witnesses, b->d_producer, t.u, b->fp, b->d_lane_map, b->d_assigned, n_slow, (uint4 *)b->d_stage, k->d_digests);
+        } else {
+            if (folded && (defer || !n_lanes || (!b->force_slow && !b->stepping))) launch_digest_final(s, b->d_leaves, p.n_digest_segments, b->Bp, 0, n, side_digests ? b->d_event : nullptr, b->fp, k->d_digests);
+            else if (int rc = generic()) return rc;
+            if (side_digests) enqueue_side_digests(b, s, d_lanes, n_lanes, n, (uint4 *)d_digest_scratch, d_digest_scratch + align256((size_t)digest_chunks(p.n_witnesses) * n_slow * 32), k->d_digests);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    if (!b->ev_sink) HIPCHK(hipEventCreateWithFlags(&b->ev_sink, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(b->ev_sink, s));
+    return 0;
+} ABI_CATCH
+
+void batch_set_exact_sink(acvm_batch *b, const TileSink *sink) {
+    if (!b->pending) return;
+    b->exact_sink = *sink;
+    b->exact_sink_set = true;
+}
+int batch_stream_synchronize(acvm_batch *b) {
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    return 0;
+}
+
+int side_table_to_sink(acvm_batch *b, ExactOutcome *out) {
+    const TileSink &k = b->exact_sink;
+    hipStream_t s = b->xstream();
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size();
+    if (out) {
+        out->instance = b->slow_ids;
+        out->results.resize(n_slow);
+        for (uint32_t t = 0; t < n_slow; t++) result_head(b->slow_res[t], out->results[t]);
+    }
+    std::vector<uint32_t> lanes, records;
+    for (uint32_t t = 0; t < n_slow; t++) {
+        const uint32_t j = b->slow_ids[t];
+        if (j >= k.n) continue;
+        lanes.insert(lanes.end(), {t, j});
+        records.insert(records.end(), {b->slow_res[t].status, b->slow_res[t].err, b->slow_res[t].opcode_index, j});
+    }
+    const uint32_t n_lanes = (uint32_t)(lanes.size() / 2);
+    if (!n_lanes) return 0;
+    const size_t lanes_bytes = align256(lanes.size() * 4), rec_bytes = align256(records.size() * 4);
+    if (int rc = sink_reserve(b, 1, lanes_bytes + rec_bytes + (k.d_digests ? side_digest_bytes(b, n_slow) : 0))) return rc;
+    uint32_t *d_lanes = (uint32_t *)b->d_sink[1], *d_records = (uint32_t *)(b->d_sink[1] + lanes_bytes);
+    uint8_t *d_digest_scratch = b->d_sink[1] + lanes_bytes + rec_bytes;
+    if (k.d_digests)
+        if (int rc = ensure_digest_tables(b)) return rc;
+    // the level kernels' leftovers for these rows were written on the handle's stream: these writes go over them
+    if (b->ev_sink) HIPCHK(hipStreamWaitEvent(s, b->ev_sink, 0));
+    HIPCHK(hipMemcpyAsync(d_lanes, lanes.data(), lanes.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_records, records.data(), records.size() * 4, hipMemcpyHostToDevice, s));
+    if (k.h2d) *k.h2d += (uint64_t)(lanes.size() + records.size()) * 4;
+    if (k.d_kept && k.n_keep) {  // from the side table while it still holds them: the next job's gather overwrites it
+        const ExportDevice x{k.encoding, k.layout, 0u, k.n, k.d_keep, k.n_keep, b->plan().n_witnesses, k.stride, k.d_kept, k.d_kept_assigned};
+        (export_enc_is_narrow(k.encoding) ? launch_export_narrow_lanes : launch_export_device_lanes)(s, x, b->d_Wx, b->x_cap, true, d_lanes, n_lanes, b->d_assigned, n_slow);
+    }
+    launch_outcomes_lanes(s, d_records, n_lanes, k.n, k.d_status, k.d_err, k.d_opcode_index);
+    if (k.d_digests) enqueue_side_digests(b, s, d_lanes, n_lanes, k.n, (uint4 *)d_digest_scratch, d_digest_scratch + align256((size_t)digest_chunks(b->plan().n_witnesses) * n_slow * 32), k.d_digests);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps the two lists alive for their copies)
+    return 0;
+}
+
 int acvm_batch_outcomes_device(acvm_batch_t *b, const acvm_outcomes_desc_t *d, uint32_t *n_selected) try {
     if (!d) return set_err(ACVM_E_INVALID, "null argument");
     if (!d->d_status && !d->d_err && !d->d_opcode_index && !d->d_selected && !n_selected)
@@ -494,8 +646,7 @@ int acvm_batch_outcomes_device(acvm_batch_t *b, const acvm_outcomes_desc_t *d, u
         HIPCHK(hipMemcpyAsync(d_records, records.data(), records.size() * 4, hipMemcpyHostToDevice, s));
         b->n_export_h2d_bytes += (uint64_t)records.size() * 4;
     }
-    launch_outcomes_fill(s, n, d_status, d->d_err, d->d_opcode_index);
-    launch_outcomes_lanes(s, d_records, n_lanes, n, d_status, d->d_err, d->d_opcode_index);
+    enqueue_outcomes(s, n, d_records, n_lanes, d_status, d->d_err, d->d_opcode_index);
     uint32_t count = 0;
     if (select) {
         launch_select(s, d_status, first, n, d->select_mask, d_scan, d->d_selected, d_count);

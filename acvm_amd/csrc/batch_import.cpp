@@ -96,6 +96,11 @@ int batch_import_plan_async(acvm_batch *b, const ImportPlan &plan, hipEvent_t im
 int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported) {
     return batch_import_plan_async(b, import_plan_plain((uint32_t)b->plan().initial_ids.size(), d_values_be32), imported, nullptr);
 }
+int batch_import_desc_async(acvm_batch *b, const acvm_import_desc_t *d, const void *d_values) {
+    ImportPlan plan;
+    if (int rc = import_plan_of(b, d, d_values, &plan)) return rc;
+    return batch_import_plan_async(b, plan, nullptr, nullptr);
+}
 // the import and the wait of the public entry points: the caller may reuse its buffers as soon as the call returns (an import that ran behind
 // the previous solve left the buffer alone since: nothing to wait for)
 static int import_and_wait(acvm_batch *b, const ImportPlan &plan) {

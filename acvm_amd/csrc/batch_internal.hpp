@@ -92,6 +92,9 @@ bool fetch_one(acvm_batch *b, uint32_t j, uint32_t w, uint8_t out[32]);
 // the assigned set of the last solve (assigned_view.hpp) over the handle's bookkeeping; rows of the exact lanes' bitmap are copied when asked
 // for (the blocking copy: not while an exact job is pending), a failing copy leaves its error in *err (if given) and the row unassigned
 AssignedView batch_assigned(const acvm_batch *b, hipError_t *err = nullptr);
+// the outcome of the pending exact job into b->exact_sink, on the job's stream and waited for (the side table is the next job's afterwards);
+// *out (may be null): the instances and the heads of their results
+int side_table_to_sink(acvm_batch *b, ExactOutcome *out);
 
 // ---- batch_messages.cpp
 // status, error, opcode index, aux words and call stack of an exact lane's outcome (r zeroed first); the message text is format_message's

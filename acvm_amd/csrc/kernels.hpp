@@ -147,6 +147,9 @@ void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *e
 void launch_outcomes_lanes(hipStream_t s, const uint32_t *records, uint32_t n_lanes, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);
 // lane_of[ids[t]] = t for t < n_slow (the map filled with -1 before: launch_fill_u32)
 void launch_lane_map_scatter(hipStream_t s, int32_t *lane_of, uint32_t n_instances, const uint32_t *ids, uint32_t n_slow);
+// rows of 32 bytes to where their instances are: out[i] = rows[t] for the n_lanes pairs (t, i) of `lanes` with i < n -- the digests of the side
+// table's lanes into a column of the caller (any alignment)
+void launch_scatter_rows32(hipStream_t s, const uint32_t *rows, const uint32_t *lanes, uint32_t n_lanes, uint32_t n, uint8_t *out);
 // The ordered selection (select_scan.hpp): out[0 .. *count) = first + i for the i < n, ascending, whose status byte has its bit set in select_mask; what lies
 // behind *count is not written. scratch: select_scratch_words(n) words; out may be null (the count alone); count: one device word.
 size_t select_scratch_words(uint32_t n);

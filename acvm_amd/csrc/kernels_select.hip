@@ -32,6 +32,18 @@ __global__ void __launch_bounds__(256) lane_map_scatter_kernel(int32_t *__restri
     const uint32_t j = ids[t];
     if (j < n_instances) lane_of[j] = (int32_t)t;
 }
+// out[i] = rows[t] for the pairs (t, i) of the exact lanes: one thread per 4-byte word of a 32-byte row, stored as bytes (the column is the
+// caller's and has no alignment of its own); few lanes by construction
+__global__ void __launch_bounds__(256) scatter_rows32_kernel(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ lanes, uint32_t n_lanes, uint32_t n,
+                                                             uint8_t *__restrict__ out) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t x = g >> 3, w = g & 7u;
+    if (x >= n_lanes) return;
+    const uint32_t t = lanes[2 * x], i = lanes[2 * x + 1];
+    if (i >= n) return;
+    const uint32_t v = rows[(uint64_t)t * 8 + w];
+    for (uint32_t k = 0; k < 4; k++) out[(uint64_t)i * 32 + 4 * w + k] = (uint8_t)(v >> (8 * k));
+}
 
 // ---- the selection
 // the ballots of a block: p[r] / rank[r] of this thread in round r, counts[] (LDS) the population of every slot
@@ -100,6 +112,10 @@ void launch_outcomes_lanes(hipStream_t s, const uint32_t *records, uint32_t n_la
 void launch_lane_map_scatter(hipStream_t s, int32_t *lane_of, uint32_t n_instances, const uint32_t *ids, uint32_t n_slow) {
     if (!n_slow) return;
     hipLaunchKernelGGL(lane_map_scatter_kernel, dim3((n_slow + 255u) / 256u), dim3(256), 0, s, lane_of, n_instances, ids, n_slow);
+}
+void launch_scatter_rows32(hipStream_t s, const uint32_t *rows, const uint32_t *lanes, uint32_t n_lanes, uint32_t n, uint8_t *out) {
+    if (!n_lanes) return;
+    hipLaunchKernelGGL(scatter_rows32_kernel, dim3((unsigned)(((uint64_t)n_lanes * 8 + 255u) / 256u)), dim3(256), 0, s, rows, lanes, n_lanes, n, out);
 }
 size_t select_scratch_words(uint32_t n) { return (size_t)select_blocks(n) + 1u; }
 void launch_select(hipStream_t s, const uint8_t *status, uint32_t first, uint32_t n, uint32_t select_mask, uint32_t *scratch, uint32_t *out, uint32_t *count) {

@@ -9,8 +9,12 @@
 //     level schedule of the NEXT tile (batch.cpp, asynchronous exact path): a few diverging inputs per tile do not stall the tile;
 //   * per instance the caller gets the result record, the kept witnesses (normally the circuit's return values) and the 32-byte
 //     digest of the whole witness map, in global instance order.
+// acvm_node_solve_device is the same driver for callers whose data lives on the GPUs: per lane the inputs are read from, and kept witnesses,
+// outcome columns, digests and the selection written into, device memory of that lane (run_lane_device_body; checks and tile views:
+// node_io_plan.cpp). No staging, no producer thread; the exact path still runs beside the next tile and writes its rows on the device.
 #include "batch.hpp"
 #include "circuit.hpp"
+#include "node_io_plan.hpp"
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -43,6 +47,7 @@ struct DeviceLane {
     double device_ms = 0, h2d_wait_ms = 0, export_ms = 0, total_ms = 0;
     uint32_t tiles = 0, exact_instances = 0;
     uint64_t not_solved = 0;
+    uint64_t io_h2d = 0, io_d2h = 0;  // bytes the device form copied for this lane, cumulative (acvm_debug_node_io_bytes)
     std::string error;
     int rc = 0;
     // host placement: the CPUs local to the device (sysfs), empty = unknown / not pinned
@@ -380,6 +385,132 @@ void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last
     L.total_ms = now_ms() - t_begin;
 }
 
+// The lane body of the device form (acvm_node_solve_device): the lane's rows are where the caller's producer left them and its outcomes stay
+// where the caller's consumer reads them, so there is no producer thread, no pinned staging and nothing to harvest. Per tile: live count,
+// import of the tile's view (node_io_plan.cpp: the address rule), solve, then kept witnesses, outcome columns and digests of the instances the
+// level kernels solved are ENQUEUED into the caller's buffers -- nothing in the loop waits for the pending exact job, which runs beside the
+// next tile as in run_lane_body; its rows are written on the device when its outcome is collected (batch_set_exact_sink).
+void run_lane_device_body(acvm_node *node, DeviceLane &L, const NodeLaneIo &lane, acvm_node_lane_io_t *io) {
+    const double t_begin = now_ms();
+    L.rc = 0;
+    L.error.clear();
+    L.device_ms = L.h2d_wait_ms = L.export_ms = 0;
+    L.tiles = L.exact_instances = 0;
+    L.not_solved = 0;
+    io->n_selected = io->not_solved = 0;
+    auto fail = [&](int rc, const std::string &what) { if (!L.rc) { L.rc = rc; L.error = what + ": " + acvm_last_error(); } };
+    auto fail_hip = [&](const char *what, hipError_t e) { if (!L.rc) { L.rc = ACVM_E_DEVICE; L.error = std::string(what) + ": " + hipGetErrorString(e); } };
+    L.total_ms = 0;
+    if (!lane.n_tiles) return;
+    if (hipError_t e = hipSetDevice(L.device); e != hipSuccess) { fail_hip("hipSetDevice", e); return; }
+    const NodeIoShape shape{(uint32_t)node->ids.size(), (uint32_t)node->keep.size(), node->tile};
+    const uint32_t n = (uint32_t)lane.io.n;
+    // the selection runs over the lane's status column: a scratch one when the caller wants none
+    NodeLaneIo view = lane;
+    uint8_t *d_scratch_status = nullptr;
+    uint32_t *d_scan = nullptr;
+    const size_t scan_words = select_scratch_words(n) + 1;  // (the count behind the scan's scratch)
+    if (!view.io.d_status) {
+        if (hipError_t e = hipMalloc((void **)&d_scratch_status, n); e != hipSuccess) { fail_hip("hipMalloc (status column)", e); return; }
+        view.io.d_status = d_scratch_status;
+    }
+    if (hipError_t e = hipMalloc((void **)&d_scan, scan_words * 4); e != hipSuccess) { fail_hip("hipMalloc (selection)", e); hipFree(d_scratch_status); return; }
+    const uint64_t list_copies = acvm_debug_import_list_copies(L.batch);
+    auto sink_of = [&](const NodeTileIo &t) {
+        TileSink k;
+        k.n = t.m;
+        k.encoding = view.io.kept_encoding;
+        k.layout = view.io.kept_layout;
+        k.d_keep = L.d_keep;
+        k.n_keep = shape.n_keep;
+        k.stride = t.kept_stride;
+        k.d_kept = t.d_kept;
+        k.d_kept_assigned = t.d_kept_assigned;
+        k.d_status = t.d_status;
+        k.d_err = t.d_err;
+        k.d_opcode_index = t.d_opcode_index;
+        k.d_digests = t.d_digests32;
+        k.h2d = &L.io_h2d;
+        return k;
+    };
+    auto count_outcome = [&](const ExactOutcome &o, uint32_t n_valid) {
+        for (size_t t = 0; t < o.instance.size(); t++) L.not_solved += o.instance[t] < n_valid && o.results[t].status != ACVM_STATUS_SOLVED;
+    };
+    try {
+    uint32_t prev_valid = 0;
+    for (uint32_t k = 0; k < lane.n_tiles && !L.rc; k++) {
+        NodeTileIo t;
+        std::string text;
+        if (int rc = node_io_tile(shape, view, k, &t, &text)) { L.rc = rc; L.error = text; break; }
+        if (int rc = batch_set_live_count(L.batch, t.m)) { fail(rc, "live count"); break; }
+        if (int rc = batch_import_desc_async(L.batch, &t.in, t.d_values)) { fail(rc, "import"); break; }
+        const int rc = acvm_batch_solve(L.batch);  // asynchronous handles: collects the exact job of tile k - 1 on the way, into that tile's sink
+        if (rc < 0) { fail(rc, "solve"); break; }
+        acvm_stats_t st;
+        acvm_batch_stats(L.batch, &st);
+        L.device_ms += st.solve_device_ms;
+        L.exact_instances += st.n_slow_instances;
+        L.tiles++;
+        const double t1 = now_ms();
+        if (k > 0) {
+            ExactOutcome o;
+            batch_take_outcome(L.batch, &o);
+            count_outcome(o, prev_valid);
+        }
+        L.not_solved += batch_exact_unsolved(L.batch, t.m);  // (a synchronous exact path: its lanes are final)
+        const TileSink sink = sink_of(t);
+        if (int rc2 = batch_enqueue_tile_outcomes(L.batch, &sink)) { fail(rc2, "outcomes"); break; }
+        batch_set_exact_sink(L.batch, &sink);
+        L.export_ms += now_ms() - t1;
+        prev_valid = t.m;
+    }
+    if (!L.rc) {  // the exact job of the last tile
+        ExactOutcome o;
+        if (int rc = batch_finish_pending(L.batch, &o)) fail(rc, "exact path");
+        else count_outcome(o, prev_valid);
+    }
+    if (!L.rc)
+        if (int rc = batch_stream_synchronize(L.batch)) fail(rc, "synchronize");
+    if (!L.rc) {  // one selection over the whole lane, behind the last outcome
+        uint32_t count = 0;
+        launch_select(L.out, view.io.d_status, 0, n, view.io.select_mask, d_scan, view.io.d_selected, d_scan + scan_words - 1);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&count, d_scan + scan_words - 1, 4, hipMemcpyDeviceToHost, L.out);
+        if (e == hipSuccess) e = hipStreamSynchronize(L.out);
+        if (e != hipSuccess) fail_hip("selection", e);
+        L.io_d2h += 4;
+        io->n_selected = count;
+    }
+    } catch (const std::bad_alloc &) {
+        if (!L.rc) { L.rc = ACVM_E_NOMEM; L.error = "out of host memory in the lane's solver thread"; }
+    } catch (const std::exception &e) {
+        if (!L.rc) { L.rc = ACVM_E_INVALID; L.error = std::string("lane: ") + e.what(); }
+    }
+    if (L.rc) {  // leave the handle reusable (the sink of a job in flight is still the caller's memory: it is written or dropped here)
+        ExactOutcome o;
+        batch_finish_pending(L.batch, &o);
+        acvm_device_synchronize();
+    }
+    L.io_h2d += (acvm_debug_import_list_copies(L.batch) - list_copies) * (uint64_t)shape.n_in * 4;  // (the column list, when it changed)
+    hipFree(d_scratch_status);
+    hipFree(d_scan);
+    io->not_solved = L.not_solved;
+    L.total_ms = now_ms() - t_begin;
+}
+
+void run_lane_device(acvm_node *node, DeviceLane &L, const NodeLaneIo &lane, acvm_node_lane_io_t *io) {
+    try {
+        pin_thread(L.cpus);
+        run_lane_device_body(node, L, lane, io);
+    } catch (const std::bad_alloc &) {
+        if (!L.rc) { L.rc = ACVM_E_NOMEM; L.error = "out of host memory"; }
+    } catch (const std::exception &e) {
+        if (!L.rc) { L.rc = ACVM_E_INVALID; L.error = e.what(); }
+    } catch (...) {
+        if (!L.rc) { L.rc = ACVM_E_INVALID; L.error = "unknown exception"; }
+    }
+}
+
 // a lane's thread: pinned to the CPUs of its device's NUMA node (its upload thread and the staging helpers inherit the mask), and closed
 // against exceptions: std::terminate is not an error code
 void run_lane(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, acvm_result_t *results, uint8_t *kept, uint8_t *kept_assigned,
@@ -518,6 +649,34 @@ long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *v
     for (DeviceLane &L : n->lanes) not_solved += (long long)L.not_solved;
     return not_solved;
 } ABI_CATCH
+
+// The device form: every lane is checked (node_io_plan.cpp) before any lane starts, then each lane's thread walks its own rows.
+long long acvm_node_solve_device(acvm_node_t *n, acvm_node_lane_io_t *lanes, uint32_t n_lanes) try {
+    if (!n) return set_err(ACVM_E_INVALID, "null argument");
+    const double t0 = now_ms();
+    const size_t D = n->lanes.size();
+    std::vector<NodeLaneIo> checked;
+    std::string text;
+    if (int rc = node_io_check(NodeIoShape{(uint32_t)n->ids.size(), (uint32_t)n->keep.size(), n->tile}, lanes, n_lanes, (uint32_t)D, &checked, &text)) return set_err(rc, text);
+    std::vector<std::thread> th;
+    for (size_t d = 0; d < D; d++) th.emplace_back(run_lane_device, n, std::ref(n->lanes[d]), std::cref(checked[d]), &lanes[d]);
+    for (auto &t : th) t.join();
+    uint64_t total = 0;
+    for (size_t d = 0; d < D; d++) total += lanes[d].n;
+    n->last_n = total;
+    n->last_total_ms = now_ms() - t0;
+    for (size_t d = 0; d < D; d++)
+        if (n->lanes[d].rc) return set_err(n->lanes[d].rc, "lane " + std::to_string(d) + " (device " + std::to_string(n->lanes[d].device) + "): " + n->lanes[d].error);
+    long long not_solved = 0;
+    for (DeviceLane &L : n->lanes) not_solved += (long long)L.not_solved;
+    return not_solved;
+} ABI_CATCH
+int acvm_debug_node_io_bytes(const acvm_node_t *n, uint32_t lane, uint64_t *h2d, uint64_t *d2h) {
+    if (!n || lane >= n->lanes.size()) return set_err(ACVM_E_INVALID, "no such lane");
+    if (h2d) *h2d = n->lanes[lane].io_h2d;
+    if (d2h) *d2h = n->lanes[lane].io_d2h;
+    return 0;
+}
 
 int acvm_node_stats(acvm_node_t *n, acvm_node_stats_t *out) {
     if (!n || !out) return set_err(ACVM_E_INVALID, "null argument");

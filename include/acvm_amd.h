@@ -511,7 +511,7 @@ int acvm_batch_extract_witnesses(acvm_batch_t *b, const uint32_t *witnesses, uin
  *     map as it stands), after acvm_batch_solve_opcode steps, with the forced slow path, with ACVM_BATCH_REUSE_SLOTS (initial witnesses and
  *     keep_ids only). The same refusals (ACVM_E_STATE): not solved; a witness that was not kept, or the whole map, of a batch that recycles
  *     rows or keeps exact lanes in its side table; initial witnesses or the whole map after acvm_batch_solve_then_import.
- * Not here: device outputs for acvm_node_solve, an asynchronous variant; the host exports above are unchanged.
+ * Not here: an asynchronous variant (the node's form is acvm_node_solve_device); the host exports above are unchanged.
  */
 enum { ACVM_ENC_BE32 = 0,          /* canonical, 32 bytes big-endian: byte for byte what acvm_batch_witness_map writes */
        ACVM_ENC_LE32 = 1,          /* canonical, 4 x u64 little-endian limbs (= 32 bytes little-endian) */
@@ -547,7 +547,7 @@ int acvm_batch_export_device(acvm_batch_t *b, const acvm_export_desc_t *d, void 
  *     beyond the live instances.
  *   - The call enqueues on the batch's stream and returns after that stream is synchronised. Going up: 16 bytes per instance of the exact path in the
  *     range. Coming back: the count, four bytes. Nothing proportional to n crosses PCIe.
- * Not here: a form for acvm_node_solve, an asynchronous variant; acvm_batch_results is unchanged.
+ * Not here: an asynchronous variant (the node's form is acvm_node_solve_device); acvm_batch_results is unchanged.
  */
 typedef struct {
     uint32_t first, n;          /* instances [first, first + n) */
@@ -569,7 +569,7 @@ int acvm_batch_outcomes_device(acvm_batch_t *b, const acvm_outcomes_desc_t *d, u
  *   - Host-to-device traffic per call: the witness list, and 4 bytes per instance of the exact path when the set of those instances changed since the
  *     last list export of the handle. Never anything per instance of the batch or per list entry (acvm_debug_export_h2d_bytes: the cumulative bytes
  *     the three device-outcome entry points -- range export, list export, outcomes -- have copied to the device for this handle).
- * Not here: a form for acvm_node_solve, an asynchronous variant.
+ * Not here: a node form (acvm_node_solve_device writes every row and the selection), an asynchronous variant.
  */
 int acvm_batch_export_device_list(acvm_batch_t *b, const acvm_export_desc_t *d, const uint32_t *d_instances, void *d_values, uint8_t *d_assigned);
 uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b);
@@ -595,7 +595,7 @@ uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b);
  * acvm_batch_solve_then_import_ex is acvm_batch_solve_then_import for such a buffer: the same gate, the same refusals, a plain solve in the same
  * cases. The following acvm_batch_import_device costs nothing only when the pointer AND the descriptor's contents, column list included, are the
  * same (the library keeps a copy of the descriptor, not the caller's pointer); anything else imports again.
- * Not here: device inputs for acvm_node_solve, an asynchronous variant, a mask of unassigned inputs (every instance of a batch assigns the same
+ * Not here: an asynchronous variant (the node's form is acvm_node_solve_device), a mask of unassigned inputs (every instance of a batch assigns the same
  * ids); the host import and the two entry points above keep their behaviour.
  */
 typedef struct {
@@ -617,7 +617,7 @@ int acvm_batch_solve_then_import_ex(acvm_batch_t *b, const acvm_import_desc_t *d
  *     batch's stream is synchronised. At most one small host-to-device copy is made: all lists of the call in one buffer, which is reused while
  *     they do not change (acvm_debug_import_list_copies counts the copies a handle has made).
  *   - n_parts == 0 is valid only for a circuit without initial witnesses; a part with n == 0 supplies nothing.
- * Not here: an acvm_batch_solve_then_import form for parts, an asynchronous variant, device I/O for acvm_node_solve.
+ * Not here: an acvm_batch_solve_then_import form for parts, an asynchronous variant, parts for the inputs of acvm_node_solve_device.
  */
 typedef struct {
     const void *d_values;        /* device, aligned to the element size (16 bytes for the 32-byte encodings) */
@@ -714,7 +714,7 @@ typedef struct {
 typedef struct {
     uint32_t n_devices, tile_instances;
     uint64_t n_instances;
-    double total_ms;            /* wall clock of the last acvm_node_solve */
+    double total_ms;            /* wall clock of the last acvm_node_solve / acvm_node_solve_device */
     int device[16];
     uint32_t async_exact[16];   /* 1: the handle re-solves diverging instances beside the next tile */
     uint32_t tiles[16], exact_instances[16];
@@ -741,6 +741,45 @@ uint32_t acvm_node_num_devices(const acvm_node_t *n);
 long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, acvm_result_t *results, uint8_t *kept_be32,
                           uint8_t *kept_assigned, uint8_t *digests32);
 int acvm_node_stats(acvm_node_t *n, acvm_node_stats_t *out);
+/*
+ * acvm_node_solve for a producer and a consumer that live on the GPUs: every lane (one per handle of the node, in the order of the device list)
+ * reads its initial witnesses from, and writes its outcomes into, DEVICE memory of its own device. No value crosses PCIe in either direction.
+ *   - The caller decides the split: lane l solves rows 0 .. n - 1 of ITS buffers, in tiles of acvm_node_tile_instances. n == 0: the lane idles and
+ *     none of its pointers is read. There is no global numbering: d_selected holds row numbers of the lane's own buffers.
+ *   - d_values / in: read per tile as acvm_batch_import_device reads them; row i runs over the lane's n, a stride of 0 is dense over n.
+ *   - d_kept / d_kept_assigned: element (i, k), k = position in the node's keep_ids, in any ACVM_ENC_* and either layout, kept_stride in elements
+ *     (0 = dense over n): what acvm_batch_export_device of a plain batch writes, mask bytes 0 / 1 / 2 and zero bytes for unassigned elements
+ *     included. BE32, instance-major, dense is byte for byte the lane's slice of acvm_node_solve's kept_be32 / kept_assigned.
+ *   - d_status / d_err / d_opcode_index [n]: the columns of acvm_batch_outcomes_device; d_digests32 [n][32]: acvm_batch_digest's definition.
+ *   - select_mask / d_selected ([n] capacity): the ascending row numbers whose status is in the mask; n_selected is counted whether or not
+ *     d_selected is given. not_solved: the lane's rows that did not reach Solved. Both are written by the call.
+ *   - Every output may be NULL. Bytes outside the described elements are never written. The buffers must not be touched during the call; the call
+ *     returns after every lane's streams are synchronised, and every call reads the inputs anew.
+ *   - Every lane gets the checks of acvm_batch_import_device and acvm_batch_export_device (shape, alignment, stride against n, column range)
+ *     before ANY lane starts; also refused (ACVM_E_INVALID, the message names the lane): null inputs with n > 0 and initial witnesses, a mask
+ *     without d_kept, n >= 2^32, n_lanes != acvm_node_num_devices. A refused call starts nothing and leaves the node usable.
+ *   - The exact path of tile k still runs beside tile k + 1 (acvm_node_stats async_exact); its rows are written into the caller's buffers on the
+ *     device when its outcome is collected, one tile later.
+ *   - Returns the total number of rows not Solved, or a negative error. acvm_node_stats describes the last call of either form.
+ * acvm_debug_node_io_bytes: the cumulative bytes the device form's own code copied for that lane, host to device (column list, the lanes and
+ * records of the instances of the exact path) and back (the selection's count): nothing of it grows with n. The solve's own bookkeeping (the
+ * event words of a tile that flagged instances, the exact lanes' result records) is the batch's and is not counted.
+ * Not here: an asynchronous (caller-stream) variant, parts and broadcast columns for the inputs, whole-map outputs (keep_ids only), dense
+ * compaction of the solved rows across tiles.
+ */
+typedef struct {
+    uint64_t n;                  /* instances of this lane = rows 0 .. n-1 of every buffer below; 0: the lane idles. n < 2^32 */
+    const void *d_values;        /* initial witnesses on the lane's device, read as acvm_batch_import_device reads them */
+    acvm_import_desc_t in;       /* encoding, layout, columns, n_columns, stride; row i runs over the lane's n; stride 0 = dense over n */
+    void *d_kept; uint8_t *d_kept_assigned;                    /* element (i, k), k = position in the node's keep_ids; may be NULL */
+    uint32_t kept_encoding, kept_layout; uint64_t kept_stride; /* any ACVM_ENC_*, instance- or witness-major, 0 = dense over n */
+    uint8_t *d_status, *d_err; uint32_t *d_opcode_index;       /* [n] each, may be NULL: the columns of acvm_batch_outcomes_device */
+    uint8_t *d_digests32;        /* [n][32], acvm_batch_digest's definition; may be NULL */
+    uint32_t select_mask; uint32_t *d_selected;                /* [n] capacity: ascending ROW numbers i whose status is in the mask; may be NULL */
+    uint64_t n_selected, not_solved;                           /* written by the call */
+} acvm_node_lane_io_t;
+long long acvm_node_solve_device(acvm_node_t *n, acvm_node_lane_io_t *lanes, uint32_t n_lanes); /* n_lanes == acvm_node_num_devices */
+int acvm_debug_node_io_bytes(const acvm_node_t *n, uint32_t lane, uint64_t *h2d, uint64_t *d2h);
 /* host-only probes of the lanes' placement logic: a sysfs cpulist ("0-15,32-47") into CPU numbers (returns how many; the first `cap` are
  * written), and the NUMA node + local CPUs of PCI device `bus_id` under `pci_root` (normally /sys/bus/pci/devices) */
 int acvm_debug_cpulist(const char *text, uint32_t *cpus, uint32_t cap);
