@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
     "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
     "acvm_node_solve_device", "acvm_debug_node_io_bytes",
+    "acvm_batch_foreign_call_sites", "acvm_batch_foreign_call_inputs_device", "acvm_batch_resolve_foreign_calls_device", "acvm_debug_foreign_call_stats",
 ]
 
 
@@ -89,6 +90,26 @@ class NodeLaneIo(C.Structure):
                 ("kept_encoding", C.c_uint32), ("kept_layout", C.c_uint32), ("kept_stride", C.c_uint64), ("d_status", C.c_void_p), ("d_err", C.c_void_p),
                 ("d_opcode_index", C.c_void_p), ("d_digests32", C.c_void_p), ("select_mask", C.c_uint32), ("d_selected", C.c_void_p),
                 ("n_selected", C.c_uint64), ("not_solved", C.c_uint64)]
+
+
+class ForeignCallSite(C.Structure):
+    """acvm_foreign_call_site_t"""
+    _fields_ = [("opcode_index", C.c_uint32), ("brillig_index", C.c_uint32), ("n_inputs", C.c_uint32), ("n_waiting", C.c_uint32), ("n_resolved", C.c_uint32),
+                ("function", C.c_char * 64)]
+
+
+class ForeignCallInputsDesc(C.Structure):
+    """acvm_foreign_call_inputs_desc_t (the d_* fields are device addresses, 0 / None = NULL)"""
+    _fields_ = [("opcode_index", C.c_uint32), ("brillig_index", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32), ("encoding", C.c_uint32),
+                ("layout", C.c_uint32), ("n_columns", C.c_uint32), ("stride", C.c_uint64), ("d_instances", C.c_void_p), ("d_lens", C.c_void_p),
+                ("d_values", C.c_void_p), ("d_mask", C.c_void_p)]
+
+
+class ForeignCallAnswersDesc(C.Structure):
+    """acvm_foreign_call_answers_desc_t"""
+    _fields_ = [("opcode_index", C.c_uint32), ("brillig_index", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32), ("n_values", C.c_uint32),
+                ("is_array", C.c_char_p), ("lens", C.POINTER(C.c_uint32)), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("n_columns", C.c_uint32),
+                ("stride", C.c_uint64), ("d_values", C.c_void_p)]
 
 
 def element_size(encoding):
@@ -373,6 +394,12 @@ def lib():
         L.acvm_node_solve_device.restype = C.c_longlong
         L.acvm_node_solve_device.argtypes = [C.c_void_p, C.POINTER(NodeLaneIo), C.c_uint32]
         L.acvm_debug_node_io_bytes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "acvm_batch_foreign_call_sites"):
+        L.acvm_batch_foreign_call_sites.argtypes = [C.c_void_p, C.POINTER(ForeignCallSite), C.c_uint32]
+        L.acvm_batch_foreign_call_inputs_device.argtypes = [C.c_void_p, C.POINTER(ForeignCallInputsDesc), C.POINTER(C.c_uint32)]
+        L.acvm_batch_resolve_foreign_calls_device.argtypes = [C.c_void_p, C.POINTER(ForeignCallAnswersDesc)]
+        L.acvm_debug_foreign_call_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                     C.POINTER(C.c_uint64)]
     if hasattr(L, "acvm_debug_table_read"):
         L.acvm_debug_table_info.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.acvm_debug_table_read.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -1092,6 +1119,55 @@ class Batch:
         lens = (C.c_uint32 * max(len(values), 1))(*[1 if isinstance(v, int) else len(v) for v in values])
         flat = b"".join(int(v).to_bytes(32, "big") if isinstance(v, int) else b"".join(int(x).to_bytes(32, "big") for x in v) for v in values)
         _check(lib().acvm_batch_resolve_foreign_call(self._h, instance, len(values), is_arr, lens, flat))
+
+    def foreign_call_sites(self):
+        """The sites at which instances wait (acvm_batch_foreign_call_sites), ascending by (opcode, brillig index): a list of dicts with opcode_index,
+        brillig_index, n_inputs, n_waiting, n_resolved, function. Host only."""
+        n = _check(lib().acvm_batch_foreign_call_sites(self._h, None, 0))
+        arr = (ForeignCallSite * max(n, 1))()
+        n = min(n, _check(lib().acvm_batch_foreign_call_sites(self._h, arr, n)))
+        return [dict(opcode_index=s.opcode_index, brillig_index=s.brillig_index, n_inputs=s.n_inputs, n_waiting=s.n_waiting, n_resolved=s.n_resolved,
+                     function=s.function.decode()) for s in arr[:n]]
+
+    def foreign_call_inputs_device(self, opcode_index: int, brillig_index: int, first_row=0, n_rows=None, d_values=None, encoding=ENC_BE32,
+                                   layout=LAYOUT_INSTANCE_MAJOR, n_columns=0, stride=0, d_instances=None, d_lens=None, d_mask=None) -> int:
+        """The pending inputs of rows [first_row, first_row + n_rows) of the site's waiting list into device memory (acvm_batch_foreign_call_inputs_device):
+        d_values / d_mask hold n_columns elements per row in `encoding`, `layout` and `stride` (in elements, 0 = dense) as export_device writes witnesses;
+        d_instances uint32 [n_rows], d_lens uint32 [n_rows][n_inputs]; each a device pointer or None. Returns the largest number of values of a row --
+        with no pointer given that is the sizing call. n_rows None: to the end of the list. No value is copied to the host."""
+        if n_rows is None:
+            here = [s for s in self.foreign_call_sites() if (s["opcode_index"], s["brillig_index"]) == (opcode_index, brillig_index)]
+            n_rows = max((here[0]["n_waiting"] if here else 0) - first_row, 0)
+        desc = ForeignCallInputsDesc(opcode_index=opcode_index, brillig_index=brillig_index, first_row=first_row, n_rows=n_rows, encoding=encoding, layout=layout,
+                                     n_columns=n_columns, stride=stride, d_instances=d_instances, d_lens=d_lens, d_values=d_values, d_mask=d_mask)
+        longest = C.c_uint32()
+        _check(lib().acvm_batch_foreign_call_inputs_device(self._h, C.byref(desc), C.byref(longest)))
+        return longest.value
+
+    def resolve_foreign_calls_device(self, opcode_index: int, brillig_index: int, shape, d_values: int, first_row=0, n_rows=None, encoding=ENC_BE32,
+                                     layout=LAYOUT_INSTANCE_MAJOR, n_columns=None, stride=0):
+        """ACVM::resolve_pending_foreign_call for rows [first_row, first_row + n_rows) of the site's waiting list at once
+        (acvm_batch_resolve_foreign_calls_device). shape: one entry per output of the ForeignCallResult, None for a single value or the length of an
+        array -- the same for every row; d_values: device pointer, the row's values back to back in columns 0 .. total - 1, read as import_device
+        reads a buffer (n_columns None: the shape's total). No value is copied from the host."""
+        shape = list(shape)
+        if n_rows is None:
+            here = [s for s in self.foreign_call_sites() if (s["opcode_index"], s["brillig_index"]) == (opcode_index, brillig_index)]
+            n_rows = max((here[0]["n_waiting"] if here else 0) - first_row, 0)
+        is_arr = bytes(0 if n is None else 1 for n in shape)
+        lens = (C.c_uint32 * max(len(shape), 1))(*[1 if n is None else n for n in shape])
+        total = sum(1 if n is None else n for n in shape)
+        desc = ForeignCallAnswersDesc(opcode_index=opcode_index, brillig_index=brillig_index, first_row=first_row, n_rows=n_rows, n_values=len(shape), is_array=is_arr,
+                                      lens=lens, encoding=encoding, layout=layout, n_columns=total if n_columns is None else n_columns, stride=stride, d_values=d_values)
+        _check(lib().acvm_batch_resolve_foreign_calls_device(self._h, C.byref(desc)))
+
+    def foreign_call_stats(self) -> dict:
+        """bytes both forms of the foreign-call round trip copied over PCIe for this handle so far, and the device times of the last batch-wide kernels
+        and the device bytes of the result store's tables
+        (acvm_debug_foreign_call_stats)"""
+        h2d, d2h, t_in, t_app, store = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double(), C.c_uint64()
+        _check(lib().acvm_debug_foreign_call_stats(self._h, C.byref(h2d), C.byref(d2h), C.byref(t_in), C.byref(t_app), C.byref(store)))
+        return dict(h2d_bytes=h2d.value, d2h_bytes=d2h.value, inputs_kernel_ms=t_in.value, append_kernel_ms=t_app.value, store_bytes=store.value)
 
     def stats(self) -> dict:
         s = Stats()

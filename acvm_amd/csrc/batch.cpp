@@ -31,9 +31,19 @@ int stage_reserve(acvm_batch *b, size_t bytes) {
     return 0;
 }
 void clear_fc_store(acvm_batch *b) {
-    for (auto &sl : b->fc_slots)
+    for (auto &sl : b->fc_slots) {
+        if (sl.device_owned) {
+            // No column holds a result any more and the slot is host-built again. Its count row is zeroed where it lives by the next solve, in front of
+            // everything that solve enqueues (upload_fc_tables): nothing is enqueued or waited for here, an import stays as asynchronous as it was,
+            // and a failing memset is that solve's error.
+            sl.device_owned = false;
+            sl.clear_pending = true;
+            sl.bounds = FcBounds();
+        }
         if (!sl.inst.empty()) { sl.inst.clear(); sl.dirty = true; }
+    }
     b->fc_fail_msg.clear();
+    b->fc_epoch++;  // (no list of the old inputs is a list any more)
 }
 
 const char *acvm_last_error(void) { return g_last_error.c_str(); }

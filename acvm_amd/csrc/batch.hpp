@@ -2,6 +2,7 @@
 // node-level driver: one handle per device). Internal to the library.
 #pragma once
 #include "../../include/acvm_amd.h"
+#include "foreign_plan.hpp"
 #include "import_plan.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
@@ -215,6 +216,14 @@ struct acvm_batch {
         uint32_t *d_desc = nullptr;
         uint4 *d_vals = nullptr;
         bool dirty = false;
+        // Device-owned (batch_foreign.cpp): after the first batch-wide resolve into the slot its results live in d_desc / d_vals only -- `inst` is empty
+        // and stays so -- and every resolve, the per-instance one included, appends there through fc_append_kernel. bounds: what any instance's column
+        // may hold (foreign_plan.hpp FcBounds): exact at the conversion, grown by the largest result of a ROUND when a solve consumes the round's
+        // answers (fc_round_consumed) -- a column gains one result per round however many calls answer its rows.
+        // clear_fc_store returns the slot to host-built; the count row of its table is zeroed on the device by the next solve (clear_pending,
+        // batch_exact.cpp upload_fc_tables), so that an import that is not waited for stays so.
+        bool device_owned = false, clear_pending = false;
+        FcBounds bounds;
     };
     std::vector<FcSlot> fc_slots;
     FcStoreSlot *d_fc_store = nullptr;
@@ -223,6 +232,18 @@ struct acvm_batch {
     uint32_t fc_pend_desc_words = 0, fc_pend_vals_cap = 0, fc_lanes_cap = 0;
     std::vector<uint32_t> h_pend_desc, h_pend_vals;
     bool pend_host_valid = false;
+    // (acvm_debug_foreign_call_stats) bytes both forms of the round trip copied, and the device times of the last batch-wide kernels
+    uint64_t n_fc_h2d_bytes = 0, n_fc_d2h_bytes = 0;
+    hipEvent_t ev_fc[2] = {nullptr, nullptr};
+    // the (lane, instance) pairs of the last range of a waiting list the batch-wide calls were given, on the device (batch_foreign.cpp rows_on_device);
+    // fc_epoch counts what may change the lists: every solve and step, new inputs (clear_fc_store)
+    uint64_t fc_epoch = 1, fc_rows_key[4] = {0, 0, 0, 0};
+    std::vector<uint32_t> fc_rows_host;
+    uint32_t *d_fc_rows = nullptr;
+    size_t fc_rows_cap = 0;
+    bool fc_rows_valid = false, fc_rows_longest_valid = false;
+    uint32_t fc_rows_longest = 0;
+    double fc_inputs_ms = 0, fc_append_ms = 0;
     // grow-only device staging arena of the entry points that move data in or out (no hipMalloc / hipFree per call)
     uint8_t *d_stage = nullptr;
     size_t stage_cap = 0;
@@ -283,6 +304,9 @@ struct acvm_batch {
         for (auto &sl : fc_slots)
             for (void *p : {(void *)sl.d_desc, (void *)sl.d_vals})
                 if (p) hipFree(p);
+        if (d_fc_rows) hipFree(d_fc_rows);
+        for (hipEvent_t e : ev_fc)
+            if (e) hipEventDestroy(e);
         if (stream_dyn) hipStreamDestroy(stream_dyn);
         if (ev_start) hipEventDestroy(ev_start);
         if (ev_end) hipEventDestroy(ev_end);

@@ -51,6 +51,16 @@ int upload_fc_tables(acvm_batch *b, uint32_t n_slow) {
         HIPCHK(hipMalloc((void **)&b->d_fc_pend_desc, (size_t)pend_words * n_slow * 4));
         HIPCHK(hipMalloc((void **)&b->d_fc_pend_vals, (size_t)pend_vals * 2 * n_slow * sizeof(uint4)));
     }
+    // a slot that was device-owned when new inputs arrived (clear_fc_store): its count row is zeroed here, in front of everything this solve enqueues
+    // on any stream, and waited for -- the blocking copies below do not queue behind the batch's stream
+    bool cleared = false;
+    for (auto &sl : b->fc_slots)
+        if (sl.clear_pending) {
+            if (sl.d_desc) HIPCHK(hipMemsetAsync(sl.d_desc, 0, (size_t)b->Bp * 4, b->stream));
+            sl.clear_pending = false;
+            cleared = true;
+        }
+    if (cleared) HIPCHK(hipStreamSynchronize(b->stream));
     bool any = false;
     for (size_t si = 0; si < b->fc_slots.size(); si++) {
         auto &sl = b->fc_slots[si];
@@ -103,6 +113,7 @@ int upload_fc_tables(acvm_batch *b, uint32_t n_slow) {
         }
         HIPCHK(hipMemcpy(sl.d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(sl.d_vals, vbuf.data(), vbuf.size() * 4, hipMemcpyHostToDevice));
+        b->n_fc_h2d_bytes += (uint64_t)(desc.size() + vbuf.size()) * 4;
     }
     if (any && b->d_fc_store) {  // the kernels reach the tables through this array: the pointers may have moved
         std::vector<FcStoreSlot> tab(b->fc_slots.size());
@@ -427,6 +438,7 @@ int solve_resume(acvm_batch *b) {
             b->slow_res[t].status = ACVM_STATUS_IN_PROGRESS;
         }
     if (resumed.empty()) return count_not_solved(b);
+    fc_round_consumed(b);
     if (int rc = upload_fc_tables(b, n_slow)) return rc;
     hipStream_t s = b->stream;
     HIPCHK(hipEventRecord(b->ev_start, s));
@@ -451,6 +463,7 @@ int solve_stepping(acvm_batch *b, bool one) {
     const Plan &p = b->plan();
     hipStream_t s = b->stream;
     const uint32_t n_slow = b->B;
+    b->fc_epoch++;  // (a step may bring lanes to a site without consuming an answer: batch.hpp)
     if (!b->stepping) {
         b->slow_ids.resize(n_slow);
         b->events_clean = false;
@@ -485,6 +498,7 @@ int solve_stepping(acvm_batch *b, bool one) {
                 any = true;
             }
         if (any) {
+            fc_round_consumed(b);
             if (int rc = upload_fc_tables(b, n_slow)) return rc;
             HIPCHK(hipMemcpyAsync(b->d_slow_start, b->slow_start.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(b->d_slow_res, b->slow_res.data(), (size_t)n_slow * sizeof(SlowResult), hipMemcpyHostToDevice, s));
@@ -722,6 +736,7 @@ static int fetch_pending(acvm_batch *b) {
     if (n_slow && b->d_fc_pend_desc) {
         HIPCHK(hipMemcpy(b->h_pend_desc.data(), b->d_fc_pend_desc, b->h_pend_desc.size() * 4, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(b->h_pend_vals.data(), b->d_fc_pend_vals, b->h_pend_vals.size() * 4, hipMemcpyDeviceToHost));
+        b->n_fc_d2h_bytes += (uint64_t)(b->h_pend_desc.size() + b->h_pend_vals.size()) * 4;
     }
     b->pend_host_valid = true;
     return 0;
@@ -918,6 +933,8 @@ int acvm_batch_resolve_foreign_call(acvm_batch_t *b, uint32_t instance, uint32_t
     const auto &slots = b->plan().fc_slot_opcode;
     const size_t si = (size_t)(std::find(slots.begin(), slots.end(), opcode) - slots.begin());
     if (si >= b->fc_slots.size()) return set_err(ACVM_E_STATE, "the instance does not wait at a Brillig opcode with a foreign call");
+    // (an opcode whose results live on the device: a one-row append through the kernel of the batch-wide form, batch_foreign.cpp)
+    if (b->fc_slots[si].device_owned) return fc_append_one_instance(b, (uint32_t)t, si, n_values, is_array, lens, values_be32);
     std::vector<acvm_batch::FcValue> res(n_values);
     size_t off = 0;
     for (uint32_t i = 0; i < n_values; i++) {

@@ -57,6 +57,16 @@ int solve_stepping(acvm_batch *b, bool one);
 int ensure_side_table(acvm_batch *b, uint32_t n_lanes, bool own_scratch);
 int side_table_outcome(acvm_batch *b, ExactOutcome *out);
 
+// ---- batch_foreign.cpp
+// acvm_batch_resolve_foreign_call for exact lane t whose opcode's results (slot si) live on the device: the values are staged and appended by
+// fc_append_kernel as a list of one row; sets the lane's resolved_new
+int fc_append_one_instance(acvm_batch *b, uint32_t t, size_t si, uint32_t n_values, const uint8_t *is_array, const uint32_t *lens, const uint8_t *values_be32);
+
+// a solve is about to consume the answers of the round (the lanes' resolved_new are cleared): the round's largest result joins every device-owned slot's bounds
+static inline void fc_round_consumed(acvm_batch *b) {
+    for (auto &sl : b->fc_slots) foreign_bounds_fold(&sl.bounds);
+}
+
 // ---- the table a host read or a digest is made from: where the values lie, how they are unscaled, witness -> row (null: row = witness index)
 struct TableView { const uint4 *W; uint64_t Bp; Unscale u; const uint32_t *row_of; };
 // the table of the level kernels: scaled columns leave through 1 / scale unless the lane's event word says it took the exact path

@@ -107,6 +107,7 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
     const Plan &p = b->plan();
     b->next_imported = false;
     b->next_inputs = nullptr;
+    b->fc_epoch++;  // (any solve may change who waits where: batch.hpp)
     if (b->solved) {  // only resolved foreign calls can change anything
         if (b->stepping) return solve_stepping(b, false);
         // A few resumed instances continue on the exact in-order kernels from their Brillig opcode on. When a sizeable part of the
@@ -119,6 +120,7 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
         const int64_t mode = p.tune.fc_relevel;
         const bool relevel = n_resolved && (mode >= 0 ? mode != 0 : (uint64_t)n_resolved * 16 >= b->B);
         if (!relevel) return solve_resume(b);
+        fc_round_consumed(b);
         b->solved = false;
     }
     hipStream_t s = b->stream;

@@ -246,6 +246,34 @@ void launch_digest_fold_level(hipStream_t s, const uint4 *W, uint64_t Bp, uint32
                               const DigestTables &T, uint4 *partial);
 void launch_digest_final(hipStream_t s, const uint4 *partial, uint32_t n_rows, uint64_t stride, uint32_t first, uint32_t n, const uint32_t *event, const DigestTables &T,
                          uint8_t *out);
+// ---- kernels_foreign.hip: the foreign-call round trip of a whole batch on the device (foreign_store.hpp). rows: device pairs (exact lane,
+// instance) of the listed rows of a site's waiting list; row r of the launch is element row r of the caller's buffer.
+struct FcInputsOut {
+    const uint32_t *rows;
+    uint32_t n_rows, n_inputs;      // n_inputs: words per row of lens
+    uint32_t encoding, layout, n_columns;
+    uint64_t stride;                // in elements, >= the layout's dense stride
+    uint32_t *instances, *lens;     // each may be null
+    uint8_t *values, *mask;         // each may be null; values aligned to the element size (16 bytes for the 32-byte encodings)
+};
+// the largest number of pending values among the rows, max-ed into *max_values (one device word, zeroed by the caller)
+void launch_fc_inputs_max(hipStream_t s, const FcLanes &fc, uint32_t n_slow, const uint32_t *rows, uint32_t n_rows, uint32_t *max_values);
+void launch_fc_inputs(hipStream_t s, const FcLanes &fc, uint32_t n_slow, const FcInputsOut &o);
+struct FcAppend {
+    uint32_t *desc;                 // the slot's tables (FcStoreSlot, writable) and their capacities
+    uint4 *vals;
+    uint64_t Bp;
+    uint32_t desc_words, vals_cap;
+    const uint32_t *rows;
+    uint32_t n_rows;
+    const uint32_t *shape;          // device: [n_values, (is_array, n) x n_values], the same for every row
+    uint32_t shape_total;           // values of one result
+    uint32_t encoding, layout;
+    uint64_t stride;
+    const void *values;             // the caller's buffer: the row's values back to back in columns 0 .. shape_total - 1
+    uint32_t *refused;              // one device word, zeroed by the caller: rows whose result did not fit (nothing of them is written)
+};
+void launch_fc_append(hipStream_t s, const FcAppend &a);
 // InProgress -> Solved after the last opcode
 void launch_exact_finish(hipStream_t s, const ExactLanes &L, uint32_t min_ip = 0);
 

@@ -740,6 +740,7 @@ struct Planner {
                         }
                     fc_pending_vals = std::max(fc_pending_vals, vals);
                     p.fc_function[((uint64_t)oi << 32) | (uint32_t)k] = op.function;
+                    p.fc_n_inputs[((uint64_t)oi << 32) | (uint32_t)k] = (uint32_t)op.inputs.size();
                     p.fc_max_inputs = std::max<uint32_t>(p.fc_max_inputs, (uint32_t)op.inputs.size());
                 }
                 // results the circuit already carries (Brillig::foreign_call_results): descriptor

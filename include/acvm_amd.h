@@ -409,6 +409,88 @@ int acvm_batch_pending_foreign_call(acvm_batch_t *b, uint32_t instance, acvm_for
 int acvm_batch_pending_foreign_call_inputs(acvm_batch_t *b, uint32_t instance, uint32_t *lens, uint8_t *values_be32);
 int acvm_batch_resolve_foreign_call(acvm_batch_t *b, uint32_t instance, uint32_t n_values, const uint8_t *is_array, const uint32_t *lens,
                                     const uint8_t *values_be32);
+/*
+ * The same round trip for the whole batch, where both halves of the data already are: the inputs of the waiting instances as DEVICE columns, the
+ * answers read from DEVICE columns -- a GPU oracle (a note database, a Merkle-path service, a logger that discards its input) answers a batch
+ * without a value crossing PCIe and without a call per instance. Encodings, layouts, stride and alignment are those of acvm_batch_export_device /
+ * acvm_batch_import_device below (ACVM_ENC_*, ACVM_LAYOUT_*).
+ *
+ * Sites and rows. A waiting instance waits at a site = (opcode_index, brillig_index). acvm_batch_foreign_call_sites writes up to `cap` of the distinct
+ * sites at which instances of the batch wait, ascending by (opcode, brillig index), and returns their number (0 for a batch that is not solved);
+ * it is host only and copies nothing. The calls the library answers itself (a caller's BlackBoxFunctionSolver inside a Brillig program) are never
+ * listed. The WAITING LIST of a site is its instances in ascending instance number; it is fixed from one acvm_batch_solve / acvm_batch_solve_opcode
+ * to the next: answering a row does not remove it (n_resolved counts the answered ones). Row r below is position r of that list, and element row
+ * i = r - first_row of the caller's buffer.
+ *
+ * acvm_batch_foreign_call_inputs_device: for rows [first_row, first_row + n_rows) of the site
+ *   - d_instances[i] = the row's absolute instance number; d_lens[i * n_inputs + k] = the number of values of input k (n_inputs of the site);
+ *   - element (i, v) of d_values = the v-th value of the row's inputs back to back -- the values acvm_batch_pending_foreign_call_inputs returns for
+ *     that instance -- encoded as the export encodes a witness, at (i * stride + v) * size instance-major, (v * stride + i) * size witness-major
+ *     (stride in elements, 0 = dense: n_columns resp. n_rows); d_mask, same layout and stride, one byte per element: 1 = the value exists (and fits
+ *     a narrow encoding), 2 = it exists but is 2^(8 size) or more. A column at or beyond the row's total is zero bytes, mask 0.
+ *   - *max_values (may be NULL) = the largest total over the rows, found on the device (four bytes come back). With d_values and d_mask NULL this is
+ *     the sizing call. n_columns below that maximum is ACVM_E_INVALID when d_values or d_mask is given; the message states the needed width and nothing
+ *     is written.
+ *   - Each of the four pointers may be NULL. ACVM_E_INVALID: a null descriptor, rows outside the list, an unknown encoding or layout, a stride below
+ *     the dense one, a d_values that is not aligned as the export asks. ACVM_E_STATE: a batch that is not solved.
+ *   - The host knows which lanes wait where (it holds every instance's status): the calls upload 8 bytes per listed row (lane and
+ *     instance number), once per range between two solves, and no value; each returns after the batch's stream is synchronised.
+ *
+ * acvm_batch_resolve_foreign_calls_device: ACVM::resolve_pending_foreign_call (pwg/mod.rs:214-228) for rows [first_row, first_row + n_rows) at once:
+ * ONE ForeignCallResult shape for all of them -- n_values outputs, output k a single value (is_array[k] == 0) or an array of lens[k] values; both
+ * arrays on the HOST -- and the values of row i back to back in columns 0 .. total - 1 of d_values, read as acvm_batch_import_device reads a buffer
+ * (row = the instance axis). One result is appended to each instance's results of that opcode.
+ *   - Every 256-bit string is accepted and reduced as the per-instance call reduces it (BE32: from_be_bytes_reduce; LE32, MONT256_LE and the narrow
+ *     encodings as acvm_batch_import_device decodes them).
+ *   - The shape is not checked against the bytecode: a count or size that does not match fails the VM when it runs again, exactly as after the
+ *     per-instance call.
+ *   - Refused as a whole, the handle left as it was: ACVM_E_STATE for a batch that is not solved or a row that was already answered since the last
+ *     solve; ACVM_E_INVALID for rows outside the list, n_columns below the shape's total, a bad stride, alignment, encoding or layout, null arrays;
+ *     ACVM_E_UNSUPPORTED for a handle with a caller's BlackBoxFunctionSolver (its internal calls keep the result store on the host).
+ *   - Afterwards acvm_batch_solve / acvm_batch_solve_opcode continue the rows exactly as after per-instance resolves. Both forms may be mixed, in
+ *     any order, on one handle: acvm_batch_resolve_foreign_call appends through the same kernel once an opcode's results live on the device.
+ *   - Uploads the shape words, and 8 bytes per listed row unless the inputs call left them there for the same range; returns after the batch's
+ *     stream is synchronised. However many calls answer the rows of one round, the result store grows by one result per instance and round.
+ * acvm_debug_foreign_call_stats: the cumulative bytes BOTH forms of the round trip copied host-to-device / device-to-host for this handle, and the
+ * device times (HIP events) of the last inputs and append kernels, and the device bytes the result store's tables hold right now (they grow by one
+ * result per column and round, however many calls answer a round's rows). Each pointer may be NULL.
+ * Not here: per-row result shapes (the per-instance call); a node form; an asynchronous variant; answering by a device-side instance list (the
+ * host must know which lanes resume).
+ */
+typedef struct {
+    uint32_t opcode_index, brillig_index;
+    uint32_t n_inputs;      /* inputs of the ForeignCall as written in the bytecode */
+    uint32_t n_waiting;     /* instances whose status is RequiresForeignCall at this site */
+    uint32_t n_resolved;    /* of those, how many were answered since the last solve */
+    char function[64];
+} acvm_foreign_call_site_t;
+int acvm_batch_foreign_call_sites(acvm_batch_t *b, acvm_foreign_call_site_t *out, uint32_t cap);
+typedef struct {
+    uint32_t opcode_index, brillig_index;
+    uint32_t first_row, n_rows;      /* rows [first_row, first_row + n_rows) of the site's list */
+    uint32_t encoding, layout;       /* any ACVM_ENC_*; ACVM_LAYOUT_INSTANCE_MAJOR (row-major) or ACVM_LAYOUT_WITNESS_MAJOR (column-major) */
+    uint32_t n_columns;              /* capacity in values per row */
+    uint64_t stride;                 /* elements, 0 = dense */
+    uint32_t *d_instances;           /* [n_rows] absolute instance numbers (may be NULL) */
+    uint32_t *d_lens;                /* [n_rows][n_inputs] values per input, row-major (may be NULL) */
+    void     *d_values;              /* (may be NULL) */
+    uint8_t  *d_mask;                /* same layout and stride, one byte per element (may be NULL) */
+} acvm_foreign_call_inputs_desc_t;
+int acvm_batch_foreign_call_inputs_device(acvm_batch_t *b, const acvm_foreign_call_inputs_desc_t *d, uint32_t *max_values);
+typedef struct {
+    uint32_t opcode_index, brillig_index;
+    uint32_t first_row, n_rows;
+    uint32_t n_values;               /* outputs of ONE ForeignCallResult, the same shape for every row */
+    const uint8_t *is_array;         /* HOST [n_values] */
+    const uint32_t *lens;            /* HOST [n_values], length of an array output (ignored for a single value) */
+    uint32_t encoding, layout;
+    uint32_t n_columns;
+    uint64_t stride;
+    const void *d_values;            /* the row's values back to back in columns 0 .. total - 1 */
+} acvm_foreign_call_answers_desc_t;
+int acvm_batch_resolve_foreign_calls_device(acvm_batch_t *b, const acvm_foreign_call_answers_desc_t *d);
+int acvm_debug_foreign_call_stats(const acvm_batch_t *b, uint64_t *h2d_bytes, uint64_t *d2h_bytes, double *inputs_kernel_ms, double *append_kernel_ms,
+                                  uint64_t *store_bytes);
 /* enable per-kernel HIP-event timing of the level kernels (small overhead) */
 int acvm_batch_set_profiling(acvm_batch_t *b, int on);
 
