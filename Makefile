@@ -5,14 +5,22 @@
 #               feeds it its command streams), and the assigned set of the host reads: tools/asan/assigned_view_host_test
 #               (tests/test_assigned_view_on_host.py), and the checks and tile views of the node's device form: tools/asan/node_io_plan_host_test
 #               (tests/test_node_io_plan_on_host.py), and the site lists, refusals, shapes and capacity rule of the batch-wide foreign calls:
-#               tools/asan/foreign_plan_host_test (tests/test_foreign_plan_on_host.py)
+#               tools/asan/foreign_plan_host_test (tests/test_foreign_plan_on_host.py), and their per-row form -- the lanes a mask resumes, the
+#               refusal order, the width behind the sizing launch: tools/asan/foreign_rows_plan_host_test -- with the per-row append of the result
+#               store run on the host: tools/asan/foreign_rows_store_host_test (hipcc, host side sanitized; tests/test_foreign_rows_on_host.py), and the
+#               host-only decisions of the node's foreign-call loop -- handler checks, row_base, scratch sizes, round cap:
+#               tools/asan/node_foreign_plan_host_test (tests/test_foreign_rows_on_host.py)
 CXX ?= g++
 ASAN_FLAGS = -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wno-sign-compare
 ASAN_SRCS = tools/asan/fuzz_driver.cpp acvm_amd/csrc/circuit.cpp acvm_amd/csrc/plan.cpp acvm_amd/csrc/tuning.cpp acvm_amd/csrc/schedule.cpp acvm_amd/csrc/schedule_check.cpp
 PLAN_SRCS = tools/import_plan_host_test.cpp acvm_amd/csrc/import_plan.cpp
 NODE_IO_SRCS = tools/node_io_plan_host_test.cpp acvm_amd/csrc/node_io_plan.cpp acvm_amd/csrc/import_plan.cpp
 FOREIGN_SRCS = tools/foreign_plan_host_test.cpp acvm_amd/csrc/foreign_plan.cpp acvm_amd/csrc/import_plan.cpp
-asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigned_view_host_test tools/asan/node_io_plan_host_test tools/asan/foreign_plan_host_test
+FOREIGN_ROWS_SRCS = tools/foreign_rows_plan_host_test.cpp acvm_amd/csrc/foreign_plan.cpp acvm_amd/csrc/import_plan.cpp
+NODE_FOREIGN_SRCS = tools/node_foreign_plan_host_test.cpp acvm_amd/csrc/node_foreign_plan.cpp acvm_amd/csrc/import_plan.cpp
+HIPCC ?= /opt/rocm/bin/hipcc
+asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigned_view_host_test tools/asan/node_io_plan_host_test tools/asan/foreign_plan_host_test \
+      tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test
 tools/asan/fuzz_driver: $(ASAN_SRCS) $(wildcard acvm_amd/csrc/*.hpp)
 	$(CXX) $(ASAN_FLAGS) -o $@ $(ASAN_SRCS) -lz
 tools/asan/import_plan_host_test: $(PLAN_SRCS) acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
@@ -21,6 +29,12 @@ tools/asan/node_io_plan_host_test: $(NODE_IO_SRCS) acvm_amd/csrc/node_io_plan.hp
 	$(CXX) $(ASAN_FLAGS) -o $@ $(NODE_IO_SRCS)
 tools/asan/foreign_plan_host_test: $(FOREIGN_SRCS) acvm_amd/csrc/foreign_plan.hpp acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
 	$(CXX) $(ASAN_FLAGS) -o $@ $(FOREIGN_SRCS)
+tools/asan/foreign_rows_plan_host_test: $(FOREIGN_ROWS_SRCS) acvm_amd/csrc/foreign_plan.hpp acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
+	$(CXX) $(ASAN_FLAGS) -o $@ $(FOREIGN_ROWS_SRCS)
+tools/asan/foreign_rows_store_host_test: tools/foreign_rows_store_host_test.hip acvm_amd/csrc/foreign_store.hpp
+	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/foreign_rows_store_host_test.hip
+tools/asan/node_foreign_plan_host_test: $(NODE_FOREIGN_SRCS) acvm_amd/csrc/node_foreign_plan.hpp acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
+	$(CXX) $(ASAN_FLAGS) -o $@ $(NODE_FOREIGN_SRCS)
 tools/asan/assigned_view_host_test: tools/assigned_view_host_test.cpp acvm_amd/csrc/assigned_view.hpp
 	$(CXX) $(ASAN_FLAGS) -o $@ tools/assigned_view_host_test.cpp
 .PHONY: asan

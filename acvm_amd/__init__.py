@@ -50,6 +50,8 @@ ABI_SYMBOLS = [
     "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
     "acvm_node_solve_device", "acvm_debug_node_io_bytes",
     "acvm_batch_foreign_call_sites", "acvm_batch_foreign_call_inputs_device", "acvm_batch_resolve_foreign_calls_device", "acvm_debug_foreign_call_stats",
+    "acvm_batch_resolve_foreign_calls_device_rows",
+    "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
 ]
 
 
@@ -110,6 +112,79 @@ class ForeignCallAnswersDesc(C.Structure):
     _fields_ = [("opcode_index", C.c_uint32), ("brillig_index", C.c_uint32), ("first_row", C.c_uint32), ("n_rows", C.c_uint32), ("n_values", C.c_uint32),
                 ("is_array", C.c_char_p), ("lens", C.POINTER(C.c_uint32)), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("n_columns", C.c_uint32),
                 ("stride", C.c_uint64), ("d_values", C.c_void_p)]
+
+
+class ForeignCallAnswersRowsDesc(C.Structure):
+    """acvm_foreign_call_answers_rows_desc_t"""
+    _fields_ = ForeignCallAnswersDesc._fields_ + [("d_lens", C.c_void_p), ("d_answered", C.c_void_p)]
+
+
+SPACE_DEVICE, SPACE_HOST = 0, 1
+
+
+class NodeForeignRound(C.Structure):
+    """acvm_node_foreign_round_t (rows, lens, values and mask are addresses in the handler's memory space)"""
+    _fields_ = [("lane", C.c_uint32), ("device", C.c_int), ("tile", C.c_uint32), ("round", C.c_uint32), ("site", ForeignCallSite), ("n_rows", C.c_uint32),
+                ("max_values", C.c_uint32), ("row_base", C.c_uint64), ("rows", C.c_void_p), ("lens", C.c_void_p), ("values", C.c_void_p), ("mask", C.c_void_p)]
+
+
+class NodeForeignAnswer(C.Structure):
+    """acvm_node_foreign_answer_t"""
+    _fields_ = [("n_values", C.c_uint32), ("is_array", C.c_void_p), ("lens", C.c_void_p), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("n_columns", C.c_uint32),
+                ("stride", C.c_uint64), ("values", C.c_void_p), ("row_lens", C.c_void_p), ("answered", C.c_void_p)]
+
+
+_NODE_FOREIGN_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(NodeForeignRound), C.POINTER(NodeForeignAnswer))
+
+
+class NodeForeignHandler(C.Structure):
+    """acvm_node_foreign_handler_t"""
+    _fields_ = [("fn", _NODE_FOREIGN_FN), ("user", C.c_void_p), ("space", C.c_uint32), ("in_encoding", C.c_uint32), ("in_layout", C.c_uint32), ("max_rounds", C.c_uint32)]
+
+
+class NodeForeignStats(C.Structure):
+    """acvm_node_foreign_stats_t"""
+    _fields_ = [("rounds", C.c_uint32), ("handler_calls", C.c_uint32), ("rows_answered", C.c_uint64), ("rows_declined", C.c_uint64), ("rows_left_waiting", C.c_uint64),
+                ("handler_ms", C.c_double), ("h2d_bytes", C.c_uint64), ("d2h_bytes", C.c_uint64)]
+
+
+class ForeignRound:
+    """What a node's foreign-call handler is asked (acvm_node_foreign_round_t): lane, device, tile, round, opcode_index, brillig_index, function, n_inputs,
+    n_rows, max_values, row_base, in_encoding, in_layout, space, and the addresses rows, lens, values, mask -- device addresses for SPACE_DEVICE (the
+    lane's device is current: device_download reads them), host addresses for SPACE_HOST, which rows_list / lens_list / values_bytes / mask_bytes read."""
+
+    def __init__(self, r, space, in_encoding, in_layout):
+        self.lane, self.device, self.tile, self.round = r.lane, r.device, r.tile, r.round
+        self.opcode_index, self.brillig_index, self.n_inputs, self.function = r.site.opcode_index, r.site.brillig_index, r.site.n_inputs, r.site.function.decode()
+        self.n_rows, self.max_values, self.row_base = r.n_rows, r.max_values, r.row_base
+        self.rows, self.lens, self.values, self.mask = r.rows, r.lens, r.values, r.mask
+        self.space, self.in_encoding, self.in_layout = space, in_encoding, in_layout
+
+    def _read(self, ptr, size):
+        if not size:
+            return b""
+        return C.string_at(ptr, size) if self.space == SPACE_HOST else device_download(ptr, size)
+
+    def rows_list(self):
+        """the rows' instance numbers inside the tile, ascending; the caller's number of row i is row_base + rows_list()[i]"""
+        return list(memoryview(self._read(self.rows, 4 * self.n_rows)).cast("I"))
+
+    def lens_list(self):
+        flat = list(memoryview(self._read(self.lens, 4 * self.n_rows * self.n_inputs)).cast("I"))
+        return [flat[i * self.n_inputs:(i + 1) * self.n_inputs] for i in range(self.n_rows)]
+
+    def values_bytes(self) -> bytes:
+        return self._read(self.values, self.n_rows * self.max_values * element_size(self.in_encoding))
+
+    def mask_bytes(self) -> bytes:
+        return self._read(self.mask, self.n_rows * self.max_values)
+
+
+def device_download(ptr: int, size: int) -> bytes:
+    """`size` bytes at a device address of the current device (acvm_device_download)"""
+    out = C.create_string_buffer(max(size, 1))
+    _check(lib().acvm_device_download(out, ptr, size))
+    return out.raw[:size]
 
 
 def element_size(encoding):
@@ -400,6 +475,11 @@ def lib():
         L.acvm_batch_resolve_foreign_calls_device.argtypes = [C.c_void_p, C.POINTER(ForeignCallAnswersDesc)]
         L.acvm_debug_foreign_call_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                      C.POINTER(C.c_uint64)]
+    if hasattr(L, "acvm_batch_resolve_foreign_calls_device_rows"):
+        L.acvm_batch_resolve_foreign_calls_device_rows.argtypes = [C.c_void_p, C.POINTER(ForeignCallAnswersRowsDesc)]
+    if hasattr(L, "acvm_node_set_foreign_call_handler"):
+        L.acvm_node_set_foreign_call_handler.argtypes = [C.c_void_p, C.POINTER(NodeForeignHandler)]
+        L.acvm_node_foreign_stats.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(NodeForeignStats)]
     if hasattr(L, "acvm_debug_table_read"):
         L.acvm_debug_table_info.argtypes = [C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         L.acvm_debug_table_read.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
@@ -816,7 +896,7 @@ class Node:
         dg = np.zeros((n_instances, 32), dtype=np.uint8) if digests else None
         rc = lib().acvm_node_solve(self._h, n_instances, buf.ctypes.data if buf.size else None, C.cast(res, C.c_void_p) if res is not None else None,
                                    kv.ctypes.data if kv is not None else None, ka.ctypes.data if ka is not None else None, dg.ctypes.data if dg is not None else None)
-        _check(rc)
+        self._finish_call(rc)
         return rc, res, kv, ka, dg
 
     def solve_device(self, lanes):
@@ -841,8 +921,74 @@ class Node:
             for f in ("d_kept", "d_kept_assigned", "d_status", "d_err", "d_opcode_index", "d_digests32", "d_selected"):
                 setattr(io, f, lane.get(f) or None)
             io.select_mask = lane.get("select_mask", 0)
-        self.last_not_solved = _check(lib().acvm_node_solve_device(self._h, arr, len(lanes)))  # (the call's own return value: the total)
+        self.last_not_solved = self._finish_call(lib().acvm_node_solve_device(self._h, arr, len(lanes)))  # (the call's own return value: the total)
         return [(arr[q].not_solved, arr[q].n_selected) for q in range(len(lanes))]
+
+    def _finish_call(self, rc):
+        """a Python exception of the foreign-call handler left the node call as a negative return: it is raised again here, in front of the call's own error"""
+        raised = getattr(self, "_fc_raised", None)
+        if raised:
+            exc = raised[0]
+            del raised[:]
+            raise exc
+        return _check(rc)
+
+    def set_foreign_call_handler(self, fn, space=SPACE_DEVICE, in_encoding=ENC_BE32, in_layout=LAYOUT_INSTANCE_MAJOR, max_rounds=0):
+        """acvm_node_set_foreign_call_handler: fn(ForeignRound) is called on a lane's thread once per tile, round and site (lanes call it concurrently).
+        It returns a dict -- shape (one entry per output: None for a single value, otherwise an array's length; with row_lens any non-None entry), values,
+        and optionally encoding, layout, n_columns (default: the shape's total), stride, row_lens, answered -- or False to decline the site for this
+        tile, or a negative int to abort the node call. values / row_lens / answered: device addresses (int) for SPACE_DEVICE; bytes-like objects (or
+        None) for SPACE_HOST. A Python exception aborts the node call and is raised again by solve / solve_device. fn None: no handler."""
+        if fn is None:
+            _check(lib().acvm_node_set_foreign_call_handler(self._h, None))
+            self._fc = None
+            return
+        raised, keep = [], {}
+
+        def address(lane, what, x):
+            if x is None:
+                return None
+            if isinstance(x, int):
+                return x
+            buf = (C.c_char * max(len(x), 1)).from_buffer_copy(bytes(x) if len(x) else b"\0")
+            keep[lane].append(buf)
+            return C.addressof(buf)
+
+        def trampoline(user, r_ptr, out_ptr):
+            try:
+                r, out = r_ptr.contents, out_ptr.contents
+                ans = fn(ForeignRound(r, space, in_encoding, in_layout))
+                if ans is False:
+                    return 1
+                if isinstance(ans, int):
+                    return ans
+                keep[r.lane] = []  # (what the previous answer of this lane pointed at may go now)
+                shape = list(ans["shape"])
+                is_arr = (C.c_uint8 * max(len(shape), 1))(*[0 if n is None else 1 for n in shape])
+                lens = (C.c_uint32 * max(len(shape), 1))(*[1 if n is None else n for n in shape])
+                keep[r.lane] += [is_arr, lens]
+                out.n_values, out.is_array, out.lens = len(shape), C.addressof(is_arr), C.addressof(lens)
+                out.encoding, out.layout = ans.get("encoding", ENC_BE32), ans.get("layout", LAYOUT_INSTANCE_MAJOR)
+                total = sum(1 if n is None else n for n in shape)
+                out.n_columns, out.stride = ans["n_columns"] if ans.get("n_columns") is not None else total, ans.get("stride", 0)
+                out.values = address(r.lane, "values", ans.get("values"))
+                out.row_lens = address(r.lane, "row_lens", ans.get("row_lens"))
+                out.answered = address(r.lane, "answered", ans.get("answered"))
+                return 0
+            except BaseException as e:  # nothing unwinds through the library
+                raised.append(e)
+                return -1  # (ACVM_E_INVALID)
+
+        cb = _NODE_FOREIGN_FN(trampoline)
+        h = NodeForeignHandler(fn=cb, user=None, space=space, in_encoding=in_encoding, in_layout=in_layout, max_rounds=max_rounds)
+        _check(lib().acvm_node_set_foreign_call_handler(self._h, C.byref(h)))
+        self._fc, self._fc_raised = (cb, keep), raised  # the callback lives as long as the node may call it
+
+    def foreign_stats(self, lane: int) -> dict:
+        """acvm_node_foreign_stats: the foreign-call loop of this lane during the last solve / solve_device"""
+        st = NodeForeignStats()
+        _check(lib().acvm_node_foreign_stats(self._h, lane, C.byref(st)))
+        return {f: getattr(st, f) for f, _ in NodeForeignStats._fields_}
 
     def io_bytes(self, lane: int):
         """(host-to-device, device-to-host) bytes the device form has copied for this lane so far (acvm_debug_node_io_bytes)"""
@@ -1160,6 +1306,24 @@ class Batch:
         desc = ForeignCallAnswersDesc(opcode_index=opcode_index, brillig_index=brillig_index, first_row=first_row, n_rows=n_rows, n_values=len(shape), is_array=is_arr,
                                       lens=lens, encoding=encoding, layout=layout, n_columns=total if n_columns is None else n_columns, stride=stride, d_values=d_values)
         _check(lib().acvm_batch_resolve_foreign_calls_device(self._h, C.byref(desc)))
+
+    def resolve_foreign_calls_device_rows(self, opcode_index: int, brillig_index: int, shape, d_values, first_row=0, n_rows=None, encoding=ENC_BE32,
+                                          layout=LAYOUT_INSTANCE_MAJOR, n_columns=None, stride=0, d_lens=None, d_answered=None):
+        """resolve_foreign_calls_device with per-row answers (acvm_batch_resolve_foreign_calls_device_rows). d_lens: device pointer, uint32
+        [n_rows][len(shape)] row-major, the length of array output k of row i (None: the lengths of `shape` hold for every row; with d_lens an array
+        entry of `shape` only has to be not None); d_answered: device pointer, one byte per row, 0 = the row is not answered and keeps waiting (None:
+        every row is answered). n_columns None: the shape's total."""
+        shape = list(shape)
+        if n_rows is None:
+            here = [s for s in self.foreign_call_sites() if (s["opcode_index"], s["brillig_index"]) == (opcode_index, brillig_index)]
+            n_rows = max((here[0]["n_waiting"] if here else 0) - first_row, 0)
+        is_arr = bytes(0 if n is None else 1 for n in shape)
+        lens = (C.c_uint32 * max(len(shape), 1))(*[1 if n is None else n for n in shape])
+        total = sum(1 if n is None else n for n in shape)
+        desc = ForeignCallAnswersRowsDesc(opcode_index=opcode_index, brillig_index=brillig_index, first_row=first_row, n_rows=n_rows, n_values=len(shape),
+                                          is_array=is_arr, lens=lens, encoding=encoding, layout=layout, n_columns=total if n_columns is None else n_columns,
+                                          stride=stride, d_values=d_values, d_lens=d_lens, d_answered=d_answered)
+        _check(lib().acvm_batch_resolve_foreign_calls_device_rows(self._h, C.byref(desc)))
 
     def foreign_call_stats(self) -> dict:
         """bytes both forms of the foreign-call round trip copied over PCIe for this handle so far, and the device times of the last batch-wide kernels

@@ -241,6 +241,9 @@ struct acvm_batch {
     std::vector<uint32_t> fc_rows_host;
     uint32_t *d_fc_rows = nullptr;
     size_t fc_rows_cap = 0;
+    // the handle's own copy of a per-row call's d_answered: the host judges it and the kernels read it, whatever the caller does to its column meanwhile
+    uint8_t *d_fc_mask = nullptr;
+    size_t fc_mask_cap = 0;
     bool fc_rows_valid = false, fc_rows_longest_valid = false;
     uint32_t fc_rows_longest = 0;
     double fc_inputs_ms = 0, fc_append_ms = 0;
@@ -305,6 +308,7 @@ struct acvm_batch {
             for (void *p : {(void *)sl.d_desc, (void *)sl.d_vals})
                 if (p) hipFree(p);
         if (d_fc_rows) hipFree(d_fc_rows);
+        if (d_fc_mask) hipFree(d_fc_mask);
         for (hipEvent_t e : ev_fc)
             if (e) hipEventDestroy(e);
         if (stream_dyn) hipStreamDestroy(stream_dyn);

@@ -1,6 +1,6 @@
 // batch_foreign.cpp -- the Brillig foreign-call round trip for the whole batch (include/acvm_amd.h acvm_batch_foreign_call_sites,
-// acvm_batch_foreign_call_inputs_device, acvm_batch_resolve_foreign_calls_device): the pending inputs of the waiting instances leave as device columns
-// and the answers are appended to the result store where it lives (kernels_foreign.hip). Every check of what the caller hands over is foreign_plan.cpp's;
+// acvm_batch_foreign_call_inputs_device, acvm_batch_resolve_foreign_calls_device, acvm_batch_resolve_foreign_calls_device_rows): the pending inputs of
+// the waiting instances leave as device columns and the answers are appended to the result store where it lives (kernels_foreign.hip). Every check of what the caller hands over is foreign_plan.cpp's;
 // this file owns the store: a slot starts host-built (FcSlot::inst, batch_exact.cpp upload_fc_tables) and becomes device-owned at the first batch-wide
 // resolve into it.
 #include <algorithm>
@@ -213,11 +213,38 @@ static int slot_reserve(acvm_batch *b, acvm_batch::FcSlot &sl, uint32_t add_word
     return refresh_fc_store(b, s);
 }
 
-// One result of the shape `words` appended for the listed rows (pairs: lane, instance) from a device buffer -- the caller's, or h_values staged here
-// (fc_append_one_instance). Marks the lanes answered.
-// d_rows_ready: the pairs are on the device already (rows_on_device); null: they are staged here.
-static int append_rows(acvm_batch *b, size_t si, const std::vector<uint32_t> &pairs, const uint32_t *d_rows_ready, const std::vector<uint32_t> &words, uint32_t total, uint32_t encoding, uint32_t layout,
-                       uint64_t stride, const void *d_values, const uint8_t *h_values, size_t h_bytes) {
+// the per-row form of an append: only the rows of `resumed` are answered
+struct FcRowsForm {
+    const uint32_t *d_lens;
+    const uint8_t *d_answered;
+    uint32_t n_columns;
+    const std::vector<uint32_t> *resumed;  // pairs (lane, instance) of the answered rows (foreign_mask_resumes)
+};
+// what one append is given
+struct FcAppendCall {
+    size_t si = 0;                                 // the slot
+    const std::vector<uint32_t> *pairs = nullptr;  // (lane, instance) per listed row
+    const uint32_t *d_rows_ready = nullptr;        // the pairs on the device already, or null
+    const std::vector<uint32_t> *words = nullptr;  // the shape words
+    uint32_t total = 0;                            // values per row: the shape's total -- with rows_form the LARGEST total of an answered row
+    uint32_t encoding = 0, layout = 0;
+    uint64_t stride = 0;
+    const void *d_values = nullptr;                // the caller's device buffer, or
+    const uint8_t *h_values = nullptr;             // host values staged here (h_bytes of them)
+    size_t h_bytes = 0;
+    const FcRowsForm *rows_form = nullptr;         // the per-row form, or null
+};
+// One result of the shape `words` appended for the listed rows from a device buffer -- the caller's, or h_values staged here (fc_append_one_instance).
+// Marks the lanes answered.
+static int append_rows(acvm_batch *b, const FcAppendCall &c) {
+    const size_t si = c.si, h_bytes = c.h_bytes;
+    const std::vector<uint32_t> &pairs = *c.pairs, &words = *c.words;
+    const uint32_t *d_rows_ready = c.d_rows_ready;
+    const uint32_t total = c.total, encoding = c.encoding, layout = c.layout;
+    const uint64_t stride = c.stride;
+    const void *d_values = c.d_values;
+    const uint8_t *h_values = c.h_values;
+    const FcRowsForm *rows_form = c.rows_form;
     const uint32_t n_rows = (uint32_t)(pairs.size() / 2);
     if (!n_rows) return 0;
     HIPCHK(hipSetDevice(b->device));
@@ -241,7 +268,8 @@ static int append_rows(acvm_batch *b, size_t si, const std::vector<uint32_t> &pa
     b->n_fc_h2d_bytes += ((d_rows_ready ? 0 : pairs.size()) + words.size()) * 4 + h_bytes;
     const FcAppend a{sl.d_desc, sl.d_vals, b->Bp, sl.desc_words, sl.vals_cap, d_rows, n_rows, d_shape, total, encoding, layout, stride, d_values, d_refused};
     HIPCHK(hipEventRecord(b->ev_fc[0], s));
-    launch_fc_append(s, a);
+    if (rows_form) launch_fc_append_rows(s, FcAppendRows{a, rows_form->d_lens, rows_form->d_answered, rows_form->n_columns});
+    else launch_fc_append(s, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(b->ev_fc[1], s));
     uint32_t refused = 0;
@@ -255,7 +283,8 @@ static int append_rows(acvm_batch *b, size_t si, const std::vector<uint32_t> &pa
     if (refused) return set_err(ACVM_E_DEVICE, "the foreign-call result store refused " + std::to_string(refused) + " rows: its capacity bounds are broken");
     foreign_bounds_add(&sl.bounds, (uint32_t)words.size(), total);  // (per round, not per call: fc_round_consumed folds it in)
     if (b->fc_lane.size() < b->slow_ids.size()) b->fc_lane.resize(b->slow_ids.size());
-    for (uint32_t r = 0; r < n_rows; r++) b->fc_lane[pairs[2 * (size_t)r]].resolved_new = true;
+    const std::vector<uint32_t> &answered = rows_form ? *rows_form->resumed : pairs;
+    for (size_t r = 0; r < answered.size() / 2; r++) b->fc_lane[answered[2 * r]].resolved_new = true;
     return 0;
 }
 
@@ -276,7 +305,88 @@ int acvm_batch_resolve_foreign_calls_device(acvm_batch_t *b, const acvm_foreign_
     HIPCHK(hipSetDevice(b->device));
     bool cached = false;
     if (int rc = rows_on_device(b, list, d->opcode_index, d->brillig_index, d->first_row, d->n_rows, &cached)) return rc;
-    return append_rows(b, si, b->fc_rows_host, b->d_fc_rows, words, total, d->encoding, d->layout, stride, d->d_values, nullptr, 0);
+    FcAppendCall call;
+    call.si = si;
+    call.pairs = &b->fc_rows_host;
+    call.d_rows_ready = b->d_fc_rows;
+    call.words = &words;
+    call.total = total;
+    call.encoding = d->encoding;
+    call.layout = d->layout;
+    call.stride = stride;
+    call.d_values = d->d_values;
+    return append_rows(b, call);
+} ABI_CATCH
+
+int acvm_batch_resolve_foreign_calls_device_rows(acvm_batch_t *b, const acvm_foreign_call_answers_rows_desc_t *d) try {
+    if (!b || !d) return set_err(ACVM_E_INVALID, "null argument");
+    const std::vector<FcLaneRecord> lanes = lane_records(b);
+    const std::vector<FcRow> list = foreign_waiting_list(lanes.data(), lanes.size(), d->opcode_index, d->brillig_index);
+    const FcHandleView view = handle_view(b, d->opcode_index, d->brillig_index);
+    uint64_t stride = 0;
+    std::vector<uint32_t> words;
+    uint32_t total = 0;
+    std::string refusal;
+    if (int rc = foreign_check_answers_rows(&view, d, list, &stride, &words, &total, &refusal)) return set_err(rc, refusal);
+    if (!d->n_rows) return 0;
+    const auto &slots = b->plan().fc_slot_opcode;
+    const size_t si = (size_t)(std::find(slots.begin(), slots.end(), d->opcode_index) - slots.begin());
+    if (si >= b->fc_slots.size()) return set_err(ACVM_E_STATE, "the rows do not wait at a Brillig opcode with a foreign call");
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    // the host must know which lanes resume: the mask comes down, one byte per row. It is read ONCE: a copy in the handle's own device memory is what
+    // comes down and what both kernels read, so that the lanes marked answered and the rows appended are the same whatever happens to the caller's column
+    std::vector<uint8_t> mask;
+    const uint8_t *d_answered = nullptr;
+    if (d->d_answered) {
+        if (d->n_rows > b->fc_mask_cap) {
+            if (b->d_fc_mask) hipFree(b->d_fc_mask);
+            b->d_fc_mask = nullptr;
+            b->fc_mask_cap = 0;
+            const size_t cap = (size_t)d->n_rows + d->n_rows / 4 + 256;
+            HIPCHK(hipMalloc((void **)&b->d_fc_mask, cap));
+            b->fc_mask_cap = cap;
+        }
+        HIPCHK(hipMemcpyAsync(b->d_fc_mask, d->d_answered, d->n_rows, hipMemcpyDeviceToDevice, s));
+        d_answered = b->d_fc_mask;
+        mask.resize(d->n_rows);
+        HIPCHK(hipMemcpyAsync(mask.data(), d_answered, d->n_rows, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        b->n_fc_d2h_bytes += d->n_rows;
+    }
+    std::vector<uint32_t> resumed;
+    if (int rc = foreign_mask_resumes(list, d->first_row, d->n_rows, d->d_answered ? mask.data() : nullptr, &resumed, &refusal)) return set_err(rc, refusal);
+    if (resumed.empty()) return 0;  // (every row is left out: nothing is appended, nobody resumes)
+    // the largest total among the answered rows, found on the device before anything is written: it sizes the store and judges n_columns
+    if (d->d_lens) {
+        if (int rc = stage_reserve(b, 256 + align256(words.size() * 4))) return rc;
+        uint32_t *d_max = (uint32_t *)b->d_stage, *d_shape = (uint32_t *)(b->d_stage + 256);
+        uint32_t longest = 0;
+        HIPCHK(hipMemsetAsync(d_max, 0, 4, s));
+        HIPCHK(hipMemcpyAsync(d_shape, words.data(), words.size() * 4, hipMemcpyHostToDevice, s));
+        launch_fc_answers_max(s, d_shape, d->d_lens, d_answered, d->n_rows, d_max);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&longest, d_max, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        b->n_fc_h2d_bytes += words.size() * 4;
+        b->n_fc_d2h_bytes += 4;
+        if (int rc = foreign_check_rows_width(d->n_columns, longest, d->d_values != nullptr, &total, &refusal)) return set_err(rc, refusal);
+    }
+    bool cached = false;
+    if (int rc = rows_on_device(b, list, d->opcode_index, d->brillig_index, d->first_row, d->n_rows, &cached)) return rc;
+    const FcRowsForm form{d->d_lens, d_answered, d->n_columns, &resumed};
+    FcAppendCall call;
+    call.si = si;
+    call.pairs = &b->fc_rows_host;
+    call.d_rows_ready = b->d_fc_rows;
+    call.words = &words;
+    call.total = total;  // (the largest total of an answered row)
+    call.encoding = d->encoding;
+    call.layout = d->layout;
+    call.stride = stride;
+    call.d_values = d->d_values;
+    call.rows_form = &form;
+    return append_rows(b, call);
 } ABI_CATCH
 
 int fc_append_one_instance(acvm_batch *b, uint32_t t, size_t si, uint32_t n_values, const uint8_t *is_array, const uint32_t *lens, const uint8_t *values_be32) {
@@ -286,7 +396,17 @@ int fc_append_one_instance(acvm_batch *b, uint32_t t, size_t si, uint32_t n_valu
     if (int rc = foreign_shape(n_values, is_array, lens, &words, &total, &refusal)) return set_err(rc, refusal);
     const std::vector<uint32_t> pairs = {t, b->slow_ids[t]};
     // (canonical big-endian values back to back: one instance-major row; the arena is 256-byte aligned)
-    return append_rows(b, si, pairs, nullptr, words, total, ACVM_ENC_BE32, ACVM_LAYOUT_INSTANCE_MAJOR, std::max<uint32_t>(total, 1), nullptr, values_be32, (size_t)total * 32);
+    FcAppendCall call;
+    call.si = si;
+    call.pairs = &pairs;
+    call.words = &words;
+    call.total = total;
+    call.encoding = ACVM_ENC_BE32;
+    call.layout = ACVM_LAYOUT_INSTANCE_MAJOR;
+    call.stride = std::max<uint32_t>(total, 1);
+    call.h_values = values_be32;
+    call.h_bytes = (size_t)total * 32;
+    return append_rows(b, call);
 }
 
 int acvm_debug_foreign_call_stats(const acvm_batch_t *b, uint64_t *h2d_bytes, uint64_t *d2h_bytes, double *inputs_kernel_ms, double *append_kernel_ms,

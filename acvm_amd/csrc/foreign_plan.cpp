@@ -112,9 +112,10 @@ int foreign_check_width(const acvm_foreign_call_inputs_desc_t *d, uint32_t max_v
     return ACVM_E_INVALID;
 }
 
-int foreign_check_answers(const FcHandleView *view, const acvm_foreign_call_answers_desc_t *d, const std::vector<FcRow> &list, uint64_t *stride, std::vector<uint32_t> *words,
-                          uint32_t *total, std::string *err) {
-    if (!view || !d) { *err = "null argument"; return ACVM_E_INVALID; }
+// what both resolve calls check before a device is touched; per_row_lens: the lengths are a device column (the host shape's total and the width are
+// judged behind the sizing launch, foreign_check_rows_width); masked: which rows are answered is a device column (foreign_mask_resumes judges them)
+static int check_answers(const FcHandleView *view, const acvm_foreign_call_answers_desc_t *d, bool per_row_lens, bool masked, const std::vector<FcRow> &list, uint64_t *stride,
+                         std::vector<uint32_t> *words, uint32_t *total, std::string *err) {
     *err = buffer_check_shape(d->encoding, d->layout, false);
     if (!err->empty()) return ACVM_E_INVALID;
     if (!view->solved) { *err = "batch not solved"; return ACVM_E_STATE; }
@@ -126,23 +127,70 @@ int foreign_check_answers(const FcHandleView *view, const acvm_foreign_call_answ
     if (!err->empty()) return ACVM_E_INVALID;
     std::vector<uint32_t> w;
     uint32_t sum = 0;
-    if (int rc = foreign_shape(d->n_values, d->is_array, d->lens, &w, &sum, err)) return rc;
-    if (d->n_columns < sum) {
-        *err = "n_columns " + std::to_string(d->n_columns) + " is below the " + std::to_string(sum) + " values of the result's shape";
-        return ACVM_E_INVALID;
+    if (per_row_lens) {
+        // (the host lens are not read: an array output's words carry length 0 here, the row's own length on the device)
+        if (d->n_values && !d->is_array) { *err = "null argument"; return ACVM_E_INVALID; }
+        const std::vector<uint32_t> none(d->n_values, 0u);
+        if (int rc = foreign_shape(d->n_values, d->is_array, none.data(), &w, &sum, err)) return rc;
+    } else {
+        if (int rc = foreign_shape(d->n_values, d->is_array, d->lens, &w, &sum, err)) return rc;
+        if (d->n_columns < sum) {
+            *err = "n_columns " + std::to_string(d->n_columns) + " is below the " + std::to_string(sum) + " values of the result's shape";
+            return ACVM_E_INVALID;
+        }
+        if (sum && d->n_rows && !d->d_values) { *err = "null values"; return ACVM_E_INVALID; }
     }
-    if (sum && d->n_rows && !d->d_values) { *err = "null values"; return ACVM_E_INVALID; }
     uint64_t s = d->stride;
     *err = buffer_refusal(d->encoding, d->layout, d->n_rows, d->n_columns, d->d_values, &s);
     if (!err->empty()) return ACVM_E_INVALID;
-    for (uint32_t r = d->first_row; r < d->first_row + d->n_rows; r++)
+    if (!masked) {
+        std::vector<uint32_t> pairs;
+        if (int rc = foreign_mask_resumes(list, d->first_row, d->n_rows, nullptr, &pairs, err)) return rc;
+    }
+    *stride = s;
+    *words = std::move(w);
+    *total = sum;
+    return 0;
+}
+
+int foreign_check_answers(const FcHandleView *view, const acvm_foreign_call_answers_desc_t *d, const std::vector<FcRow> &list, uint64_t *stride, std::vector<uint32_t> *words,
+                          uint32_t *total, std::string *err) {
+    if (!view || !d) { *err = "null argument"; return ACVM_E_INVALID; }
+    return check_answers(view, d, false, false, list, stride, words, total, err);
+}
+
+int foreign_check_answers_rows(const FcHandleView *view, const acvm_foreign_call_answers_rows_desc_t *d, const std::vector<FcRow> &list, uint64_t *stride,
+                               std::vector<uint32_t> *words, uint32_t *total, std::string *err) {
+    if (!view || !d) { *err = "null argument"; return ACVM_E_INVALID; }
+    const acvm_foreign_call_answers_desc_t base{d->opcode_index, d->brillig_index, d->first_row, d->n_rows, d->n_values, d->is_array, d->lens, d->encoding, d->layout,
+                                                d->n_columns, d->stride, d->d_values};
+    return check_answers(view, &base, d->d_lens != nullptr, d->d_answered != nullptr, list, stride, words, total, err);
+}
+
+int foreign_mask_resumes(const std::vector<FcRow> &list, uint32_t first_row, uint32_t n_rows, const uint8_t *answered, std::vector<uint32_t> *pairs, std::string *err) {
+    std::vector<uint32_t> out;
+    for (uint32_t i = 0; i < n_rows; i++) {
+        if (answered && !answered[i]) continue;  // (left out: it may have been answered before, or be answered later in the round)
+        const uint32_t r = first_row + i;
         if (list[r].resolved) {
             *err = "row " + std::to_string(r) + " (instance " + std::to_string(list[r].instance) + ") was already answered since the last solve; call acvm_batch_solve";
             return ACVM_E_STATE;
         }
-    *stride = s;
-    *words = std::move(w);
-    *total = sum;
+        out.push_back(list[r].lane);
+        out.push_back(list[r].instance);
+    }
+    *pairs = std::move(out);
+    return 0;
+}
+
+int foreign_check_rows_width(uint32_t n_columns, uint32_t longest, bool has_values, uint32_t *total, std::string *err) {
+    if (longest >= FC_MAX_WORDS) { *err = "a row's lengths sum to 2^31 values or more: beyond any result"; return ACVM_E_INVALID; }
+    if (n_columns < longest) {
+        *err = "n_columns " + std::to_string(n_columns) + " is below the " + std::to_string(longest) + " values of the longest answered row";
+        return ACVM_E_INVALID;
+    }
+    if (longest && !has_values) { *err = "null values"; return ACVM_E_INVALID; }
+    *total = longest;
     return 0;
 }
 

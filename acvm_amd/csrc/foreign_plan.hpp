@@ -2,7 +2,8 @@
 // acvm_batch_resolve_foreign_calls_device), checked and laid out before anything touches a device: what batch_foreign.cpp hands to the kernels of
 // kernels_foreign.hip. Pure host code like import_plan.hpp: no HIP call, no handle, no thread-local error text -- the site list, a site's waiting list,
 // every refusal with its text, the shape words and the capacity rule of the result store run in a plain C++ program
-// (tools/foreign_plan_host_test.cpp, tests/test_foreign_plan_on_host.py, `make asan`).
+// (tools/foreign_plan_host_test.cpp, tests/test_foreign_plan_on_host.py, `make asan`; the per-row form acvm_batch_resolve_foreign_calls_device_rows:
+// tools/foreign_rows_plan_host_test.cpp, tests/test_foreign_rows_on_host.py).
 #pragma once
 #include "import_plan.hpp"
 
@@ -51,6 +52,20 @@ int foreign_check_width(const acvm_foreign_call_inputs_desc_t *d, uint32_t max_v
 // acvm_batch_resolve_foreign_calls_device, everything: 0 with *stride, *words and *total, or the code and the text
 int foreign_check_answers(const FcHandleView *view, const acvm_foreign_call_answers_desc_t *d, const std::vector<FcRow> &list, uint64_t *stride, std::vector<uint32_t> *words,
                           uint32_t *total, std::string *err);
+
+// acvm_batch_resolve_foreign_calls_device_rows. The refusals come in this order: the checks of foreign_check_answers up to the buffer (with d_lens the
+// host lens are not read, the words of an array output carry length 0 -- the row's own length is the device's -- and the shape's total and the width
+// are judged behind the sizing launch); then, with the mask on the host, foreign_mask_resumes; then, with the sizing launch's answer,
+// foreign_check_rows_width. Without d_answered the rows that were already answered are refused here, as in foreign_check_answers.
+int foreign_check_answers_rows(const FcHandleView *view, const acvm_foreign_call_answers_rows_desc_t *d, const std::vector<FcRow> &list, uint64_t *stride,
+                               std::vector<uint32_t> *words, uint32_t *total, std::string *err);
+// The lanes a mask resumes: *pairs = (lane, instance) of the rows of [first_row, first_row + n_rows) whose answered[i] is nonzero (answered null: all
+// of them), ascending. ACVM_E_STATE when one of those was already answered since the last solve; an answered row that is left out is fine.
+int foreign_mask_resumes(const std::vector<FcRow> &list, uint32_t first_row, uint32_t n_rows, const uint8_t *answered, std::vector<uint32_t> *pairs, std::string *err);
+// Behind the sizing launch: longest = the largest total among the answered rows (0xFFFFFFFF: 2^31 or more). ACVM_E_INVALID for a total beyond any
+// result, for n_columns below the longest row (the text states the needed width), for values without a buffer; else *total = longest, what the
+// capacity rule below takes as this call's add_vals.
+int foreign_check_rows_width(uint32_t n_columns, uint32_t longest, bool has_values, uint32_t *total, std::string *err);
 
 // The capacity rule of a device-owned slot. A row is answered once between two solves, so a column gains at most ONE result per round, whatever the
 // number of calls that answer the round's rows (partial ranges, per-instance resolves): the bounds grow per round, not per call.

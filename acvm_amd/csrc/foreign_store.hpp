@@ -2,7 +2,8 @@
 // walk in ops_brillig.hpp brillig_foreign_call, which reads what is written here. Descriptor words of instance j lie at desc[w * Bp + j]:
 //     [n_results, (n_values, (is_array, n) x n_values) x n_results]
 // and its values, in the order of the descriptor, at vals[(2 v + h) * Bp + j] (two 16-byte halves per value, like a row of W). Everything here is
-// __host__ __device__ so that the host can run what kernels_foreign.hip runs (tools/foreign_store_host_test.hip, tests/test_foreign_store_on_host.py).
+// __host__ __device__ so that the host can run what kernels_foreign.hip runs (tools/foreign_store_host_test.hip, tests/test_foreign_store_on_host.py;
+// the per-row form: tools/foreign_rows_store_host_test.hip, tests/test_foreign_rows_on_host.py).
 #pragma once
 #include "import_decode.hpp"
 
@@ -79,6 +80,51 @@ FR_HD __forceinline__ bool fc_store_append(uint32_t *desc, uint4 *vals, uint64_t
     for (uint32_t c = 0; c < shape_total; c++) fc_store_write_value(vals, Bp, j, p.value + c, fc_answer_row(a.values, a.encoding, a.layout, a.stride, r, c));
     fc_store_commit(desc, j, p);
     return true;
+}
+
+// ---- per-row answers (acvm_batch_resolve_foreign_calls_device_rows): the shape words give n_values and which outputs are arrays; an array output k of
+// row r has lens[r * n_values + k] values (lens null: the shape's own n), a single value always 1; answered[r] == 0 (answered non-null) leaves the row out.
+struct FcRowAnswers {
+    const uint32_t *lens;     // [n_rows][n_values] row-major, or null
+    const uint8_t *answered;  // [n_rows], or null: every row
+    uint32_t n_columns;       // values per row the caller's buffer holds
+};
+FR_HD __forceinline__ bool fc_row_answered(const FcRowAnswers &ra, uint64_t r) { return !ra.answered || ra.answered[r] != 0; }
+FR_HD __forceinline__ uint32_t fc_row_len(const uint32_t *shape, const FcRowAnswers &ra, uint64_t r, uint32_t k) {
+    if (!shape[1u + 2u * k]) return 1u;
+    return ra.lens ? ra.lens[r * shape[0] + k] : shape[2u + 2u * k];
+}
+// the row's number of values, summed in 64 bits
+FR_HD __forceinline__ uint64_t fc_row_total(const uint32_t *shape, const FcRowAnswers &ra, uint64_t r) {
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < shape[0]; k++) total += fc_row_len(shape, ra, r, k);
+    return total;
+}
+// what the sizing launch reduces: 0 for a row that is left out, the row's total, 0xFFFFFFFF for a total of 2^31 or more (refused by the host)
+FR_HD __forceinline__ uint32_t fc_row_total_saturated(const uint32_t *shape, const FcRowAnswers &ra, uint64_t r) {
+    if (!fc_row_answered(ra, r)) return 0u;
+    const uint64_t total = fc_row_total(shape, ra, r);
+    return total >= (1ull << 31) ? 0xFFFFFFFFu : (uint32_t)total;
+}
+enum FcRowAppend : uint32_t { FC_ROW_APPENDED = 0, FC_ROW_LEFT_OUT = 1, FC_ROW_REFUSED = 2 };
+// The whole append of one row of the per-row form, as fc_append_rows_kernel's lane runs it. A row that is left out touches nothing. A row whose lengths
+// pass the caller's columns or the slot's words or values is refused, having written nothing. The shape words come from the row's own lengths; the
+// count word is written last.
+FR_HD __forceinline__ FcRowAppend fc_store_append_row(uint32_t *desc, uint4 *vals, uint64_t Bp, uint64_t j, uint32_t desc_words, uint32_t vals_cap, const uint32_t *shape,
+                                                      const FcRowAnswers &ra, const FcAnswers &a, uint64_t r) {
+    if (!fc_row_answered(ra, r)) return FC_ROW_LEFT_OUT;
+    const uint64_t total = fc_row_total(shape, ra, r);
+    if (total > ra.n_columns) return FC_ROW_REFUSED;
+    const FcAppendPos p = fc_store_walk(desc, Bp, j, desc_words);
+    if (!fc_store_fits(p, fc_shape_words(shape[0]), (uint32_t)total, desc_words, vals_cap)) return FC_ROW_REFUSED;
+    desc[(uint64_t)p.word * Bp + j] = shape[0];
+    for (uint32_t k = 0; k < shape[0]; k++) {
+        desc[(uint64_t)(p.word + 1u + 2u * k) * Bp + j] = shape[1u + 2u * k];
+        desc[(uint64_t)(p.word + 2u + 2u * k) * Bp + j] = fc_row_len(shape, ra, r, k);
+    }
+    for (uint32_t c = 0; c < (uint32_t)total; c++) fc_store_write_value(vals, Bp, j, p.value + c, fc_answer_row(a.values, a.encoding, a.layout, a.stride, r, c));
+    fc_store_commit(desc, j, p);
+    return FC_ROW_APPENDED;
 }
 
 // ---- the pending inputs of an exact lane (kernels.hpp FcLanes): pend_desc [n_inputs, len x n_inputs] at pend_desc[w * n_slow + t]

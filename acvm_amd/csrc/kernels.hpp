@@ -274,6 +274,16 @@ struct FcAppend {
     uint32_t *refused;              // one device word, zeroed by the caller: rows whose result did not fit (nothing of them is written)
 };
 void launch_fc_append(hipStream_t s, const FcAppend &a);
+// The per-row form (acvm_batch_resolve_foreign_calls_device_rows): a.shape gives n_values and which outputs are arrays, a.shape_total is not used.
+struct FcAppendRows {
+    FcAppend a;
+    const uint32_t *lens;           // device [n_rows][n_values] row-major: values of array output k of row r (null: a.shape's own lengths)
+    const uint8_t *answered;        // device [n_rows]: 0 = the row is left out (null: every row is answered)
+    uint32_t n_columns;             // values per row of the caller's buffer: a row whose lengths sum to more is refused
+};
+// the largest total among the answered rows, max-ed into *max_values (one device word, zeroed by the caller); 0xFFFFFFFF: a total of 2^31 or more
+void launch_fc_answers_max(hipStream_t s, const uint32_t *shape, const uint32_t *lens, const uint8_t *answered, uint32_t n_rows, uint32_t *max_values);
+void launch_fc_append_rows(hipStream_t s, const FcAppendRows &ar);
 // InProgress -> Solved after the last opcode
 void launch_exact_finish(hipStream_t s, const ExactLanes &L, uint32_t min_ip = 0);
 

@@ -4,6 +4,8 @@
 //  fc_inputs_max_kernel  one lane per listed row: the row's number of pending values, reduced to the maximum -- one atomic per wave
 //  fc_inputs_kernel      one thread per (row, column): the pending inputs of the row's exact lane, encoded like a witness of the export
 //  fc_append_kernel      one lane per listed row: one ForeignCallResult appended behind the instance's results of the opcode
+//  fc_answers_max_kernel the twin of fc_inputs_max_kernel for per-row answers: the total of each answered row's lengths, reduced to the maximum
+//  fc_append_rows_kernel fc_append_kernel with the row's own lengths and a mask of the rows that are answered
 //
 // Row r of a site's waiting list is exact lane rows[2 r], instance rows[2 r + 1]; the list is ascending in both, so consecutive rows are (mostly)
 // consecutive lanes: the loads of pend_desc / pend_vals along t and the stores of the result store along j coalesce like the rows of W. The caller's
@@ -86,6 +88,34 @@ __global__ void __launch_bounds__(256) fc_append_kernel(const FcAppend a) {
     if (!fc_store_append(a.desc, a.vals, a.Bp, j, a.desc_words, a.vals_cap, a.shape, a.shape_total, ans, r)) atomicAdd(a.refused, 1u);
 }
 
+// ---- per-row answers: the lengths of array outputs and the answered rows are device columns
+__global__ void __launch_bounds__(256) fc_answers_max_kernel(const uint32_t *__restrict__ shape, const uint32_t *__restrict__ lens, const uint8_t *__restrict__ answered,
+                                                             uint32_t n_rows, uint32_t *max_values) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const FcRowAnswers ra{lens, answered, 0u};
+    // (no early return: every lane of the wave takes part in the reduction)
+    uint32_t total = r < n_rows ? fc_row_total_saturated(shape, ra, r) : 0u;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)total, off, 64);
+        total = other > total ? other : total;
+    }
+    if ((threadIdx.x & 63u) == 0u && total) atomicMax(max_values, total);
+}
+
+// one lane per row; a row that is left out returns at once; refused[0] counts the answered rows whose result did not fit (nothing of them is written)
+__global__ void __launch_bounds__(256) fc_append_rows_kernel(const FcAppendRows ar) {
+    const FcAppend &a = ar.a;
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= a.n_rows) return;
+    const FcRowAnswers ra{ar.lens, ar.answered, ar.n_columns};
+    if (!fc_row_answered(ra, r)) return;
+    const uint64_t j = a.rows[2u * r + 1u];
+    if (j >= a.Bp) { atomicAdd(a.refused, 1u); return; }
+    const FcAnswers ans{(const uint8_t *)a.values, a.encoding, a.layout, a.stride};
+    if (fc_store_append_row(a.desc, a.vals, a.Bp, j, a.desc_words, a.vals_cap, a.shape, ra, ans, r) == FC_ROW_REFUSED) atomicAdd(a.refused, 1u);
+}
+
 void launch_fc_inputs_max(hipStream_t s, const FcLanes &fc, uint32_t n_slow, const uint32_t *rows, uint32_t n_rows, uint32_t *max_values) {
     if (!n_rows) return;
     hipLaunchKernelGGL(fc_inputs_max_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, fc, (uint64_t)n_slow, rows, n_rows, max_values);
@@ -98,6 +128,14 @@ void launch_fc_inputs(hipStream_t s, const FcLanes &fc, uint32_t n_slow, const F
 void launch_fc_append(hipStream_t s, const FcAppend &a) {
     if (!a.n_rows) return;
     hipLaunchKernelGGL(fc_append_kernel, dim3((a.n_rows + 255u) / 256u), dim3(256), 0, s, a);
+}
+void launch_fc_answers_max(hipStream_t s, const uint32_t *shape, const uint32_t *lens, const uint8_t *answered, uint32_t n_rows, uint32_t *max_values) {
+    if (!n_rows) return;
+    hipLaunchKernelGGL(fc_answers_max_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, s, shape, lens, answered, n_rows, max_values);
+}
+void launch_fc_append_rows(hipStream_t s, const FcAppendRows &ar) {
+    if (!ar.a.n_rows) return;
+    hipLaunchKernelGGL(fc_append_rows_kernel, dim3((ar.a.n_rows + 255u) / 256u), dim3(256), 0, s, ar);
 }
 
 }  // namespace acvm

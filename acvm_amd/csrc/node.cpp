@@ -12,10 +12,14 @@
 // acvm_node_solve_device is the same driver for callers whose data lives on the GPUs: per lane the inputs are read from, and kept witnesses,
 // outcome columns, digests and the selection written into, device memory of that lane (run_lane_device_body; checks and tile views:
 // node_io_plan.cpp). No staging, no producer thread; the exact path still runs beside the next tile and writes its rows on the device.
+// Both forms answer Brillig foreign calls through the node's handler, per tile, behind the tile's solve and in front of its export (foreign_rounds:
+// execute.rs:109-113; the host-only decisions: node_foreign_plan.cpp). Without a handler the rows leave in RequiresForeignCall.
 #include "batch.hpp"
 #include "circuit.hpp"
+#include "node_foreign_plan.hpp"
 #include "node_io_plan.hpp"
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -50,6 +54,13 @@ struct DeviceLane {
     uint64_t io_h2d = 0, io_d2h = 0;  // bytes the device form copied for this lane, cumulative (acvm_debug_node_io_bytes)
     std::string error;
     int rc = 0;
+    // the foreign-call handler's round trips (foreign_rounds): device scratch for a site's inputs and for an answer uploaded from host memory (both
+    // grow-only), host staging for a host-space handler, the statistics of the last node call
+    uint32_t index = 0;
+    uint8_t *d_fc = nullptr, *d_fc_ans = nullptr;
+    uint64_t fc_cap = 0, fc_ans_cap = 0;
+    std::vector<uint8_t> h_fc;
+    acvm_node_foreign_stats_t fc{};
     // host placement: the CPUs local to the device (sysfs), empty = unknown / not pinned
     int numa_node = -1;
     std::vector<uint32_t> cpus;
@@ -114,6 +125,13 @@ struct Joiner {
     }
 };
 
+// a node call is running (acvm_node_set_foreign_call_handler refuses meanwhile)
+struct RunningCall {
+    std::atomic<int> &count;
+    explicit RunningCall(acvm_node *n);
+    ~RunningCall() { count.fetch_sub(1); }
+};
+
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 }  // namespace
@@ -127,6 +145,10 @@ struct acvm_node {
     std::shared_ptr<const Plan> plan;  // the one plan every lane's handle shares
     uint32_t plans_built = 0;          // how often acvm_node_new levelised the circuit (0: the circuit's cache already held the plan; never more than 1)
     double create_ms = 0, plan_ms = 0;
+    // the foreign-call handler (acvm_node_set_foreign_call_handler): read by the lanes' threads during a node call, changed only between calls
+    bool has_solver = false, has_handler = false;
+    acvm_node_foreign_handler_t handler{};
+    std::atomic<int> running{0};
     ~acvm_node() {
         for (DeviceLane &l : lanes) {
             hipSetDevice(l.device);
@@ -140,6 +162,8 @@ struct acvm_node {
                 if (l.h_exp[k]) hipHostFree(l.h_exp[k]);
             }
             if (l.d_keep) hipFree(l.d_keep);
+            if (l.d_fc) hipFree(l.d_fc);
+            if (l.d_fc_ans) hipFree(l.d_fc_ans);
             if (l.copy) hipStreamDestroy(l.copy);
             if (l.out) hipStreamDestroy(l.out);
         }
@@ -147,6 +171,8 @@ struct acvm_node {
 };
 
 namespace {
+
+RunningCall::RunningCall(acvm_node *n) : count(n->running) { count.fetch_add(1); }
 
 // instances per handle when the caller leaves the choice to the library: the largest power of two (at most 2^17, the measured optimum of
 // the 10k-gate circuit, NOTEBOOK.md section 7) that every listed device has room for. Per device: 90 % of its free memory, less the lookup
@@ -205,6 +231,181 @@ uint64_t patch_outcome(const ExactOutcome &o, uint64_t base, uint32_t n_valid, u
     return not_solved;
 }
 
+// a grow-only device buffer of the lane; false: no memory (the old buffer is gone, the capacity says so)
+bool grow_device(uint8_t **d, uint64_t *cap, uint64_t need) {
+    const uint64_t want = node_foreign_grow(*cap, need);
+    if (!want) return true;
+    if (*d) hipFree(*d);
+    *d = nullptr;
+    *cap = 0;
+    if (hipMalloc((void **)d, want) != hipSuccess) { (void)hipGetLastError(); *d = nullptr; return false; }
+    *cap = want;
+    return true;
+}
+
+// The foreign-call loop of one tile, behind its acvm_batch_solve and in front of its export (include/acvm_amd.h acvm_node_set_foreign_call_handler;
+// the reference's caller: acvm_js/src/execute.rs:109-113 per instance): per round every site the handle lists is handed to the handler with its
+// inputs in the lane's scratch, the answer goes through acvm_batch_resolve_foreign_calls_device_rows, and the tile is solved again. The host-only
+// decisions are node_foreign_plan.cpp's. A failure sets L.rc / L.error; the callers' L.rc paths leave the handle reusable.
+void foreign_rounds(acvm_node *node, DeviceLane &L, uint32_t tile_index, uint64_t row_base) {
+    if (!node->has_handler || L.rc) return;
+    const acvm_node_foreign_handler_t &H = node->handler;
+    auto fail = [&](int rc, const std::string &what) { if (!L.rc) { L.rc = rc; L.error = what + ": " + acvm_last_error(); } };
+    auto fail_text = [&](int rc, const std::string &text) { if (!L.rc) { L.rc = rc; L.error = text; } };
+    const uint32_t max_rounds = node_foreign_max_rounds(H.max_rounds), in_size = buffer_element_size(H.in_encoding);
+    const bool host = H.space == ACVM_SPACE_HOST;
+    uint64_t h2d0 = 0, d2h0 = 0, own_h2d = 0, own_d2h = 0;
+    acvm_debug_foreign_call_stats(L.batch, &h2d0, &d2h0, nullptr, nullptr, nullptr);
+    std::vector<acvm_foreign_call_site_t> sites;
+    std::vector<uint64_t> declined;  // sites the handler declined for this tile
+    auto key_of = [](const acvm_foreign_call_site_t &s) { return ((uint64_t)s.opcode_index << 32) | s.brillig_index; };
+    auto list_sites = [&]() -> bool {
+        int ns = acvm_batch_foreign_call_sites(L.batch, nullptr, 0);
+        if (ns > 0) {
+            sites.resize((size_t)ns);
+            ns = acvm_batch_foreign_call_sites(L.batch, sites.data(), (uint32_t)ns);
+        }
+        if (ns < 0) { fail(ns, "foreign-call sites"); return false; }
+        sites.resize(std::min(sites.size(), (size_t)ns));
+        return true;
+    };
+    auto name_of = [&](const acvm_foreign_call_site_t &s, uint32_t round) {
+        char fn[65] = {0};
+        memcpy(fn, s.function, 64);
+        return "lane " + std::to_string(L.index) + ", tile " + std::to_string(tile_index) + ", round " + std::to_string(round) + ", site (opcode " +
+               std::to_string(s.opcode_index) + ", brillig index " + std::to_string(s.brillig_index) + ", '" + fn + "')";
+    };
+    for (uint32_t round = 0; !L.rc; round++) {
+        if (!list_sites()) break;
+        sites.erase(std::remove_if(sites.begin(), sites.end(), [&](const acvm_foreign_call_site_t &s) { return std::find(declined.begin(), declined.end(), key_of(s)) != declined.end(); }),
+                    sites.end());
+        if (sites.empty()) break;
+        if (round >= max_rounds) {  // the cap: what still waits is reported, and exported as RequiresForeignCall
+            for (const acvm_foreign_call_site_t &s : sites) L.fc.rows_left_waiting += s.n_waiting;
+            break;
+        }
+        L.fc.rounds++;
+        uint64_t resumed = 0;
+        const std::vector<acvm_foreign_call_site_t> asked = sites;  // (list_sites below reuses `sites`)
+        for (const acvm_foreign_call_site_t &s : asked) {
+            const uint32_t n_rows = s.n_waiting;
+            // ---- the inputs of the site's list into the lane's scratch: the sizing call, then the columns
+            acvm_foreign_call_inputs_desc_t d{};
+            d.opcode_index = s.opcode_index;
+            d.brillig_index = s.brillig_index;
+            d.n_rows = n_rows;
+            d.encoding = H.in_encoding;
+            d.layout = H.in_layout;
+            uint32_t longest = 0;
+            if (int rc = acvm_batch_foreign_call_inputs_device(L.batch, &d, &longest)) { fail(rc, "foreign-call inputs of " + name_of(s, round)); break; }
+            NodeForeignInputs sc;
+            if (!node_foreign_inputs_scratch(n_rows, s.n_inputs, longest, in_size, &sc) || !grow_device(&L.d_fc, &L.fc_cap, sc.bytes)) {
+                fail_text(ACVM_E_NOMEM, "no device memory for the foreign-call inputs of " + name_of(s, round));
+                break;
+            }
+            d.n_columns = longest;
+            d.d_instances = (uint32_t *)(L.d_fc + sc.o_rows);
+            d.d_lens = (uint32_t *)(L.d_fc + sc.o_lens);
+            d.d_values = longest ? L.d_fc + sc.o_values : nullptr;
+            d.d_mask = longest ? L.d_fc + sc.o_mask : nullptr;
+            if (int rc = acvm_batch_foreign_call_inputs_device(L.batch, &d, nullptr)) { fail(rc, "foreign-call inputs of " + name_of(s, round)); break; }
+            const uint8_t *base = L.d_fc;
+            if (host) {  // (the inputs call returned after the batch's stream was waited for)
+                L.h_fc.resize((size_t)sc.bytes);
+                hipError_t e = hipSuccess;
+                const std::pair<uint64_t, uint64_t> parts[4] = {{sc.o_rows, sc.rows_bytes}, {sc.o_lens, sc.lens_bytes}, {sc.o_values, sc.values_bytes}, {sc.o_mask, sc.mask_bytes}};
+                for (const auto &part : parts)
+                    if (e == hipSuccess && part.second) e = hipMemcpyAsync(L.h_fc.data() + part.first, L.d_fc + part.first, (size_t)part.second, hipMemcpyDeviceToHost, L.copy);
+                if (e == hipSuccess) e = hipStreamSynchronize(L.copy);
+                if (e != hipSuccess) { fail_text(ACVM_E_DEVICE, std::string("download of the foreign-call inputs: ") + hipGetErrorString(e)); break; }
+                own_d2h += sc.rows_bytes + sc.lens_bytes + sc.values_bytes + sc.mask_bytes;
+                base = L.h_fc.data();
+            }
+            // ---- the handler
+            acvm_node_foreign_round_t in{};
+            in.lane = L.index;
+            in.device = L.device;
+            in.tile = tile_index;
+            in.round = round;
+            in.site = s;
+            in.n_rows = n_rows;
+            in.max_values = longest;
+            in.row_base = row_base;
+            in.rows = (const uint32_t *)(base + sc.o_rows);
+            in.lens = (const uint32_t *)(base + sc.o_lens);
+            in.values = base + sc.o_values;
+            in.mask = base + sc.o_mask;
+            acvm_node_foreign_answer_t out{};
+            const double t0 = now_ms();
+            const int returned = H.fn(H.user, &in, &out);
+            L.fc.handler_ms += now_ms() - t0;
+            L.fc.handler_calls++;
+            int abort_rc = 0;
+            const NodeForeignVerdict verdict = node_foreign_verdict(returned, &abort_rc);
+            if (verdict == NODE_FOREIGN_ABORT) { fail_text(abort_rc, "the foreign-call handler returned " + std::to_string(returned) + " for " + name_of(s, round)); break; }
+            if (hipSetDevice(L.device) != hipSuccess) { fail_text(ACVM_E_DEVICE, "hipSetDevice behind the foreign-call handler"); break; }  // (whatever the handler made current)
+            if (verdict == NODE_FOREIGN_DECLINED) {
+                declined.push_back(key_of(s));
+                L.fc.rows_declined += n_rows;
+                continue;
+            }
+            // ---- the answer: from host memory it goes up into the lane's scratch first; then the one resolve path
+            acvm_foreign_call_answers_rows_desc_t a{};
+            a.opcode_index = s.opcode_index;
+            a.brillig_index = s.brillig_index;
+            a.n_rows = n_rows;
+            a.n_values = out.n_values;
+            a.is_array = out.is_array;
+            a.lens = out.lens;
+            a.encoding = out.encoding;
+            a.layout = out.layout;
+            a.n_columns = out.n_columns;
+            a.stride = out.stride;
+            a.d_values = out.values;
+            a.d_lens = out.row_lens;
+            a.d_answered = out.answered;
+            if (host) {
+                NodeForeignAnswer as;
+                std::string text;
+                if (int rc = node_foreign_answer_scratch(&out, n_rows, &as, &text)) { fail_text(rc, "the answer for " + name_of(s, round) + ": " + text); break; }
+                if (!grow_device(&L.d_fc_ans, &L.fc_ans_cap, as.bytes)) { fail_text(ACVM_E_NOMEM, "no device memory for the answer for " + name_of(s, round)); break; }
+                hipError_t e = hipSuccess;
+                if (as.values_bytes) e = hipMemcpyAsync(L.d_fc_ans + as.o_values, out.values, (size_t)as.values_bytes, hipMemcpyHostToDevice, L.copy);
+                if (e == hipSuccess && as.lens_bytes) e = hipMemcpyAsync(L.d_fc_ans + as.o_lens, out.row_lens, (size_t)as.lens_bytes, hipMemcpyHostToDevice, L.copy);
+                if (e == hipSuccess && as.answered_bytes) e = hipMemcpyAsync(L.d_fc_ans + as.o_answered, out.answered, (size_t)as.answered_bytes, hipMemcpyHostToDevice, L.copy);
+                if (e == hipSuccess) e = hipStreamSynchronize(L.copy);  // (the handler's memory is read until here)
+                if (e != hipSuccess) { fail_text(ACVM_E_DEVICE, std::string("upload of the foreign-call answer: ") + hipGetErrorString(e)); break; }
+                own_h2d += as.values_bytes + as.lens_bytes + as.answered_bytes;
+                a.d_values = as.values_bytes ? L.d_fc_ans + as.o_values : nullptr;
+                a.d_lens = out.row_lens ? (const uint32_t *)(L.d_fc_ans + as.o_lens) : nullptr;
+                a.d_answered = out.answered ? L.d_fc_ans + as.o_answered : nullptr;
+            }
+            if (int rc = acvm_batch_resolve_foreign_calls_device_rows(L.batch, &a)) { fail(rc, "the answer for " + name_of(s, round)); break; }
+            // the rows the answer resumed: the site's n_resolved (host only)
+            if (!list_sites()) break;
+            uint32_t now_resolved = 0;
+            for (const acvm_foreign_call_site_t &q : sites)
+                if (key_of(q) == key_of(s)) now_resolved = q.n_resolved;
+            const uint32_t answered = now_resolved > s.n_resolved ? now_resolved - s.n_resolved : 0u;
+            L.fc.rows_answered += answered;
+            L.fc.rows_declined += n_rows - std::min(n_rows, answered);
+            resumed += answered;
+        }
+        if (L.rc || !resumed) break;  // nobody resumes: no further solve
+        const int rc = acvm_batch_solve(L.batch);
+        if (rc < 0) { fail(rc, "solve behind the foreign-call round " + std::to_string(round) + " of tile " + std::to_string(tile_index)); break; }
+        acvm_stats_t st;
+        acvm_batch_stats(L.batch, &st);
+        L.device_ms += st.solve_device_ms;
+    }
+    uint64_t h2d1 = h2d0, d2h1 = d2h0;
+    acvm_debug_foreign_call_stats(L.batch, &h2d1, &d2h1, nullptr, nullptr, nullptr);
+    L.fc.h2d_bytes += h2d1 - h2d0 + own_h2d;
+    L.fc.d2h_bytes += d2h1 - d2h0 + own_d2h;
+    L.io_h2d += h2d1 - h2d0 + own_h2d;
+    L.io_d2h += d2h1 - d2h0 + own_d2h;
+}
+
 void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, acvm_result_t *results, uint8_t *kept, uint8_t *kept_assigned,
                    uint8_t *digests) {
     const double t_begin = now_ms();
@@ -213,6 +414,7 @@ void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last
     L.device_ms = L.h2d_wait_ms = L.export_ms = 0;
     L.tiles = L.exact_instances = 0;
     L.not_solved = 0;
+    L.fc = acvm_node_foreign_stats_t{};
     auto fail = [&](int rc, const std::string &what) { if (!L.rc) { L.rc = rc; L.error = what + ": " + acvm_last_error(); } };
     if (hipSetDevice(L.device) != hipSuccess) { fail(ACVM_E_DEVICE, "hipSetDevice"); return; }
     const uint32_t tile = node->tile, n_keep = (uint32_t)node->keep.size();
@@ -331,6 +533,8 @@ void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last
         L.device_ms += st.solve_device_ms;
         L.exact_instances += st.n_slow_instances;
         L.tiles++;
+        foreign_rounds(node, L, k, node_foreign_row_base(false, first, k, tile));  // (no handler: nothing)
+        if (L.rc) break;
         const double t1 = now_ms();
         // the kept witnesses of the PREVIOUS tile: their copy ran on the download stream beside this solve
         if (!harvest()) break;
@@ -397,6 +601,7 @@ void run_lane_device_body(acvm_node *node, DeviceLane &L, const NodeLaneIo &lane
     L.device_ms = L.h2d_wait_ms = L.export_ms = 0;
     L.tiles = L.exact_instances = 0;
     L.not_solved = 0;
+    L.fc = acvm_node_foreign_stats_t{};
     io->n_selected = io->not_solved = 0;
     auto fail = [&](int rc, const std::string &what) { if (!L.rc) { L.rc = rc; L.error = what + ": " + acvm_last_error(); } };
     auto fail_hip = [&](const char *what, hipError_t e) { if (!L.rc) { L.rc = ACVM_E_DEVICE; L.error = std::string(what) + ": " + hipGetErrorString(e); } };
@@ -451,6 +656,8 @@ void run_lane_device_body(acvm_node *node, DeviceLane &L, const NodeLaneIo &lane
         L.device_ms += st.solve_device_ms;
         L.exact_instances += st.n_slow_instances;
         L.tiles++;
+        foreign_rounds(node, L, k, node_foreign_row_base(true, 0, k, node->tile));  // (no handler: nothing)
+        if (L.rc) break;
         const double t1 = now_ms();
         if (k > 0) {
             ExactOutcome o;
@@ -543,6 +750,7 @@ acvm_node_t *acvm_node_new(const acvm_circuit_t *c, const acvm_bb_solver_t *solv
     for (uint32_t &w : node->keep)
         if (w >= acvm_circuit_num_witnesses(c)) w = 0xFFFFFFFFu;
     node->flags = opts ? opts->batch_flags : 0;
+    node->has_solver = solver != nullptr;
     std::vector<int> devices;
     // n_devices == 0 selects every visible device and `devices` is not read (it holds n_devices entries: none)
     const bool listed = opts && opts->n_devices && opts->devices;
@@ -576,6 +784,7 @@ acvm_node_t *acvm_node_new(const acvm_circuit_t *c, const acvm_bb_solver_t *solv
     std::vector<std::thread> th;
     for (size_t i = 0; i < devices.size(); i++) {
         node->lanes[i].device = devices[i];
+        node->lanes[i].index = (uint32_t)i;
         th.emplace_back([&, i] {
             DeviceLane &L = node->lanes[i];
             try {  // (nothing leaves a thread: std::terminate is not an error code)
@@ -631,6 +840,7 @@ uint32_t acvm_node_num_devices(const acvm_node_t *n) { return n ? (uint32_t)n->l
 long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, acvm_result_t *results, uint8_t *kept_be32, uint8_t *kept_assigned,
                           uint8_t *digests32) try {
     if (!n || (n_instances && !n->ids.empty() && !values_be32)) return set_err(ACVM_E_INVALID, "null argument");
+    RunningCall running(n);
     const double t0 = now_ms();
     const size_t D = n->lanes.size();
     // contiguous split, multiples of 64 instances per device except the last
@@ -653,6 +863,7 @@ long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *v
 // The device form: every lane is checked (node_io_plan.cpp) before any lane starts, then each lane's thread walks its own rows.
 long long acvm_node_solve_device(acvm_node_t *n, acvm_node_lane_io_t *lanes, uint32_t n_lanes) try {
     if (!n) return set_err(ACVM_E_INVALID, "null argument");
+    RunningCall running(n);
     const double t0 = now_ms();
     const size_t D = n->lanes.size();
     std::vector<NodeLaneIo> checked;
@@ -675,6 +886,20 @@ int acvm_debug_node_io_bytes(const acvm_node_t *n, uint32_t lane, uint64_t *h2d,
     if (!n || lane >= n->lanes.size()) return set_err(ACVM_E_INVALID, "no such lane");
     if (h2d) *h2d = n->lanes[lane].io_h2d;
     if (d2h) *d2h = n->lanes[lane].io_d2h;
+    return 0;
+}
+
+int acvm_node_set_foreign_call_handler(acvm_node_t *n, const acvm_node_foreign_handler_t *h) try {
+    if (!n) return set_err(ACVM_E_INVALID, "null argument");
+    std::string text;
+    if (int rc = node_foreign_check_handler(h, n->has_solver, n->running.load() != 0, &text)) return set_err(rc, text);
+    n->has_handler = h != nullptr;
+    n->handler = h ? *h : acvm_node_foreign_handler_t{};
+    return 0;
+} ABI_CATCH
+int acvm_node_foreign_stats(acvm_node_t *n, uint32_t lane, acvm_node_foreign_stats_t *out) {
+    if (!n || !out || lane >= n->lanes.size()) return set_err(ACVM_E_INVALID, !n || !out ? "null argument" : "no such lane");
+    *out = n->lanes[lane].fc;
     return 0;
 }
 

@@ -454,8 +454,8 @@ int acvm_batch_resolve_foreign_call(acvm_batch_t *b, uint32_t instance, uint32_t
  * acvm_debug_foreign_call_stats: the cumulative bytes BOTH forms of the round trip copied host-to-device / device-to-host for this handle, and the
  * device times (HIP events) of the last inputs and append kernels, and the device bytes the result store's tables hold right now (they grow by one
  * result per column and round, however many calls answer a round's rows). Each pointer may be NULL.
- * Not here: per-row result shapes (the per-instance call); a node form; an asynchronous variant; answering by a device-side instance list (the
- * host must know which lanes resume).
+ * The node form is acvm_node_set_foreign_call_handler below.
+ * Not here: an asynchronous variant; rows whose outputs differ in number or kind (the per-instance call); parking a waiting tile beside the next one.
  */
 typedef struct {
     uint32_t opcode_index, brillig_index;
@@ -489,6 +489,39 @@ typedef struct {
     const void *d_values;            /* the row's values back to back in columns 0 .. total - 1 */
 } acvm_foreign_call_answers_desc_t;
 int acvm_batch_resolve_foreign_calls_device(acvm_batch_t *b, const acvm_foreign_call_answers_desc_t *d);
+/*
+ * acvm_batch_resolve_foreign_calls_device_rows: the same call with PER-ROW answers -- what a handler per instance can do (pwg/mod.rs:214-228 takes one
+ * ForeignCallResult of any shape per instance): a slice-returning oracle (a HeapVector output) returns a different length per row, and a GPU oracle
+ * finds an entry for some rows and not for others. The descriptor is acvm_foreign_call_answers_desc_t plus two optional DEVICE columns:
+ *   d_lens      [n_rows][n_values] row-major: the number of values of array output k of row i (ignored where is_array[k] == 0). NULL: the host
+ *               `lens` hold for every row. The values of row i stay back to back in columns 0 .. total_i - 1.
+ *   d_answered  [n_rows]: 0 = the row is NOT answered -- it keeps waiting, n_resolved does not count it, nothing is appended for it and a later call
+ *               of the same round may answer it; nonzero = answered. NULL: every row is answered.
+ *   - With d_lens a sizing launch runs before anything is written: the largest total among the answered rows, summed in 64 bits (four bytes come
+ *     back). n_columns below it is ACVM_E_INVALID, the message states the needed width; a total of 2^31 or more is refused the same way. The result
+ *     store is sized from that largest total.
+ *   - With d_answered the call downloads the mask (n_rows bytes): the host must know which lanes resume. Without it nothing more comes back than
+ *     from acvm_batch_resolve_foreign_calls_device. The mask is read once, into memory of the handle: the rows judged and the rows appended are the
+ *     same whatever the caller does to d_answered meanwhile. d_lens must stay unchanged until the call returns.
+ *   - The refusals are those of acvm_batch_resolve_foreign_calls_device, the handle left as it was; a row that was already answered since the last
+ *     solve AND is marked answered again is ACVM_E_STATE, an already answered row that is masked out is fine. The host `lens` are not read, and may be NULL,
+ *     when d_lens is given.
+ *   - The per-instance call, acvm_batch_resolve_foreign_calls_device and this call may be mixed on one handle in any order.
+ */
+typedef struct {
+    uint32_t opcode_index, brillig_index;
+    uint32_t first_row, n_rows;
+    uint32_t n_values;               /* outputs of one ForeignCallResult; which of them are arrays is the same for every row */
+    const uint8_t *is_array;         /* HOST [n_values] */
+    const uint32_t *lens;            /* HOST [n_values]: the lengths of every row when d_lens is NULL */
+    uint32_t encoding, layout;
+    uint32_t n_columns;
+    uint64_t stride;
+    const void *d_values;            /* row i's values back to back in columns 0 .. total_i - 1 */
+    const uint32_t *d_lens;          /* DEVICE [n_rows][n_values], may be NULL */
+    const uint8_t *d_answered;       /* DEVICE [n_rows], may be NULL */
+} acvm_foreign_call_answers_rows_desc_t;
+int acvm_batch_resolve_foreign_calls_device_rows(acvm_batch_t *b, const acvm_foreign_call_answers_rows_desc_t *d);
 int acvm_debug_foreign_call_stats(const acvm_batch_t *b, uint64_t *h2d_bytes, uint64_t *d2h_bytes, double *inputs_kernel_ms, double *append_kernel_ms,
                                   uint64_t *store_bytes);
 /* enable per-kernel HIP-event timing of the level kernels (small overhead) */
@@ -862,6 +895,74 @@ typedef struct {
 } acvm_node_lane_io_t;
 long long acvm_node_solve_device(acvm_node_t *n, acvm_node_lane_io_t *lanes, uint32_t n_lanes); /* n_lanes == acvm_node_num_devices */
 int acvm_debug_node_io_bytes(const acvm_node_t *n, uint32_t lane, uint64_t *h2d, uint64_t *d2h);
+/*
+ * A foreign-call handler of the node: the round trip of acvm_js/src/execute.rs:109-113 -- while the status is RequiresForeignCall, ask the handler,
+ * resolve_pending_foreign_call (pwg/mod.rs:203-228), solve again -- once per TILE and site instead of once per instance. Both node forms run the
+ * same loop behind a tile's solve and before anything of that tile is exported:
+ *   while the tile's handle lists sites (acvm_batch_foreign_call_sites) and the round is below max_rounds: for every site ascending, the inputs of
+ *   its waiting list are written into scratch of the lane (acvm_batch_foreign_call_inputs_device, in the handler's in_encoding / in_layout, dense:
+ *   n_rows x max_values), the handler is called, and its answer is resolved through acvm_batch_resolve_foreign_calls_device_rows; after all sites
+ *   of the round the tile is solved again. The tile's results, kept witnesses, outcome columns and digests are then those of the last solve.
+ *   - The handler returns 0: answered (optionally per row: row_lens as d_lens, answered as d_answered of the per-row call; a row whose `answered`
+ *     byte is 0 keeps waiting and is listed again in the next round). 1: the site is declined for this tile -- its rows stay RequiresForeignCall
+ *     (a reference status: the caller stopped answering) and the site is not asked about again in this tile. A negative value aborts the node
+ *     call: it returns that value and the error text names lane, tile and site; the node stays usable. Any other value is ACVM_E_INVALID.
+ *   - A round that resumed no row (every site declined or fully masked out) ends the loop: no further solve runs. Rows that still wait when
+ *     max_rounds rounds have run are counted in rows_left_waiting.
+ *   - ACVM_SPACE_DEVICE: every pointer of `in` and values / row_lens / answered of `out` are memory of the lane's device, which is the current
+ *     device of the calling thread. The handler's own GPU work must be complete when it returns (the resolve runs on the batch's stream), and its
+ *     answer buffers must stay valid until it is next called on that lane or the node call returns. No value crosses PCIe: per site and round
+ *     the round trip moves the 8 bytes per waiting row of the batch-wide calls, the mask bytes when `answered` is given, and a few words.
+ *     ACVM_SPACE_HOST: the node copies rows, lens, values and mask down into host buffers of its own (valid during the handler's call) and
+ *     uploads the answer's values, row_lens and answered into its scratch; the same device calls follow.
+ *   - The handler runs on the lane's host thread; different lanes call it concurrently: it must be thread-safe. It must not start a node call.
+ *   - Scratch is grown on demand; a failed allocation ends the lane with ACVM_E_NOMEM and leaves the handle reusable.
+ *   - acvm_node_set_foreign_call_handler(n, NULL): no handler, the node returns rows in RequiresForeignCall as without this call. Refused, nothing
+ *     changed: ACVM_E_INVALID for a null fn, an unknown space, in_encoding or in_layout; ACVM_E_UNSUPPORTED for a node created with a caller's
+ *     BlackBoxFunctionSolver (the device resolve refuses such handles); ACVM_E_STATE while a node call runs.
+ *   - acvm_node_foreign_stats: the lane's loop during the last node call. The bytes are those of the batch-wide calls
+ *     (acvm_debug_foreign_call_stats) plus the node's own copies in host space.
+ * Not here: an asynchronous variant; parking a waiting tile beside the next one (a tile waits for its handler); a handler on a node with a
+ * black-box solver.
+ */
+enum { ACVM_SPACE_DEVICE = 0, ACVM_SPACE_HOST = 1 };
+typedef struct {
+    uint32_t lane; int device;          /* index in the node's device list, its HIP device (current on the calling thread) */
+    uint32_t tile, round;               /* tile of the lane, 0-based round of that tile */
+    acvm_foreign_call_site_t site;      /* n_waiting == n_rows */
+    uint32_t n_rows, max_values;        /* rows of the site's list in this tile, the longest row */
+    uint64_t row_base;                  /* caller's number of row i = row_base + rows[i]:
+                                           acvm_node_solve: global instance number, acvm_node_solve_device: the lane's row number */
+    const uint32_t *rows;               /* [n_rows] ascending */
+    const uint32_t *lens;               /* [n_rows][n_inputs] */
+    const void *values; const uint8_t *mask;   /* n_rows x max_values, in the handler's in_encoding / in_layout, dense */
+} acvm_node_foreign_round_t;
+typedef struct {                        /* filled by the handler (zeroed before the call) */
+    uint32_t n_values; const uint8_t *is_array; const uint32_t *lens;   /* HOST, as in acvm_foreign_call_answers_desc_t */
+    uint32_t encoding, layout, n_columns; uint64_t stride;
+    const void *values;                 /* in the handler's memory space */
+    const uint32_t *row_lens;           /* optional [n_rows][n_values], same space */
+    const uint8_t *answered;            /* optional [n_rows], same space */
+} acvm_node_foreign_answer_t;
+typedef int (*acvm_node_foreign_fn)(void *user, const acvm_node_foreign_round_t *in, acvm_node_foreign_answer_t *out);
+typedef struct {
+    acvm_node_foreign_fn fn; void *user;
+    uint32_t space;                     /* ACVM_SPACE_DEVICE: every pointer of `in` and the three data pointers of `out` are memory of the lane's device;
+                                           ACVM_SPACE_HOST: host memory (the node copies inputs down and answers up) */
+    uint32_t in_encoding, in_layout;
+    uint32_t max_rounds;                /* per tile; 0 = 256 */
+} acvm_node_foreign_handler_t;
+typedef struct {                        /* one lane, the last node call */
+    uint32_t rounds;                    /* rounds in which the handler was asked, over all tiles */
+    uint32_t handler_calls;
+    uint64_t rows_answered;             /* rows resumed by an answer */
+    uint64_t rows_declined;             /* rows of declined sites, and rows an `answered` column left out */
+    uint64_t rows_left_waiting;         /* rows still waiting when a tile reached max_rounds */
+    double handler_ms;                  /* wall clock inside the handler */
+    uint64_t h2d_bytes, d2h_bytes;      /* of the round trips */
+} acvm_node_foreign_stats_t;
+int acvm_node_set_foreign_call_handler(acvm_node_t *n, const acvm_node_foreign_handler_t *h);   /* NULL: none */
+int acvm_node_foreign_stats(acvm_node_t *n, uint32_t lane, acvm_node_foreign_stats_t *out);
 /* host-only probes of the lanes' placement logic: a sysfs cpulist ("0-15,32-47") into CPU numbers (returns how many; the first `cap` are
  * written), and the NUMA node + local CPUs of PCI device `bus_id` under `pci_root` (normally /sys/bus/pci/devices) */
 int acvm_debug_cpulist(const char *text, uint32_t *cpus, uint32_t cap);

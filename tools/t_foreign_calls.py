@@ -5,7 +5,9 @@ the device times of the two batch-wide kernels (HIP events). The oracle is the s
 round trip itself is what is timed: an echo -- 'invert' answers its input, 'double' answers (its input, 0); the circuit constrains neither. On the
 device that is no kernel at all: the Montgomery-256 witness-major column the inputs were written to is handed back as the first answer column, beside
 a column of zeros. The per-instance form's answers are made by the host loop.
-    python tools/t_foreign_calls.py [--log2-b 16] [--rounds 5] [--tail 40] [--forms instance,device]
+The form `rows` is the device form answered through acvm_batch_resolve_foreign_calls_device_rows with both of its device columns given (a length
+column, read by the sizing launch, and a mask of ones, downloaded): what the per-row call costs on top of the one-shape call for the same answers.
+    python tools/t_foreign_calls.py [--log2-b 16] [--rounds 5] [--tail 40] [--forms instance,device,rows]
 With ACVM_AMD_LIB pointing at a build without the device form, --forms instance measures that build's per-instance form alone (A-B runs)."""
 import argparse
 import ctypes as C
@@ -77,7 +79,11 @@ kernel_ms = {"inputs": [], "append": []}
 d_cols = acvm_amd.DeviceBuffer(data=bytes(2 * B * 32))  # two witness-major columns of Montgomery-256 elements; the second stays zero
 
 
-def answer_on_device():
+d_row_lens = acvm_amd.DeviceBuffer(data=bytes(2 * B * 4))
+d_answered = acvm_amd.DeviceBuffer(data=bytes([1]) * B)
+
+
+def answer_on_device(per_row=False):
     n = 0
     for s in batch.foreign_call_sites():
         rows = s["n_waiting"]
@@ -88,8 +94,12 @@ def answer_on_device():
         kernel_ms["inputs"].append(fc_stats()["inputs_kernel_ms"])
         k = N_OUT[s["function"]]
         # the echo oracle costs no kernel: the column the inputs were written to IS the first answer column, the zero column the second
-        batch.resolve_foreign_calls_device(s["opcode_index"], s["brillig_index"], [None] * k, d_cols.ptr, n_rows=rows, encoding=acvm_amd.ENC_MONT256_LE,
-                                           layout=acvm_amd.LAYOUT_WITNESS_MAJOR, n_columns=k, stride=B)
+        if per_row:
+            batch.resolve_foreign_calls_device_rows(s["opcode_index"], s["brillig_index"], [None] * k, d_cols.ptr, n_rows=rows, encoding=acvm_amd.ENC_MONT256_LE,
+                                                    layout=acvm_amd.LAYOUT_WITNESS_MAJOR, n_columns=k, stride=B, d_lens=d_row_lens.ptr, d_answered=d_answered.ptr)
+        else:
+            batch.resolve_foreign_calls_device(s["opcode_index"], s["brillig_index"], [None] * k, d_cols.ptr, n_rows=rows, encoding=acvm_amd.ENC_MONT256_LE,
+                                               layout=acvm_amd.LAYOUT_WITNESS_MAJOR, n_columns=k, stride=B)
         kernel_ms["append"].append(fc_stats()["append_kernel_ms"])
         n += rows
     return n
@@ -116,7 +126,7 @@ def stats(xs):
     return f"median {xs[len(xs) // 2]:10.3f} (min {xs[0]:10.3f} - max {xs[-1]:10.3f})"
 
 
-forms = {"instance": answer_per_instance, "device": answer_on_device}
+forms = {"instance": answer_per_instance, "device": answer_on_device, "rows": lambda: answer_on_device(per_row=True)}
 todo = [f for f in args.forms.split(",") if f]
 handles = {f: acvm_amd.Batch(gc, B, ids) for f in todo}
 maps = {}
@@ -135,7 +145,7 @@ print(f"relevel circuit, {args.tail}-gate tail, B = {B}, two calls per instance,
 for f in todo:
     up, down = moved[f]
     print(f"  {f:8s} form: wall ms {stats(wall[f])} | per drive {up} B host-to-device, {down} B device-to-host" + ("" if has_stats else " (this build does not count)"))
-if "device" in todo:
+if "device" in todo or "rows" in todo:
     print(f"  fc_inputs_kernel ms {stats(kernel_ms['inputs'])} | fc_append_kernel ms {stats(kernel_ms['append'])} (HIP events, one site of {B} rows per launch)")
 d_cols.free()
 for h in handles.values():
