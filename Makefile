@@ -9,7 +9,8 @@
 #               refusal order, the width behind the sizing launch: tools/asan/foreign_rows_plan_host_test -- with the per-row append of the result
 #               store run on the host: tools/asan/foreign_rows_store_host_test (hipcc, host side sanitized; tests/test_foreign_rows_on_host.py), and the
 #               host-only decisions of the node's foreign-call loop -- handler checks, row_base, scratch sizes, round cap:
-#               tools/asan/node_foreign_plan_host_test (tests/test_foreign_rows_on_host.py)
+#               tools/asan/node_foreign_plan_host_test (tests/test_foreign_rows_on_host.py), and the masked import's addressing arithmetic and
+#               plan: tools/asan/import_mask_host_test (hipcc, host side sanitized; tests/test_import_mask_on_host.py)
 CXX ?= g++
 ASAN_FLAGS = -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wno-sign-compare
 ASAN_SRCS = tools/asan/fuzz_driver.cpp acvm_amd/csrc/circuit.cpp acvm_amd/csrc/plan.cpp acvm_amd/csrc/tuning.cpp acvm_amd/csrc/schedule.cpp acvm_amd/csrc/schedule_check.cpp
@@ -20,7 +21,7 @@ FOREIGN_ROWS_SRCS = tools/foreign_rows_plan_host_test.cpp acvm_amd/csrc/foreign_
 NODE_FOREIGN_SRCS = tools/node_foreign_plan_host_test.cpp acvm_amd/csrc/node_foreign_plan.cpp acvm_amd/csrc/import_plan.cpp
 HIPCC ?= /opt/rocm/bin/hipcc
 asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigned_view_host_test tools/asan/node_io_plan_host_test tools/asan/foreign_plan_host_test \
-      tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test
+      tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test tools/asan/import_mask_host_test
 tools/asan/fuzz_driver: $(ASAN_SRCS) $(wildcard acvm_amd/csrc/*.hpp)
 	$(CXX) $(ASAN_FLAGS) -o $@ $(ASAN_SRCS) -lz
 tools/asan/import_plan_host_test: $(PLAN_SRCS) acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
@@ -33,6 +34,8 @@ tools/asan/foreign_rows_plan_host_test: $(FOREIGN_ROWS_SRCS) acvm_amd/csrc/forei
 	$(CXX) $(ASAN_FLAGS) -o $@ $(FOREIGN_ROWS_SRCS)
 tools/asan/foreign_rows_store_host_test: tools/foreign_rows_store_host_test.hip acvm_amd/csrc/foreign_store.hpp
 	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/foreign_rows_store_host_test.hip
+tools/asan/import_mask_host_test: tools/import_mask_host_test.hip acvm_amd/csrc/import_plan.cpp acvm_amd/csrc/import_mask.hpp acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
+	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/import_mask_host_test.hip acvm_amd/csrc/import_plan.cpp
 tools/asan/node_foreign_plan_host_test: $(NODE_FOREIGN_SRCS) acvm_amd/csrc/node_foreign_plan.hpp acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
 	$(CXX) $(ASAN_FLAGS) -o $@ $(NODE_FOREIGN_SRCS)
 tools/asan/assigned_view_host_test: tools/assigned_view_host_test.cpp acvm_amd/csrc/assigned_view.hpp

@@ -7,6 +7,7 @@ results()/witness_map(). There is no CPU fallback: importing the solver without 
 creating a batch without a gfx950 device, raises.
 """
 import ctypes as C
+import functools
 import os
 
 from . import acir  # noqa: F401  (data model + wire format)
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
     "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
     "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
+    "acvm_batch_import_device_masked", "acvm_batch_set_initial_witness_masked", "acvm_debug_import_missing",
     "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
     "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
     "acvm_node_solve_device", "acvm_debug_node_io_bytes",
@@ -459,6 +461,11 @@ def lib():
         L.acvm_batch_import_device_parts.argtypes = [C.c_void_p, C.POINTER(ImportPart), C.c_uint32]
         L.acvm_debug_import_list_copies.restype = C.c_uint64
         L.acvm_debug_import_list_copies.argtypes = [C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_masked"):
+        L.acvm_batch_import_device_masked.argtypes = [C.c_void_p, C.POINTER(ImportDesc), C.c_void_p, C.c_void_p]
+        L.acvm_batch_set_initial_witness_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.acvm_debug_import_missing.restype = C.c_uint64
+        L.acvm_debug_import_missing.argtypes = [C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1074,6 +1081,17 @@ class Batch:
             desc.columns, desc.n_columns = arr, len(cols) if n_columns is None else n_columns
         return desc, arr
 
+    def _with_d_assigned(unmasked):
+        """import_device(..., d_assigned=None): the keyword routes to import_device_masked. The positional parameters stay exactly those of the
+        unmasked call -- solve(then_import_desc=...) and import_device_parts take them as a dict, and d_assigned is none of theirs."""
+        @functools.wraps(unmasked)
+        def import_device(self, d_ptr, *args, d_assigned=None, **keywords):
+            if d_assigned is None:
+                return unmasked(self, d_ptr, *args, **keywords)
+            return self.import_device_masked(d_ptr, d_assigned, *args, **keywords)
+        return import_device
+
+    @_with_d_assigned
     def import_device(self, d_ptr: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, columns=None, n_columns=None, stride=0):
         """The initial witnesses read from device memory at d_ptr (acvm_batch_import_device), the mirror image of export_device: 32 bytes per
         element in `encoding` (ENC_U8 .. ENC_U128: the integer's 1 .. 16 bytes, little-endian, d_ptr aligned to that size), element (instance i, column c) where `layout` and `stride` (in elements, 0 = dense) put it; columns: per initial
@@ -1081,6 +1099,33 @@ class Batch:
         buffer's width in columns (default: len(columns)). The defaults are set_initial_witness_device."""
         desc, _keep = self._import_desc(encoding, layout, columns, n_columns, stride)
         _check(lib().acvm_batch_import_device(self._h, C.byref(desc), d_ptr))
+
+    del _with_d_assigned
+
+    def import_device_masked(self, d_ptr: int, d_assigned: int, encoding=ENC_BE32, layout=LAYOUT_INSTANCE_MAJOR, columns=None, n_columns=None, stride=0):
+        """import_device for instances that do not all hold every initial witness (acvm_batch_import_device_masked). d_assigned: device pointer of
+        one byte per element in the values' layout, stride and column list -- what export_device writes into its d_assigned: 0 = the instance does
+        not hold that initial witness, 1 = it does. Any other byte raises, and the batch is then without initial witnesses until another import.
+        import_device(..., d_assigned=ptr) is this call; d_assigned=None is import_device."""
+        if d_assigned is None:
+            return self.import_device(d_ptr, encoding, layout, columns, n_columns, stride)
+        desc, _keep = self._import_desc(encoding, layout, columns, n_columns, stride)
+        _check(lib().acvm_batch_import_device_masked(self._h, C.byref(desc), d_ptr, d_assigned))
+
+    def set_initial_witness_masked(self, values_be: bytes, assigned: bytes):
+        """set_initial_witness with a mask (acvm_batch_set_initial_witness_masked): assigned holds B * len(ids) bytes, instance-major, 0 = the
+        instance does not hold that initial witness (its 32 value bytes are ignored), 1 = it does."""
+        import numpy as np
+        buf, mask = np.frombuffer(values_be, dtype=np.uint8), np.frombuffer(bytes(assigned), dtype=np.uint8)
+        if buf.size != self.B * len(self.ids) * 32:
+            raise ValueError("initial witness buffer has the wrong size")
+        if mask.size != self.B * len(self.ids):
+            raise ValueError("assigned needs one byte per instance and initial witness")
+        _check(lib().acvm_batch_set_initial_witness_masked(self._h, buf.ctypes.data, mask.ctypes.data))
+
+    def import_missing(self) -> int:
+        """instances with at least one absent input after the last import (acvm_debug_import_missing); 0 after any unmasked import"""
+        return lib().acvm_debug_import_missing(self._h)
 
     def import_device_parts(self, parts):
         """One import from several device buffers (acvm_batch_import_device_parts). parts: dicts with d_ptr, positions (which initial witnesses,

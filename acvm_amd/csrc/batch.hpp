@@ -179,6 +179,14 @@ struct acvm_batch {
     uint32_t *d_import_lists = nullptr;
     size_t import_lists_cap = 0;
     uint64_t n_import_list_copies = 0;  // (acvm_debug_import_list_copies)
+    // The missing set of acvm_batch_import_device_masked (import_mask.hpp): per instance which initial witnesses it does NOT hold, allocated by the
+    // first masked import, and the words its mask pass reports. n_missing: the instances with an absent input after the last import
+    // (acvm_debug_import_missing). While it is 0 -- no mask seen, a mask of all ones, any other import since (import_epilogue) -- nothing reads
+    // d_missing and none of the three passes of kernels_import_mask.hip is launched; acvm_batch_reset keeps it, as it keeps the rows.
+    uint32_t *d_missing = nullptr;
+    uint64_t *d_mask_result = nullptr;  // zero between masked imports: each leaves the memset for the next one behind its wait
+    uint64_t *h_mask_result = nullptr;  // pinned: where the call reads them
+    uint64_t n_missing = 0;
     // The instance -> exact-lane map of acvm_batch_export_device_list on the device: slow_index as the kernels read it (-1: generic), one word per
     // instance of the handle. slow_epoch counts the changes of slow_index (batch_schedule.cpp, batch_exact.cpp solve_stepping); the map is rebuilt ON the device
     // (a fill, then a scatter of slow_ids) when a list export finds it older than that, so nothing per instance is uploaded while events_clean holds
@@ -292,6 +300,9 @@ struct acvm_batch {
         if (d_stage) hipFree(d_stage);
         if (d_fetch) hipFree(d_fetch);
         if (d_import_lists) hipFree(d_import_lists);
+        if (d_missing) hipFree(d_missing);
+        if (d_mask_result) hipFree(d_mask_result);
+        if (h_mask_result) hipHostFree(h_mask_result);
         if (d_lane_map) hipFree(d_lane_map);
         for (uint8_t *q : d_sink)
             if (q) hipFree(q);

@@ -485,6 +485,7 @@ int solve_stepping(acvm_batch *b, bool one) {
         HIPCHK(hipMemcpyAsync(b->d_slow_ids, b->slow_ids.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(b->d_slow_start, b->slow_start.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
         launch_init_assigned(s, b->d_assigned, n_slow, b->n_words, p.n_witnesses, b->d_producer, b->d_slow_start);
+        if (b->n_missing) launch_import_missing_clear(s, b->d_missing, (uint32_t)p.initial_ids.size(), b->Bp, b->d_init_ids, b->d_slow_ids, n_slow, b->d_assigned);
         b->fc_lane.assign(n_slow, acvm_batch::FcLaneState());
         if (int rc = upload_fc_tables(b, n_slow)) return rc;
         launch_exact_init(s, exact_lanes(b, n_slow));

@@ -4,20 +4,22 @@
 // the import already ran behind the last solve (import_is_behind_solve) and the handle's state afterwards (import_epilogue).
 #include "batch_internal.hpp"
 #include "export_encode.hpp"
+#include "import_mask.hpp"
 
 static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
                   EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
               "the kernels (export_encode.hpp) and the checks (import_plan.cpp: include/acvm_amd.h) number encodings and layouts alike");
+static_assert(IMPORT_MASK_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && IMPORT_MASK_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR, "import_mask.hpp numbers the layouts as the ABI does");
 
 static ImportView import_view(const acvm_batch *b) {
     const Plan &p = b->plan();
     return ImportView{b->B, (uint32_t)p.initial_ids.size(), p.initial_ids.data(), b->reuse() ? b->init_rows.data() : p.initial_ids.data(),
                       p.n_byte_planes ? b->plane_of_input.data() : nullptr};
 }
-int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out) {
+int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out, const uint8_t *d_assigned) {
     const ImportView view = b ? import_view(b) : ImportView{};
     std::string err;
-    const int rc = import_plan_desc(b ? &view : nullptr, d, d_values, out, &err);
+    const int rc = import_plan_desc_masked(b ? &view : nullptr, d, d_values, d_assigned, out, &err);
     return rc ? set_err(rc, err) : 0;
 }
 
@@ -75,6 +77,7 @@ static void import_epilogue(acvm_batch *b, bool enqueued, bool reset_written) {
     b->next_imported = false;
     b->next_inputs = nullptr;
     if (enqueued) b->events_fresh = reset_written;
+    b->n_missing = 0;  // (every instance holds every input; a masked import says otherwise behind its mask pass: import_masked_and_wait)
     b->inputs_set = true;
     b->solved = false;
     b->stepping = false;
@@ -129,6 +132,71 @@ int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const
     if (int rc = import_plan_of(b, d, d_values, &plan)) return rc;
     return import_and_wait(b, plan);
 } ABI_CATCH
+// ---- the masked import (include/acvm_amd.h acvm_batch_import_device_masked): the value import as any other, the mask pass behind it on the
+// batch's stream, and the few words it reports read back behind the wait the call makes anyway.
+static int missing_set_ready(acvm_batch *b) {
+    const size_t words = (size_t)import_missing_words((uint32_t)b->plan().initial_ids.size()) * b->Bp;
+    if (!b->d_missing) {  // (zeroed once: a word no mask pass has written -- an instance beyond the live count -- says "holds everything")
+        HIPCHK(hipMalloc((void **)&b->d_missing, (words ? words : 1) * 4));
+        HIPCHK(hipMemset(b->d_missing, 0, (words ? words : 1) * 4));
+    }
+    if (!b->h_mask_result) HIPCHK(hipHostMalloc((void **)&b->h_mask_result, IMPORT_MASK_RESULT_WORDS * 8, hipHostMallocDefault));
+    if (!b->d_mask_result) {
+        HIPCHK(hipMalloc((void **)&b->d_mask_result, IMPORT_MASK_RESULT_WORDS * 8));
+        HIPCHK(hipMemset(b->d_mask_result, 0, IMPORT_MASK_RESULT_WORDS * 8));
+    }
+    return 0;
+}
+static int import_masked_and_wait(acvm_batch *b, const ImportPlan &plan) {
+    if (!plan.masked()) return import_and_wait(b, plan);
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = missing_set_ready(b)) return rc;  // (in front of everything: a refusal so far leaves the handle as it was)
+    if (int rc = batch_import_plan_async(b, plan, nullptr, nullptr)) return rc;
+    const ImportPlanPart &pt = plan.parts[0];  // (a descriptor's plan: one resident part)
+    const uint32_t *columns = pt.columns_at != IMPORT_NO_LIST ? b->d_import_lists + pt.columns_at : nullptr;
+    // (d_mask_result is zero here: since its allocation, or since the memset the previous masked import left behind on the stream)
+    launch_import_mask(b->stream, ImportMaskSource{plan.d_assigned, pt.layout, columns, pt.stride}, b->d_W, b->Bp, b->B, b->reuse() ? b->d_init_rows : b->d_init_ids, pt.n,
+                       b->d_byte_plane_of_input, b->d_byte_plane, b->d_missing, b->d_mask_result);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_mask_result, b->d_mask_result, IMPORT_MASK_RESULT_WORDS * 8, hipMemcpyDeviceToHost, b->stream));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const uint64_t result[IMPORT_MASK_RESULT_WORDS] = {b->h_mask_result[0], b->h_mask_result[1], b->h_mask_result[2]};
+    // the words are zeroed for the next masked import behind this one's wait: not waited for, so the memset costs the caller nothing
+    HIPCHK(hipMemsetAsync(b->d_mask_result, 0, IMPORT_MASK_RESULT_WORDS * 8, b->stream));
+    if (result[IMPORT_MASK_BAD]) {
+        // The host could not see the bytes beforehand and the rows are written: the handle is left without initial witnesses.
+        b->inputs_set = false;
+        const uint32_t j = import_mask_key_instance(result[IMPORT_MASK_BAD_KEY]), k = import_mask_key_position(result[IMPORT_MASK_BAD_KEY]);
+        return set_err(ACVM_E_INVALID, "d_assigned: " + std::to_string(result[IMPORT_MASK_BAD]) + " elements are neither 0 nor 1, the first of them instance " + std::to_string(j) +
+                                           ", position " + std::to_string(k) + " (initial witness " + std::to_string(b->plan().initial_ids[k]) +
+                                           "); the handle is left without initial witnesses");
+    }
+    b->n_missing = result[IMPORT_MASK_MISSING];
+    return 0;
+}
+int acvm_batch_import_device_masked(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values, const uint8_t *d_assigned) try {
+    ImportPlan plan;
+    if (int rc = import_plan_of(b, d, d_values, &plan, d_assigned)) return rc;
+    return import_masked_and_wait(b, plan);
+} ABI_CATCH
+// the host form: values and mask bytes through the staging buffer, then the device path -- BE32, instance-major, dense
+int acvm_batch_set_initial_witness_masked(acvm_batch_t *b, const uint8_t *values_be32, const uint8_t *assigned) try {
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    const size_t elements = (size_t)b->B * b->plan().initial_ids.size(), bytes = elements * 32;
+    if (bytes && !values_be32) return set_err(ACVM_E_INVALID, "null values");
+    if (bytes && !assigned) return set_err(ACVM_E_INVALID, "null assigned");
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = stage_reserve(b, align256(bytes) + elements)) return rc;
+    if (bytes) {
+        HIPCHK(hipMemcpyAsync(b->d_stage, values_be32, bytes, hipMemcpyHostToDevice, b->stream));
+        HIPCHK(hipMemcpyAsync(b->d_stage + align256(bytes), assigned, elements, hipMemcpyHostToDevice, b->stream));
+    }
+    ImportPlan plan = import_plan_plain((uint32_t)b->plan().initial_ids.size(), b->d_stage);
+    if (bytes) plan.d_assigned = b->d_stage + align256(bytes);
+    return import_masked_and_wait(b, plan);
+} ABI_CATCH
+uint64_t acvm_debug_import_missing(const acvm_batch_t *b) { return b ? b->n_missing : 0; }
+
 // One import from several buffers (include/acvm_amd.h): every part is checked like a descriptor, nothing is enqueued before all have passed. The
 // event reset is given to exactly one launch. A plan of parts never rides behind a solve, so this call always waits.
 int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts) try {

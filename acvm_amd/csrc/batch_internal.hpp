@@ -25,7 +25,8 @@ int event_words_new(uint32_t B, uint32_t **base, uint32_t **event, uint32_t **h_
 
 // ---- batch_import.cpp
 // an acvm_import_desc_t checked against the handle and the pointer (import_plan.cpp import_plan_desc): 0 and *out, or ACVM_E_INVALID and the error text
-int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out);
+// (d_assigned: the mask of acvm_batch_import_device_masked, import_plan_desc_masked; null: none)
+int import_plan_of(const acvm_batch *b, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out, const uint8_t *d_assigned = nullptr);
 // the plan's lists are on the device, in the handle's one list buffer (nothing to do for a plan without lists, or for the lists of the last upload)
 int import_lists_ready(acvm_batch *b, const ImportPlan &plan);
 // THE launch of an import on the handle's stream, whatever the entry point, and the only place that chooses among launch_import (the plain plan),

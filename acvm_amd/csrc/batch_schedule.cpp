@@ -150,6 +150,10 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
         b->events_fresh = false;
     } else {
         if (int rc = enqueue_level_schedule(b, b->profiling ? &tm : nullptr)) return rc;
+        // A masked import left instances without some input (batch.hpp n_missing): they leave the generic path at opcode 0. Behind the schedule's
+        // last step on the main stream -- behind the reset of the event words, whether its step ran or the import had left them ready -- and in
+        // front of the host's read of the count. (The forced slow path and stepping make every instance an exact lane anyway.)
+        if (b->n_missing) launch_import_missing_flag(s, b->d_missing, (uint32_t)p.initial_ids.size(), b->Bp, b->B, b->d_event);
     }
     HIPCHK(hipGetLastError());
     // the exact job of the PREVIOUS solve (asynchronous mode) is collected here, while the device works on this solve's levels
@@ -234,6 +238,8 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
         }
         hipStream_t xs = b->xstream();
         launch_init_assigned(xs, b->d_assigned, n_slow, b->n_words, p.n_witnesses, b->d_producer, b->d_slow_start);
+        // (in place and in the side table alike: the bitmap is per exact lane, d_slow_ids says whose)
+        if (b->n_missing) launch_import_missing_clear(xs, b->d_missing, (uint32_t)p.initial_ids.size(), b->Bp, b->d_init_ids, b->d_slow_ids, n_slow, b->d_assigned);
         b->fc_lane.assign(n_slow, acvm_batch::FcLaneState());
         if (int rc = upload_fc_tables(b, n_slow)) return rc;
         launch_exact_init(xs, exact_lanes(b, n_slow));

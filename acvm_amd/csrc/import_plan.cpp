@@ -91,6 +91,14 @@ int import_plan_desc(const ImportView *view, const acvm_import_desc_t *d, const 
     return 0;
 }
 
+int import_plan_desc_masked(const ImportView *view, const acvm_import_desc_t *d, const void *d_values, const uint8_t *d_assigned, ImportPlan *out, std::string *err) {
+    ImportPlan plan;
+    if (int rc = import_plan_desc(view, d, d_values, &plan, err)) return rc;
+    plan.d_assigned = d_assigned;
+    *out = std::move(plan);
+    return 0;
+}
+
 int import_plan_parts(const ImportView *view, const acvm_import_part_t *parts, uint32_t n_parts, ImportPlan *out, std::string *err) {
     if (n_parts && !parts) { *err = "null argument"; return ACVM_E_INVALID; }
     ImportPlan plan;

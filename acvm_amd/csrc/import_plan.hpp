@@ -52,7 +52,12 @@ struct ImportPlan {
     bool plain = false;
     std::vector<ImportPlanPart> parts;
     std::vector<uint32_t> lists;  // all lists of the call, per part: rows, planes (circuits with byte planes), columns (parts with a list)
-    bool operator==(const ImportPlan &o) const { return plain == o.plain && parts == o.parts && lists == o.lists; }
+    // acvm_batch_import_device_masked: one byte per element in the layout, stride and column list of the (one, resident) part. A plan with a mask
+    // never compares equal to one without, and the solve_then_import entry points take none: it never counts as the import that ran behind a
+    // solve. (Like d_values the pointer itself is not compared.)
+    const uint8_t *d_assigned = nullptr;
+    bool masked() const { return d_assigned != nullptr; }
+    bool operator==(const ImportPlan &o) const { return masked() == o.masked() && plain == o.plain && parts == o.parts && lists == o.lists; }
 };
 
 // the plain plan of a handle with n_in initial witnesses: nothing to check, any pointer
@@ -60,6 +65,9 @@ ImportPlan import_plan_plain(uint32_t n_in, const void *d_values);
 // A descriptor is a plan of one (resident) part; each part of acvm_batch_import_device_parts one part with lists of its own. Each returns 0 and
 // *out, or ACVM_E_INVALID and the text in *err (*out is then untouched). view: null is the null batch, judged behind encoding and layout.
 int import_plan_desc(const ImportView *view, const acvm_import_desc_t *d, const void *d_values, ImportPlan *out, std::string *err);
+// acvm_batch_import_device_masked: every check of import_plan_desc on d and d_values, unchanged and in the same order; d_assigned (any
+// alignment) joins the plan. d_assigned null IS import_plan_desc: the same plan, equal to the unmasked call's.
+int import_plan_desc_masked(const ImportView *view, const acvm_import_desc_t *d, const void *d_values, const uint8_t *d_assigned, ImportPlan *out, std::string *err);
 int import_plan_parts(const ImportView *view, const acvm_import_part_t *parts, uint32_t n_parts, ImportPlan *out, std::string *err);
 
 }  // namespace acvm

@@ -122,6 +122,22 @@ void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint
 // Arguments and return value as launch_import_device / launch_export_device(_lanes); the mask byte of a narrow element is 0 / 1 / 2.
 bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
                          const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
+// ---- kernels_import_mask.hip (acvm_batch_import_device_masked; import_mask.hpp: where a mask byte lies, the missing set, the result words)
+struct ImportMaskSource {
+    const uint8_t *mask;      // the caller's d_assigned: one byte per element in the values' layout, stride and column list; any alignment
+    uint32_t layout;
+    const uint32_t *columns;  // device array, one column per input; null: input k is column k
+    uint64_t stride;          // in elements, >= the layout's dense stride
+};
+// The mask pass, behind the value import of all n_in inputs: missing ([words][Bp]) is written for instances [0, B), the rows (and plane words) of
+// absent elements are zeroed, result (IMPORT_MASK_RESULT_WORDS device words, zeroed by the caller) gathers what the host reads back.
+void launch_import_mask(hipStream_t s, const ImportMaskSource &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *rows, uint32_t n_in, const uint32_t *plane_of_input,
+                        uint32_t *plane, uint32_t *missing, uint64_t *result);
+// the flag pass: every instance of [0, B) with an absent input leaves the generic path at opcode 0 (ops_common.hpp flag_instance)
+void launch_import_missing_flag(hipStream_t s, const uint32_t *missing, uint32_t n_in, uint64_t Bp, uint32_t B, uint32_t *event);
+// the clear pass behind launch_init_assigned: exact lane t drops the initial witnesses instance slow_ids[t] lacks from its assigned set
+void launch_import_missing_clear(hipStream_t s, const uint32_t *missing, uint32_t n_in, uint64_t Bp, const uint32_t *init_ids, const uint32_t *slow_ids, uint32_t n_slow,
+                                 uint32_t *assigned);
 void launch_export_narrow(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u);
 void launch_export_narrow_lanes(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, bool side, const uint32_t *lanes, uint32_t n_lanes,
                                 const uint32_t *assigned_bits, uint32_t n_slow);

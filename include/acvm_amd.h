@@ -710,8 +710,8 @@ uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b);
  * acvm_batch_solve_then_import_ex is acvm_batch_solve_then_import for such a buffer: the same gate, the same refusals, a plain solve in the same
  * cases. The following acvm_batch_import_device costs nothing only when the pointer AND the descriptor's contents, column list included, are the
  * same (the library keeps a copy of the descriptor, not the caller's pointer); anything else imports again.
- * Not here: an asynchronous variant (the node's form is acvm_node_solve_device), a mask of unassigned inputs (every instance of a batch assigns the same
- * ids); the host import and the two entry points above keep their behaviour.
+ * Not here: an asynchronous variant (the node's form is acvm_node_solve_device); the host import and the two entry points above keep their
+ * behaviour. Instances that do not all assign the same ids: acvm_batch_import_device_masked below.
  */
 typedef struct {
     uint32_t encoding, layout;   /* ACVM_ENC_*, ACVM_LAYOUT_* */
@@ -721,6 +721,34 @@ typedef struct {
 } acvm_import_desc_t;
 int acvm_batch_import_device(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values);
 int acvm_batch_solve_then_import_ex(acvm_batch_t *b, const acvm_import_desc_t *d_next, const void *d_next_values);
+/*
+ * Per-instance PARTIAL initial witness maps: ACVM::new takes a WitnessMap in which absence means unassigned (pwg/mod.rs:146-156), and
+ * acvm_batch_export_device writes exactly that -- zero bytes and mask 0 for what an instance did not assign. The masked import reads both:
+ *   - d, d_values: exactly as acvm_batch_import_device, with every check, refusal and alignment rule of it, the narrow encodings included.
+ *   - d_assigned: DEVICE pointer, any alignment, one byte per element in the layout, the stride (in elements) and the column list of the values:
+ *     element (i, c) is byte i * stride + c instance-major and c * stride + i witness-major -- what acvm_batch_export_device writes into its
+ *     d_assigned. 0: instance i does NOT hold that initial witness; 1: it does, with the value read from d_values. NULL: the call IS
+ *     acvm_batch_import_device -- the same kernels, the same plan, nothing else launched.
+ *   - An instance with an absent input is solved as ACVM::solve solves that map: in order from opcode 0 on the exact path, where an opcode that
+ *     needs the witness ends it as OpcodeNotSolvable(MissingAssignment(w)) and a gate that has it as its only unknown solves it. The row of an
+ *     absent element holds zero afterwards; nothing reads it as a value. A handle with a caller's BlackBoxFunctionSolver and a handle with
+ *     ACVM_BATCH_REUSE_SLOTS are supported alike. acvm_debug_import_missing: the instances with at least one absent input after the last import.
+ *   - Any other byte is refused -- the 2 of a narrow export whose value did not fit too: the buffer does not hold that value. The host cannot see
+ *     the bytes beforehand, so this refusal comes behind the import: ACVM_E_INVALID, the message gives the number of offending elements and
+ *     names the one of the lowest instance and, in it, the lowest position of initial_ids, and the handle is left WITHOUT initial witnesses --
+ *     acvm_batch_solve is ACVM_E_STATE until another import. It is the only refusal of the call that does not leave the handle as it was.
+ *   - Synchronous like the rest. What comes back from the device is three words, nothing per instance.
+ *   - Every other import entry point leaves every instance holding every input again; acvm_batch_reset keeps what the last import said, as it
+ *     keeps the rows.
+ * acvm_batch_set_initial_witness_masked is the host form: values as acvm_batch_set_initial_witness, assigned [B][n_initial] bytes 0 / 1, both
+ * staged and read by the device path above (BE32, instance-major, dense).
+ * Instance-major, the mask row of an instance is read in 16-byte units where no column list is given; under a column list one byte per input.
+ * Not here: a mask for acvm_batch_solve_then_import_ex (a masked import never rides behind a solve), masks for the parts of
+ * acvm_batch_import_device_parts, masks for the inputs of acvm_node_solve_device, acvm_multi_* on top of a masked batch.
+ */
+int acvm_batch_import_device_masked(acvm_batch_t *b, const acvm_import_desc_t *d, const void *d_values, const uint8_t *d_assigned);
+int acvm_batch_set_initial_witness_masked(acvm_batch_t *b, const uint8_t *values_be32, const uint8_t *assigned /* [B][n_initial] */);
+uint64_t acvm_debug_import_missing(const acvm_batch_t *b);   /* instances with at least one absent input after the last import */
 /*
  * One import from several buffers: fn main(msg: [u8; 64], root: Field) takes its bytes from one producer and its root, the same for every
  * instance, from another. Each part names the initial witnesses it supplies (positions in the initial_ids given to acvm_batch_new) and how
