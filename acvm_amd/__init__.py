@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "acvm_batch_foreign_call_sites", "acvm_batch_foreign_call_inputs_device", "acvm_batch_resolve_foreign_calls_device", "acvm_debug_foreign_call_stats",
     "acvm_batch_resolve_foreign_calls_device_rows",
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
+    "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
 ]
 
 
@@ -86,6 +87,52 @@ class ImportPart(C.Structure):
     """acvm_import_part_t"""
     _fields_ = [("d_values", C.c_void_p), ("encoding", C.c_uint32), ("layout", C.c_uint32), ("positions", C.POINTER(C.c_uint32)),
                 ("columns", C.POINTER(C.c_uint32)), ("n", C.c_uint32), ("n_columns", C.c_uint32), ("stride", C.c_uint64)]
+
+
+class RecordField(C.Structure):
+    """acvm_record_field_t: initial witness `position` is the element of `encoding` at byte `offset` of every record (any alignment)"""
+    _fields_ = [("position", C.c_uint32), ("encoding", C.c_uint32), ("offset", C.c_uint64)]
+
+
+class RecordDesc(C.Structure):
+    """acvm_record_desc_t"""
+    _fields_ = [("pitch", C.c_uint64), ("fields", C.POINTER(RecordField)), ("n_fields", C.c_uint32)]
+
+
+def record_desc(pitch, fields):
+    """(RecordDesc, the array its field pointer refers to) from the bytes between two records and (position, encoding, offset) triples or
+    RecordField objects"""
+    fl = [f if isinstance(f, RecordField) else RecordField(*f) for f in fields]
+    arr = (RecordField * max(len(fl), 1))(*fl)
+    return RecordDesc(pitch=pitch, fields=arr, n_fields=len(fl)), arr
+
+
+def record_fields_from_dtype(dtype, positions):
+    """The (pitch, fields) of a numpy structured dtype, as record_desc and the *_records calls take them. positions: {field name: position, list
+    of positions, or (positions, encoding)}. A field's bytes are divided evenly among its positions, in order: ("msg", np.uint8, 64) with 64
+    positions is 64 ENC_U8 elements, ("root", "V32") with one position one 32-byte element. The element's width chooses the encoding -- 1, 2, 4,
+    8, 16 bytes: ENC_U8 .. ENC_U128, 32 bytes: ENC_BE32 -- unless one is given. Names that positions does not list are padding."""
+    import numpy as np
+    dtype = np.dtype(dtype)
+    by_size = {1: ENC_U8, 2: ENC_U16, 4: ENC_U32, 8: ENC_U64, 16: ENC_U128, 32: ENC_BE32}
+    fields = []
+    for name, want in positions.items():
+        sub, offset = dtype.fields[name][0], dtype.fields[name][1]
+        encoding = None
+        if isinstance(want, tuple):
+            want, encoding = want
+        plist = [want] if isinstance(want, int) else list(want)
+        if not plist or sub.itemsize % len(plist):
+            raise ValueError(f"field {name}: {sub.itemsize} bytes do not divide among {len(plist)} positions")
+        size = sub.itemsize // len(plist)
+        if encoding is None:
+            if size not in by_size:
+                raise ValueError(f"field {name}: no encoding for elements of {size} bytes")
+            encoding = by_size[size]
+        if element_size(encoding) != size:
+            raise ValueError(f"field {name}: the encoding takes {element_size(encoding)} bytes, an element of the field has {size}")
+        fields += [(pos, encoding, offset + k * size) for k, pos in enumerate(plist)]
+    return dtype.itemsize, fields
 
 
 class NodeLaneIo(C.Structure):
@@ -466,6 +513,11 @@ def lib():
         L.acvm_batch_set_initial_witness_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.acvm_debug_import_missing.restype = C.c_uint64
         L.acvm_debug_import_missing.argtypes = [C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_records"):
+        L.acvm_batch_import_device_records.argtypes = [C.c_void_p, C.POINTER(RecordDesc), C.c_void_p]
+        L.acvm_batch_set_initial_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordDesc), C.c_void_p]
+        L.acvm_node_solve_records.restype = C.c_longlong
+        L.acvm_node_solve_records.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(RecordDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -906,6 +958,25 @@ class Node:
         self._finish_call(rc)
         return rc, res, kv, ka, dg
 
+    def solve_records(self, records, n_instances: int, pitch: int, fields, results=True, kept=True, digests=True):
+        """solve with the inputs as host records (acvm_node_solve_records): records holds n_instances * pitch bytes (bytes or a uint8 array),
+        fields as Batch.import_device_records takes them. Returns what solve returns."""
+        import numpy as np
+        buf = np.frombuffer(records, dtype=np.uint8) if not isinstance(records, np.ndarray) else records.view(np.uint8).reshape(-1)
+        if buf.size != n_instances * pitch:
+            raise ValueError("records has the wrong size")
+        desc, _keep = record_desc(pitch, fields)
+        res = (Result * max(n_instances, 1))() if results else None
+        nk = len(self.keep)
+        kv = np.zeros((n_instances, nk, 32), dtype=np.uint8) if kept and nk else None
+        ka = np.zeros((n_instances, nk), dtype=np.uint8) if kept and nk else None
+        dg = np.zeros((n_instances, 32), dtype=np.uint8) if digests else None
+        rc = lib().acvm_node_solve_records(self._h, n_instances, C.byref(desc), buf.ctypes.data if buf.size else None, C.cast(res, C.c_void_p) if res is not None else None,
+                                           kv.ctypes.data if kv is not None else None, ka.ctypes.data if ka is not None else None,
+                                           dg.ctypes.data if dg is not None else None)
+        self._finish_call(rc)
+        return rc, res, kv, ka, dg
+
     def solve_device(self, lanes):
         """acvm_node_solve_device: one dict per handle of the node with the fields of acvm_node_lane_io_t -- n, d_values, encoding, layout, columns,
         n_columns, stride (the inputs, as import_device's keywords), d_kept, d_kept_assigned, kept_encoding, kept_layout, kept_stride, d_status,
@@ -1147,6 +1218,25 @@ class Batch:
                 keep.append(c_arr)
                 arr[q].columns, arr[q].n_columns = c_arr, len(cols) if part.get("n_columns") is None else part["n_columns"]
         _check(lib().acvm_batch_import_device_parts(self._h, arr, len(parts)))
+
+    def import_device_records(self, d_ptr: int, pitch: int, fields):
+        """The initial witnesses read from an array of structs in device memory (acvm_batch_import_device_records): instance i reads the record at
+        d_ptr + i * pitch; fields: (position, encoding, offset) triples or RecordField objects -- initial witness `position` (in the order of the
+        ids the batch was created with) is the element of `encoding` at byte `offset` of the record. Pointer, pitch and offsets of any alignment;
+        every position exactly once; bytes no field covers are padding. record_fields_from_dtype makes (pitch, fields) of a numpy dtype. (The
+        descriptor is built per call, about 0.3 us per field: a loop that minds builds record_desc once and calls the C entry point.)"""
+        desc, _keep = record_desc(pitch, fields)
+        _check(lib().acvm_batch_import_device_records(self._h, C.byref(desc), d_ptr))
+
+    def set_initial_witness_records(self, records, pitch: int, fields):
+        """import_device_records from host memory (acvm_batch_set_initial_witness_records): records holds B * pitch bytes (bytes, or a numpy
+        array -- a structured one too)"""
+        import numpy as np
+        buf = np.frombuffer(records, dtype=np.uint8) if not isinstance(records, np.ndarray) else np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        if buf.size != self.B * pitch:
+            raise ValueError("records has the wrong size")
+        desc, _keep = record_desc(pitch, fields)
+        _check(lib().acvm_batch_set_initial_witness_records(self._h, C.byref(desc), buf.ctypes.data if buf.size else None))
 
     def import_list_copies(self) -> int:
         """host-to-device copies of the imports' lists -- a descriptor's column list, the lists of import_device_parts -- this handle has made

@@ -345,6 +345,9 @@ int batch_set_live_count(acvm_batch *b, uint32_t n);
 // acvm_batch_set_initial_witness_device without the wait: the import is enqueued on the handle's stream and `imported` recorded behind it;
 // the caller keeps d_values_be32 untouched until that event has fired.
 int batch_import_async(acvm_batch *b, const void *d_values_be32, hipEvent_t imported);
+// acvm_batch_import_device_records without the wait (acvm_node_solve_records): the descriptor is checked against the handle (its live count),
+// the import enqueued and `imported` recorded behind it; d_records stays untouched until that event has fired
+int batch_import_records_async(acvm_batch *b, const acvm_record_desc_t *d, const void *d_records, hipEvent_t imported);
 // waits for the exact job in flight (if any) and moves its outcome into *out (cleared first)
 int batch_finish_pending(acvm_batch *b, ExactOutcome *out);
 // the outcome of the previous solve's exact job, which the last acvm_batch_solve collected on its way (moved into *out; empty if none)

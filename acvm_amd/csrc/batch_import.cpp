@@ -5,6 +5,7 @@
 #include "batch_internal.hpp"
 #include "export_encode.hpp"
 #include "import_mask.hpp"
+#include "record_plan.hpp"
 
 static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
                   EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
@@ -46,6 +47,10 @@ uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b) { return b ? b->n_
 // The parts one after the other, each with the rows, planes and columns of ITS inputs: from the list buffer, or -- a descriptor -- the handle's
 // resident tables.
 bool batch_launch_import(acvm_batch *b, const ImportPlan &plan, const uint32_t *gate) {
+    if (plan.records) {  // (no parts: one launch over the window and field tables of the list buffer)
+        const uint32_t *windows = b->d_import_lists, *fields = windows + (size_t)plan.record_windows * RECORD_WINDOW_WORDS;
+        return launch_import_records(b->stream, plan.d_records, plan.record_pitch, windows, plan.record_windows, fields, b->d_W, b->Bp, b->B, gate, b->d_byte_plane, b->d_event);
+    }
     bool reset_written = false;
     for (const ImportPlanPart &pt : plan.parts) {
         if (!pt.n) continue;
@@ -67,9 +72,9 @@ bool batch_launch_import(acvm_batch *b, const ImportPlan &plan, const uint32_t *
 }
 
 // acvm_batch_solve_then_import(_ex) put exactly this import behind the previous solve, and it ran: the rows are there, in stream order. (Only a
-// plan of one resident part rides behind a solve: the plan of parts never compares equal to it.)
+// plan of one resident part rides behind a solve: the plan of parts never compares equal to it, and a record plan has no parts.)
 static bool import_is_behind_solve(const acvm_batch *b, const ImportPlan &plan) {
-    return b->next_imported && plan.parts.size() == 1 && b->next_inputs == plan.parts[0].d_values && b->next_plan == plan;
+    return b->next_imported && !plan.records && plan.parts.size() == 1 && b->next_inputs == plan.parts[0].d_values && b->next_plan == plan;
 }
 // The handle's state after an import. enqueued: by this call, and reset_written is batch_launch_import's answer (events_fresh's rule: batch.hpp);
 // otherwise the import is the one behind the last solve, which set events_fresh itself.
@@ -204,5 +209,36 @@ int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *pa
     ImportPlan plan;
     std::string err;
     if (int rc = import_plan_parts(b ? &view : nullptr, parts, n_parts, &plan, &err)) return set_err(rc, err);
+    return import_and_wait(b, plan);
+} ABI_CATCH
+
+// ---- the record import (include/acvm_amd.h acvm_batch_import_device_records): the field list is checked and cut into windows by
+// record_plan.cpp, the tables travel in the handle's one list buffer, one launch reads them. A record plan never rides behind a solve.
+static int import_plan_records_of(const acvm_batch *b, const acvm_record_desc_t *d, const void *d_records, ImportPlan *out) {
+    const ImportView view = b ? import_view(b) : ImportView{};
+    std::string err;
+    const int rc = import_plan_records(b ? &view : nullptr, d, d_records, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+int batch_import_records_async(acvm_batch *b, const acvm_record_desc_t *d, const void *d_records, hipEvent_t imported) {
+    ImportPlan plan;
+    if (int rc = import_plan_records_of(b, d, d_records, &plan)) return rc;
+    return batch_import_plan_async(b, plan, imported, nullptr);
+}
+int acvm_batch_import_device_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *d_records) try {
+    ImportPlan plan;
+    if (int rc = import_plan_records_of(b, d, d_records, &plan)) return rc;
+    return import_and_wait(b, plan);
+} ABI_CATCH
+// the host form: the records through the staging buffer, then the device path. The descriptor is judged first (with the caller's pointer: the
+// null rule), so a refused call copies nothing.
+int acvm_batch_set_initial_witness_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *records) try {
+    ImportPlan plan;
+    if (int rc = import_plan_records_of(b, d, records, &plan)) return rc;
+    const size_t bytes = d->n_fields ? (size_t)b->B * d->pitch : 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = stage_reserve(b, bytes)) return rc;
+    if (bytes) HIPCHK(hipMemcpyAsync(b->d_stage, records, bytes, hipMemcpyHostToDevice, b->stream));
+    plan.d_records = b->d_stage;
     return import_and_wait(b, plan);
 } ABI_CATCH

@@ -57,7 +57,18 @@ struct ImportPlan {
     // solve. (Like d_values the pointer itself is not compared.)
     const uint8_t *d_assigned = nullptr;
     bool masked() const { return d_assigned != nullptr; }
-    bool operator==(const ImportPlan &o) const { return masked() == o.masked() && plain == o.plain && parts == o.parts && lists == o.lists; }
+    // acvm_batch_import_device_records (record_plan.hpp import_plan_records): no parts -- lists holds the window table and the field table, one
+    // launch reads them (kernels_records.hip). A record plan never compares equal to a plan of another kind, two record plans are equal when
+    // pitch, window count and tables are, and the solve_then_import entry points take none: it never counts as the import that ran behind a
+    // solve. (Like d_values the pointer d_records is not compared.)
+    bool records = false;
+    uint64_t record_pitch = 0;
+    uint32_t record_windows = 0;
+    const void *d_records = nullptr;
+    bool operator==(const ImportPlan &o) const {
+        return masked() == o.masked() && plain == o.plain && records == o.records && record_pitch == o.record_pitch && record_windows == o.record_windows && parts == o.parts &&
+               lists == o.lists;
+    }
 };
 
 // the plain plan of a handle with n_in initial witnesses: nothing to check, any pointer

@@ -122,6 +122,11 @@ void launch_export_device_lanes(hipStream_t s, const ExportDevice &x, const uint
 // Arguments and return value as launch_import_device / launch_export_device(_lanes); the mask byte of a narrow element is 0 / 1 / 2.
 bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *ids, uint32_t n_in, const uint32_t *gate = nullptr,
                          const uint32_t *plane_of_input = nullptr, uint32_t *plane = nullptr, uint32_t *event_reset = nullptr);
+// ---- kernels_records.hip (acvm_batch_import_device_records): instance i reads its fields from the record at in + i * pitch, any alignment.
+// windows / fields: the device tables of record_plan.hpp (rows and planes per field inside). The other arguments and the return value as
+// launch_import.
+bool launch_import_records(hipStream_t s, const void *in, uint64_t pitch, const uint32_t *windows, uint32_t n_windows, const uint32_t *fields, uint4 *W, uint64_t Bp,
+                           uint32_t B, const uint32_t *gate, uint32_t *plane, uint32_t *event_reset);
 // ---- kernels_import_mask.hip (acvm_batch_import_device_masked; import_mask.hpp: where a mask byte lies, the missing set, the result words)
 struct ImportMaskSource {
     const uint8_t *mask;      // the caller's d_assigned: one byte per element in the values' layout, stride and column list; any alignment

@@ -18,6 +18,7 @@
 #include "circuit.hpp"
 #include "node_foreign_plan.hpp"
 #include "node_io_plan.hpp"
+#include "record_plan.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -406,8 +407,10 @@ void foreign_rounds(acvm_node *node, DeviceLane &L, uint32_t tile_index, uint64_
     L.io_d2h += d2h1 - d2h0 + own_d2h;
 }
 
-void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, acvm_result_t *results, uint8_t *kept, uint8_t *kept_assigned,
-                   uint8_t *digests) {
+// rec: null, or the record descriptor of acvm_node_solve_records (checked by the caller): `values` are then host records of rec->pitch bytes, a
+// tile stages and uploads m * pitch bytes and is imported through the record plan; everything else is the same.
+void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, const acvm_record_desc_t *rec, acvm_result_t *results, uint8_t *kept,
+                   uint8_t *kept_assigned, uint8_t *digests) {
     const double t_begin = now_ms();
     L.rc = 0;
     L.error.clear();
@@ -418,7 +421,7 @@ void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last
     auto fail = [&](int rc, const std::string &what) { if (!L.rc) { L.rc = rc; L.error = what + ": " + acvm_last_error(); } };
     if (hipSetDevice(L.device) != hipSuccess) { fail(ACVM_E_DEVICE, "hipSetDevice"); return; }
     const uint32_t tile = node->tile, n_keep = (uint32_t)node->keep.size();
-    const size_t row = node->ids.size() * 32;
+    const size_t row = rec ? (rec->n_fields ? (size_t)rec->pitch : 0) : node->ids.size() * 32;
     const uint64_t n = last - first;
     const uint32_t n_tiles = (uint32_t)((n + tile - 1) / tile);
     if (!n_tiles) return;
@@ -520,7 +523,10 @@ void run_lane_body(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last
         L.h2d_wait_ms += now_ms() - t0;
         if (int rc = batch_set_live_count(L.batch, m)) { fail(rc, "live count"); break; }  // a partial last tile: the lanes behind it are dead
         // the import is enqueued, not waited for: it runs behind the export kernel of the previous tile and in front of this tile's levels
-        if (int rc = batch_import_async(L.batch, L.d_in[slot], L.ev_imported[slot])) { fail(rc, "set_initial_witness"); break; }
+        if (int rc = rec ? batch_import_records_async(L.batch, rec, L.d_in[slot], L.ev_imported[slot]) : batch_import_async(L.batch, L.d_in[slot], L.ev_imported[slot])) {
+            fail(rc, "set_initial_witness");
+            break;
+        }
         {   // the producer may prepare the tile after next (its upload waits for ev_imported on the copy stream)
             std::lock_guard<std::mutex> lk(mu);
             consumed = k + 1;
@@ -720,11 +726,11 @@ void run_lane_device(acvm_node *node, DeviceLane &L, const NodeLaneIo &lane, acv
 
 // a lane's thread: pinned to the CPUs of its device's NUMA node (its upload thread and the staging helpers inherit the mask), and closed
 // against exceptions: std::terminate is not an error code
-void run_lane(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, acvm_result_t *results, uint8_t *kept, uint8_t *kept_assigned,
-              uint8_t *digests) {
+void run_lane(acvm_node *node, DeviceLane &L, uint64_t first, uint64_t last, const uint8_t *values, const acvm_record_desc_t *rec, acvm_result_t *results, uint8_t *kept,
+              uint8_t *kept_assigned, uint8_t *digests) {
     try {
         pin_thread(L.cpus);
-        run_lane_body(node, L, first, last, values, results, kept, kept_assigned, digests);
+        run_lane_body(node, L, first, last, values, rec, results, kept, kept_assigned, digests);
     } catch (const std::bad_alloc &) {
         if (!L.rc) { L.rc = ACVM_E_NOMEM; L.error = "out of host memory"; }
     } catch (const std::exception &e) {
@@ -837,9 +843,10 @@ void acvm_node_free(acvm_node_t *n) { delete n; }
 uint32_t acvm_node_tile_instances(const acvm_node_t *n) { return n ? n->tile : 0; }
 uint32_t acvm_node_num_devices(const acvm_node_t *n) { return n ? (uint32_t)n->lanes.size() : 0; }
 
-long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, acvm_result_t *results, uint8_t *kept_be32, uint8_t *kept_assigned,
-                          uint8_t *digests32) try {
-    if (!n || (n_instances && !n->ids.empty() && !values_be32)) return set_err(ACVM_E_INVALID, "null argument");
+namespace {
+// the body of acvm_node_solve and acvm_node_solve_records (rec: null, or the checked record descriptor that `values` are read by)
+long long node_solve_host(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, const acvm_record_desc_t *rec, acvm_result_t *results, uint8_t *kept_be32,
+                          uint8_t *kept_assigned, uint8_t *digests32) {
     RunningCall running(n);
     const double t0 = now_ms();
     const size_t D = n->lanes.size();
@@ -849,7 +856,7 @@ long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *v
     for (size_t d = 0; d <= D; d++) bound[d] = std::min<uint64_t>(n_instances, per * d);
     std::vector<std::thread> th;
     for (size_t d = 0; d < D; d++)
-        th.emplace_back(run_lane, n, std::ref(n->lanes[d]), bound[d], bound[d + 1], values_be32, results, kept_be32, kept_assigned, digests32);
+        th.emplace_back(run_lane, n, std::ref(n->lanes[d]), bound[d], bound[d + 1], values_be32, rec, results, kept_be32, kept_assigned, digests32);
     for (auto &t : th) t.join();
     n->last_n = n_instances;
     n->last_total_ms = now_ms() - t0;
@@ -858,6 +865,29 @@ long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *v
     long long not_solved = 0;
     for (DeviceLane &L : n->lanes) not_solved += (long long)L.not_solved;
     return not_solved;
+}
+}  // namespace
+
+long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, acvm_result_t *results, uint8_t *kept_be32, uint8_t *kept_assigned,
+                          uint8_t *digests32) try {
+    if (!n || (n_instances && !n->ids.empty() && !values_be32)) return set_err(ACVM_E_INVALID, "null argument");
+    return node_solve_host(n, n_instances, values_be32, nullptr, results, kept_be32, kept_assigned, digests32);
+} ABI_CATCH
+
+// The inputs as host records: the descriptor is checked once, here, before any lane starts (record_plan.cpp; rows and planes are the lanes' own
+// and do not enter the checks), then every lane's tiles go through batch_import_records_async.
+long long acvm_node_solve_records(acvm_node_t *n, uint64_t n_instances, const acvm_record_desc_t *in, const void *records, acvm_result_t *results, uint8_t *kept_be32,
+                                  uint8_t *kept_assigned, uint8_t *digests32) try {
+    if (!n) return set_err(ACVM_E_INVALID, "null argument");
+    const ImportView view{n_instances ? 1u : 0u, (uint32_t)n->ids.size(), n->ids.data(), n->ids.data(), nullptr};
+    ImportPlan checked;
+    std::string text;
+    if (int rc = import_plan_records(&view, in, records, &checked, &text)) return set_err(rc, text);
+    if (in->n_fields && in->pitch > 32u * (uint64_t)n->ids.size())
+        return set_err(ACVM_E_INVALID, "pitch " + std::to_string(in->pitch) + " is above 32 * n_initial = " + std::to_string(32u * (uint64_t)n->ids.size()) +
+                                           ": the staging slots hold the 32-byte form, and a wider record gains nothing");
+    // (the fields are the caller's until the call returns: every lane reads the same array)
+    return node_solve_host(n, n_instances, (const uint8_t *)records, in, results, kept_be32, kept_assigned, digests32);
 } ABI_CATCH
 
 // The device form: every lane is checked (node_io_plan.cpp) before any lane starts, then each lane's thread walks its own rows.

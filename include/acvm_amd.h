@@ -772,6 +772,41 @@ typedef struct {
 } acvm_import_part_t;
 int acvm_batch_import_device_parts(acvm_batch_t *b, const acvm_import_part_t *parts, uint32_t n_parts);
 uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b);
+/*
+ * Record import: the initial witnesses as an array of structs. Each instance is one packed record of mixed-width fields at a fixed pitch --
+ * { msg: [u8; 64], root: Field, idx: u32, flags: [bool; 8] } as a Rust #[repr(C, packed)] row, a numpy structured dtype, a database row -- and
+ * every initial witness is one field of it: an encoding and a byte offset inside the record.
+ *   - Addressing: instance i of the live instances reads its field at byte i * pitch + offset of d_records. d_records, pitch and the offsets
+ *     may have ANY alignment (as ACVM_ENC_U8 already allows for a pointer): a 32-byte field behind 64 bytes of a 108-byte record is fine.
+ *   - Decoding: exactly as acvm_batch_import_device decodes an element of that encoding -- every 256-bit string is accepted and reduced, a
+ *     narrow element is the integer itself, little-endian; byte planes are filled as the typed import fills them; the event words are reset
+ *     exactly once per instance, whatever the order of the fields.
+ *   - Every initial witness must be supplied by exactly one field. Two positions may read the same or overlapping bytes, the fields may come
+ *     in any order, and bytes of a record that no field covers are padding: they influence nothing. No load touches a 4-byte-aligned word that
+ *     holds no byte of [d_records, d_records + B * pitch).
+ *   - Refused with ACVM_E_INVALID, the message naming the field or the position, the handle left as it was: a null descriptor; null fields
+ *     with n_fields > 0; a position >= n_initial; a position supplied twice, or never; an unknown encoding; offset + size > pitch (judged
+ *     without overflow); null records while there are fields and live instances. A circuit without initial witnesses takes n_fields == 0 and
+ *     reads nothing.
+ *   - Leaves the handle exactly as acvm_batch_import_device leaves it and returns after the batch's stream is synchronised. At most one small
+ *     host-to-device copy is made: the field table, which is reused while it does not change (acvm_debug_import_list_copies counts it).
+ *     Works with ACVM_BATCH_REUSE_SLOTS (rows are not ids), with a caller's solver, and after acvm_batch_set_instances.
+ * acvm_batch_set_initial_witness_records is the host form: B * pitch bytes go through the handle's staging buffer, then the device path runs.
+ * Not here: record EXPORT; a mask byte inside the record; an acvm_batch_solve_then_import form; records for the lanes of
+ * acvm_node_solve_device; big-endian or sign-extending narrow fields.
+ */
+typedef struct {
+    uint32_t position;   /* which initial witness: position in the initial_ids given to acvm_batch_new */
+    uint32_t encoding;   /* any ACVM_ENC_*: BE32, LE32, MONT256_LE, U8 .. U128 */
+    uint64_t offset;     /* byte offset of the element inside a record; ANY alignment */
+} acvm_record_field_t;
+typedef struct {
+    uint64_t pitch;                       /* bytes from one record to the next; any value >= the end of the last field */
+    const acvm_record_field_t *fields;    /* HOST, copied before the call returns */
+    uint32_t n_fields;
+} acvm_record_desc_t;
+int acvm_batch_import_device_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *d_records);
+int acvm_batch_set_initial_witness_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *records /* host */);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):
@@ -883,6 +918,13 @@ uint32_t acvm_node_tile_instances(const acvm_node_t *n);
 uint32_t acvm_node_num_devices(const acvm_node_t *n);
 long long acvm_node_solve(acvm_node_t *n, uint64_t n_instances, const uint8_t *values_be32, acvm_result_t *results, uint8_t *kept_be32,
                           uint8_t *kept_assigned, uint8_t *digests32);
+/* acvm_node_solve with the inputs as host records (acvm_batch_import_device_records): n_instances records at in->pitch. The upload thread stages
+ * and uploads m * pitch bytes per tile in place of m * n_initial * 32 and the tile is imported through the record plan; outputs, the exact path
+ * beside the next tile, the foreign-call handler and the stats are those of acvm_node_solve. The descriptor is checked once, before any lane
+ * starts: a refused call (ACVM_E_INVALID) starts nothing and leaves the node usable. A pitch above 32 * n_initial is refused too: the staging
+ * slots are sized for the 32-byte form at acvm_node_new, and a wider record gains nothing. */
+long long acvm_node_solve_records(acvm_node_t *n, uint64_t n_instances, const acvm_record_desc_t *in, const void *records /* host */,
+                                  acvm_result_t *results, uint8_t *kept_be32, uint8_t *kept_assigned, uint8_t *digests32);
 int acvm_node_stats(acvm_node_t *n, acvm_node_stats_t *out);
 /*
  * acvm_node_solve for a producer and a consumer that live on the GPUs: every lane (one per handle of the node, in the order of the device list)
