@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "acvm_batch_resolve_foreign_calls_device_rows",
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
     "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
+    "acvm_batch_export_device_records", "acvm_batch_witness_records",
 ]
 
 
@@ -105,6 +106,33 @@ def record_desc(pitch, fields):
     fl = [f if isinstance(f, RecordField) else RecordField(*f) for f in fields]
     arr = (RecordField * max(len(fl), 1))(*fl)
     return RecordDesc(pitch=pitch, fields=arr, n_fields=len(fl)), arr
+
+
+RECORD_NO_MASK = (1 << 64) - 1
+
+
+class RecordOutField(C.Structure):
+    """acvm_record_out_field_t: `witness` leaves as the element of `encoding` at byte `offset` of every record (any alignment), its mask byte at
+    byte `mask_offset` (RECORD_NO_MASK: none)"""
+    _fields_ = [("witness", C.c_uint32), ("encoding", C.c_uint32), ("offset", C.c_uint64), ("mask_offset", C.c_uint64)]
+
+
+class RecordOutDesc(C.Structure):
+    """acvm_record_out_desc_t"""
+    _fields_ = [("pitch", C.c_uint64), ("fields", C.POINTER(RecordOutField)), ("n_fields", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32)]
+
+
+def record_out_desc(pitch, fields, first, n):
+    """(RecordOutDesc, the array its field pointer refers to) from the bytes between two records and (witness, encoding, offset) or (witness,
+    encoding, offset, mask_offset) tuples (mask_offset None: no mask byte) or RecordOutField objects"""
+    fl = []
+    for f in fields:
+        if not isinstance(f, RecordOutField):
+            f = tuple(f)
+            f = RecordOutField(f[0], f[1], f[2], RECORD_NO_MASK if len(f) < 4 or f[3] is None else f[3])
+        fl.append(f)
+    arr = (RecordOutField * max(len(fl), 1))(*fl)
+    return RecordOutDesc(pitch=pitch, fields=arr, n_fields=len(fl), first=first, n=n), arr
 
 
 def record_fields_from_dtype(dtype, positions):
@@ -518,6 +546,9 @@ def lib():
         L.acvm_batch_set_initial_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordDesc), C.c_void_p]
         L.acvm_node_solve_records.restype = C.c_longlong
         L.acvm_node_solve_records.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(RecordDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "acvm_batch_export_device_records"):
+        L.acvm_batch_export_device_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p, C.c_void_p]
+        L.acvm_batch_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1342,6 +1373,29 @@ class Batch:
             arr = (C.c_uint32 * max(len(ws), 1))(*ws)
             desc.witnesses, desc.n_witnesses = arr, len(ws)
         _check(lib().acvm_batch_export_device_list(self._h, C.byref(desc), d_instances, d_ptr, d_assigned))
+
+    def export_device_records(self, d_ptr: int, pitch: int, fields, first=0, n=None, d_instances=None):
+        """The map as an array of structs in device memory (acvm_batch_export_device_records): output row i writes the record at d_ptr + i * pitch;
+        fields: (witness, encoding, offset) or (witness, encoding, offset, mask_offset) tuples or RecordOutField objects -- the element of
+        `encoding` that export_device writes for that witness goes to byte `offset` of the record, its mask byte (0 / 1, narrow 0 / 1 / 2) to byte
+        `mask_offset`. Pointer, pitch and offsets of any alignment; no byte that no field covers is written. Row i is instance first + i, or --
+        d_instances: a device array of n absolute instance numbers -- instance d_instances[i] as export_device_list reads it (n is then the
+        list's length and first must be 0). Nothing is copied to the host."""
+        if n is None:
+            if d_instances is not None:
+                raise ValueError("a list export needs n, the list's length")
+            n = self.B - first
+        desc, _keep = record_out_desc(pitch, fields, first, n)
+        _check(lib().acvm_batch_export_device_records(self._h, C.byref(desc), d_instances, d_ptr))
+
+    def witness_records(self, pitch: int, fields, first=0, n=None):
+        """export_device_records into host memory (acvm_batch_witness_records): a uint8 array [n][pitch]; the bytes no field covers are zero."""
+        import numpy as np
+        n = self.B - first if n is None else n
+        desc, _keep = record_out_desc(pitch, fields, first, n)
+        out = np.zeros((n, pitch), dtype=np.uint8)
+        _check(lib().acvm_batch_witness_records(self._h, C.byref(desc), out.ctypes.data if out.size else None))
+        return out
 
     def outcomes_device(self, first=0, n=None, d_status=None, d_err=None, d_opcode_index=None, select_mask=0, d_selected=None, count=True):
         """The outcomes of instances [first, first + n) as device columns (acvm_batch_outcomes_device): d_status / d_err uint8 [n], d_opcode_index uint32 [n],

@@ -193,6 +193,11 @@ struct acvm_batch {
     int32_t *d_lane_map = nullptr;
     uint64_t slow_epoch = 0, lane_map_epoch = 0;
     uint64_t n_export_h2d_bytes = 0;  // (acvm_debug_export_h2d_bytes)
+    // The window and field tables of acvm_batch_export_device_records (record_out_plan.hpp) on the device: those of the last call, uploaded
+    // again only when they change (the import's list buffer is not shared: an import between two exports would evict them)
+    std::vector<uint32_t> record_out_tables;
+    uint32_t *d_record_out_tables = nullptr;
+    size_t record_out_tables_cap = 0;
     // The tile sinks of the node's device form (batch_export.cpp). Two small grow-only arenas for the lists of the exact lanes -- [0] read on
     // the handle's stream behind a solve, [1] on the exact job's stream when its outcome is collected, beside the NEXT solve: they must not
     // share the staging arena -- and the host lists [0] is copied from, which live until the next solve has waited for the stream.
@@ -304,6 +309,7 @@ struct acvm_batch {
         if (d_mask_result) hipFree(d_mask_result);
         if (h_mask_result) hipHostFree(h_mask_result);
         if (d_lane_map) hipFree(d_lane_map);
+        if (d_record_out_tables) hipFree(d_record_out_tables);
         for (uint8_t *q : d_sink)
             if (q) hipFree(q);
         if (ev_sink) hipEventDestroy(ev_sink);

@@ -14,6 +14,7 @@
 #include <vector>
 #include "batch_internal.hpp"
 #include "export_encode.hpp"
+#include "record_out_plan.hpp"
 
 static const uint8_t DIGEST_G[32] = {0x23, 0x35, 0x53, 0x18, 0xdb, 0xff, 0xab, 0x2f, 0xb7, 0x72, 0x11, 0x7c, 0x57, 0x5c, 0x61, 0xb1,
                                      0x79, 0xf8, 0xc9, 0x83, 0x3c, 0x83, 0xba, 0x65, 0x59, 0x7e, 0x17, 0x3c, 0x35, 0xc4, 0xbb, 0xe3};
@@ -459,6 +460,64 @@ int acvm_batch_export_device_list(acvm_batch_t *b, const acvm_export_desc_t *d, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(s));  // (also what keeps the caller's witness list and slow_ids alive for their copies)
     return 0;
+} ABI_CATCH
+
+// ---- the map as packed records (include/acvm_amd.h acvm_batch_export_device_records): the field list is checked, cut into windows and given its
+// cover bitmaps by record_out_plan.cpp, the tables live in a device buffer of their own that is uploaded when they change, one launch writes the
+// records. Range and list are the same kernel, and both find the exact lanes through the lane map.
+static int record_out_tables_ready(acvm_batch *b, const RecordOutPlan &plan) {
+    const std::vector<uint32_t> &tables = plan.tables;
+    if (tables.empty() || (b->d_record_out_tables && b->record_out_tables == tables)) return 0;
+    HIPCHK(hipStreamSynchronize(b->stream));  // (nothing reads the old tables any more)
+    b->record_out_tables.clear();
+    if (tables.size() > b->record_out_tables_cap) {
+        if (b->d_record_out_tables) { hipFree(b->d_record_out_tables); b->d_record_out_tables = nullptr; b->record_out_tables_cap = 0; }
+        HIPCHK(hipMalloc((void **)&b->d_record_out_tables, tables.size() * 4));
+        b->record_out_tables_cap = tables.size();
+    }
+    HIPCHK(hipMemcpy(b->d_record_out_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
+    b->record_out_tables = tables;
+    b->n_export_h2d_bytes += (uint64_t)tables.size() * 4;
+    return 0;
+}
+// Both forms. records: the caller's buffer, device or host (host: the records are made in the staging buffer, zero-filled first, and copied down).
+static int export_records(acvm_batch *b, const acvm_record_out_desc_t *d, const uint32_t *d_instances, void *records, bool host) {
+    RecordOutPlan plan;
+    std::string refusal;
+    if (int rc = record_out_plan(b ? &b->B : nullptr, d, d_instances != nullptr, records, &plan, &refusal)) return set_err(rc, refusal);
+    if (int rc = finish_pending_and_require_solved(b)) return rc;
+    if (int rc = refuse_if_next_imported(b, plan.witnesses.data(), (uint32_t)plan.witnesses.size(), false)) return rc;
+    if (int rc = reuse_check_kept(b, plan.witnesses.data(), (uint32_t)plan.witnesses.size())) return rc;
+    if (!plan.n || !plan.n_entries) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (plan.mont256)
+        if (int rc = ensure_mont256_table(b)) return rc;
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size();
+    const bool map_stale = !(b->d_lane_map && b->lane_map_epoch == b->slow_epoch);
+    const size_t ids_bytes = map_stale ? align256((size_t)n_slow * 4) : 0, bytes = host ? (size_t)plan.n * plan.pitch : 0;
+    if (ids_bytes + bytes)
+        if (int rc = stage_reserve(b, ids_bytes + bytes)) return rc;
+    hipStream_t s = b->stream;
+    if (int rc = record_out_tables_ready(b, plan)) return rc;
+    if (int rc = lane_map_ready(b, s, (uint32_t *)b->d_stage)) return rc;
+    uint8_t *out = host ? b->d_stage + ids_bytes : (uint8_t *)records;
+    if (host) HIPCHK(hipMemsetAsync(out, 0, bytes, s));
+    const uint32_t *windows = b->d_record_out_tables, *fields = windows + (size_t)plan.n_windows * RECORD_OUT_WINDOW_WORDS;
+    const RecordExport x{b->d_W, b->Bp, plan.first, plan.n,
+                         ExportListSource{d_instances, b->B, b->d_lane_map, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), b->d_assigned, n_slow},
+                         b->plan().n_witnesses, b->d_slot_of, b->d_producer, b->unscale.index, b->unscale.consts_plain, b->d_unscale_m256,
+                         out, plan.pitch, windows, fields};
+    launch_export_records(s, x, plan.n_windows);
+    HIPCHK(hipGetLastError());
+    if (host) HIPCHK(hipMemcpyAsync(records, out, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps slow_ids alive for its copy)
+    return 0;
+}
+int acvm_batch_export_device_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, const uint32_t *d_instances, void *d_records) try {
+    return export_records(b, d, d_instances, d_records, false);
+} ABI_CATCH
+int acvm_batch_witness_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, void *records) try {
+    return export_records(b, d, nullptr, records, true);
 } ABI_CATCH
 
 uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b) { return b ? b->n_export_h2d_bytes : 0; }

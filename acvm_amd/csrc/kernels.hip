@@ -17,6 +17,7 @@
 #include "inverse_batch.hpp"
 #include "kernels.hpp"
 #include "export_encode.hpp"
+#include "export_source.hpp"
 #include "tuning.hpp"
 
 namespace acvm {
@@ -173,14 +174,11 @@ __device__ __forceinline__ void export_store_nt(uint4 *p, const uint4 &v) {
 // element of generic instance j at list position k (k is wave-uniform: the table lookups are scalar loads)
 __device__ __forceinline__ ExportElement export_generic_element(const ExportArgs &a, uint32_t k, uint64_t j, bool &assigned) {
     const uint32_t w = a.sel ? a.sel[k] : k;
-    uint32_t row = 0xFFFFFFFFu, ui = 0xFFFFFFFFu;
-    if (w < a.n_witnesses && a.producer[w] != 0xFFFFFFFFu) {
-        row = a.row_of ? a.row_of[w] : w;
-        if (a.u_index) ui = a.u_index[w];
-    }
-    assigned = row != 0xFFFFFFFFu;
+    struct { uint32_t row, ui; } g;  // (one aggregate: with two scalars the compiler names two SGPRs of these kernels differently, nothing else)
+    export_generic_source(w, a.n_witnesses, a.row_of, a.producer, a.u_index, g.row, g.ui);
+    assigned = g.row != 0xFFFFFFFFu;
     if (!assigned) return export_encode(fr_zero(), fr_zero(), a.encoding, false);
-    return export_encode(fr_load_nt(a.W, row, a.Bp, j), ui != 0xFFFFFFFFu ? fr_const(a.u_factor, ui) : export_plain_factor(a.encoding), a.encoding, true);
+    return export_encode(fr_load_nt(a.W, g.row, a.Bp, j), g.ui != 0xFFFFFFFFu ? fr_const(a.u_factor, g.ui) : export_plain_factor(a.encoding), a.encoding, true);
 }
 // direct: lane = instance, blockIdx.y = list position. Witness-major, a wave reads 1 KiB per half row and writes 64 x 32 contiguous bytes; no LDS.
 // Also the instance-major kernel of a list shorter than the tiled kernel's four waves (the return witness of a tile: at one position the two
@@ -242,7 +240,7 @@ __global__ void __launch_bounds__(256) export_device_lanes_kernel(const ExportAr
     if (x >= n_lanes) return;
     const uint32_t t = lanes[2 * x], i = lanes[2 * x + 1];
     const uint32_t w = a.sel ? a.sel[k] : k;
-    const bool assigned = w < a.n_witnesses && ((assigned_bits[(uint64_t)(w >> 5) * n_slow + t] >> (w & 31u)) & 1u) != 0u;
+    const bool assigned = export_lane_assigned(assigned_bits, n_slow, t, w, a.n_witnesses);
     ExportElement e;
     if (assigned) e = export_encode(fr_load(a.W, w, a.Bp, side ? (uint64_t)t : (uint64_t)a.first + i), export_plain_factor(a.encoding), a.encoding, true);
     else e = export_encode(fr_zero(), fr_zero(), a.encoding, false);
@@ -271,7 +269,7 @@ __device__ __forceinline__ ExportElement export_list_element(const ExportArgs &a
     }
     if (r.lane < 0) return export_generic_element(a, k, r.j, assigned);
     const uint32_t w = a.sel ? a.sel[k] : k;
-    assigned = w < a.n_witnesses && ((L.assigned_bits[(uint64_t)(w >> 5) * L.n_slow + (uint32_t)r.lane] >> (w & 31u)) & 1u) != 0u;
+    assigned = export_lane_assigned(L.assigned_bits, L.n_slow, (uint32_t)r.lane, w, a.n_witnesses);
     if (!assigned) return export_encode(fr_zero(), fr_zero(), a.encoding, false);
     return export_encode(fr_load(L.Wx, w, L.Bpx, L.side ? (uint64_t)(uint32_t)r.lane : (uint64_t)r.j), export_plain_factor(a.encoding), a.encoding, true);
 }

@@ -162,6 +162,23 @@ void launch_export_device_list(hipStream_t s, const ExportDevice &x, const uint4
                                const uint32_t *u_factor, const ExportListSource &src);
 void launch_export_narrow_list(hipStream_t s, const ExportDevice &x, const uint4 *W, uint64_t Bp, const uint32_t *row_of, const uint32_t *producer, const Unscale &u,
                                const ExportListSource &src);
+// ---- kernels_records_out.hip (acvm_batch_export_device_records): output row i writes its fields into the record at out + i * pitch, any
+// alignment; row i is instance src.list[i], or first + i where src.list is null (the rest of src as for the list export: the exact lanes are
+// found through lane_of either way). windows / fields: the device tables of record_out_plan.hpp, the encoding per field. u_plain / u_m256: the
+// factor rows of the scaled witnesses for every encoding but Montgomery-256 / for it (null where no field takes it).
+struct RecordExport {
+    const uint4 *W;
+    uint64_t Bp;
+    uint32_t first, n;
+    ExportListSource src;
+    uint32_t n_witnesses;  // a field's witness >= n_witnesses is unassigned
+    const uint32_t *row_of, *producer;
+    const uint32_t *u_index, *u_plain, *u_m256;
+    uint8_t *out;
+    uint64_t pitch;
+    const uint32_t *windows, *fields;
+};
+void launch_export_records(hipStream_t s, const RecordExport &x, uint32_t n_windows);
 // ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
 // {status, err, opcode index, index in the range} over them; any column may be null
 void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);

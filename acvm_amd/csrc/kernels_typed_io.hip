@@ -11,6 +11,7 @@
 #include "ops_common.hpp"
 #include "kernels.hpp"
 #include "import_decode.hpp"
+#include "export_source.hpp"
 
 namespace acvm {
 
@@ -157,11 +158,8 @@ __device__ __forceinline__ void narrow_write(uint8_t *p, const uint4 &v, uint32_
 // element of generic instance j at list position k (k is wave-uniform: the table lookups are scalar loads): kernels.hip export_generic_element
 __device__ __forceinline__ ExportNarrow narrow_generic_element(const NarrowExportArgs &a, uint32_t k, uint64_t j) {
     const uint32_t w = a.sel ? a.sel[k] : k;
-    uint32_t row = 0xFFFFFFFFu, ui = 0xFFFFFFFFu;
-    if (w < a.n_witnesses && a.producer[w] != 0xFFFFFFFFu) {
-        row = a.row_of ? a.row_of[w] : w;
-        if (a.u_index) ui = a.u_index[w];
-    }
+    uint32_t row, ui;
+    export_generic_source(w, a.n_witnesses, a.row_of, a.producer, a.u_index, row, ui);
     if (row == 0xFFFFFFFFu) return export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
     return export_encode_narrow(fr_load_nt(a.W, row, a.Bp, j), ui != 0xFFFFFFFFu ? fr_const(a.u_factor, ui) : export_plain_factor(EXPORT_ENC_LE32), a.size, true);
 }
@@ -220,7 +218,7 @@ __global__ void __launch_bounds__(256) export_narrow_lanes_kernel(const NarrowEx
     if (x >= n_lanes) return;
     const uint32_t t = lanes[2 * x], i = lanes[2 * x + 1];
     const uint32_t w = a.sel ? a.sel[k] : k;
-    const bool assigned = w < a.n_witnesses && ((assigned_bits[(uint64_t)(w >> 5) * n_slow + t] >> (w & 31u)) & 1u) != 0u;
+    const bool assigned = export_lane_assigned(assigned_bits, n_slow, t, w, a.n_witnesses);
     ExportNarrow e;
     if (assigned) e = export_encode_narrow(fr_load(a.W, w, a.Bp, side ? (uint64_t)t : (uint64_t)a.first + i), export_plain_factor(EXPORT_ENC_LE32), a.size, true);
     else e = export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
@@ -234,7 +232,7 @@ __device__ __forceinline__ ExportNarrow narrow_list_element(const NarrowExportAr
     if (j >= L.B) return export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
     if (lane < 0) return narrow_generic_element(a, k, j);
     const uint32_t w = a.sel ? a.sel[k] : k;
-    const bool assigned = w < a.n_witnesses && ((L.assigned_bits[(uint64_t)(w >> 5) * L.n_slow + (uint32_t)lane] >> (w & 31u)) & 1u) != 0u;
+    const bool assigned = export_lane_assigned(L.assigned_bits, L.n_slow, (uint32_t)lane, w, a.n_witnesses);
     if (!assigned) return export_encode_narrow(fr_zero(), fr_zero(), a.size, false);
     return export_encode_narrow(fr_load(L.Wx, w, L.Bpx, L.side ? (uint64_t)(uint32_t)lane : (uint64_t)j), export_plain_factor(EXPORT_ENC_LE32), a.size, true);
 }

@@ -792,8 +792,8 @@ uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b);
  *     host-to-device copy is made: the field table, which is reused while it does not change (acvm_debug_import_list_copies counts it).
  *     Works with ACVM_BATCH_REUSE_SLOTS (rows are not ids), with a caller's solver, and after acvm_batch_set_instances.
  * acvm_batch_set_initial_witness_records is the host form: B * pitch bytes go through the handle's staging buffer, then the device path runs.
- * Not here: record EXPORT; a mask byte inside the record; an acvm_batch_solve_then_import form; records for the lanes of
- * acvm_node_solve_device; big-endian or sign-extending narrow fields.
+ * Not here: a mask byte inside the record (the record EXPORT below writes one); an acvm_batch_solve_then_import form; records for the lanes
+ * of acvm_node_solve_device; big-endian or sign-extending narrow fields.
  */
 typedef struct {
     uint32_t position;   /* which initial witness: position in the initial_ids given to acvm_batch_new */
@@ -807,6 +807,55 @@ typedef struct {
 } acvm_record_desc_t;
 int acvm_batch_import_device_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *d_records);
 int acvm_batch_set_initial_witness_records(acvm_batch_t *b, const acvm_record_desc_t *d, const void *records /* host */);
+/*
+ * Record export: the way out in the same form. Each instance of the range (or of a device list of instances) becomes one packed record of
+ * mixed-width fields -- { digest: [u8; 32], root: Field, idx: u32, ok: bool } -- in the caller's device buffer: what the record import of the
+ * next circuit reads, a database row, a Rust #[repr(C, packed)] slice. A field is a witness, an encoding, a byte offset, and optionally the
+ * offset of a mask byte.
+ *   - Addressing: row i writes its field at byte i * pitch + offset of d_records. d_records, pitch and every offset may have ANY alignment.
+ *   - Values: byte for byte what acvm_batch_export_device writes for that witness, instance and encoding -- scaled, relaxed and recycled rows
+ *     and the instances of the exact path are handled as there. A field of ACVM_ENC_MONT256_LE takes the Montgomery-256 factor table, every
+ *     other field the plain one; both can be live in one call. An unassigned element is zero bytes. A witness index >=
+ *     acvm_circuit_num_witnesses is unassigned. A witness may appear in several fields, say as ACVM_ENC_U8 and as ACVM_ENC_BE32.
+ *   - Mask byte: for a 32-byte field 0 or 1; for a narrow field 0, 1 or 2 -- 2: assigned, but the value does not fit the width; the low bytes
+ *     are written all the same.
+ *   - What is never written: a byte of the buffer that no field and no mask byte covers -- not the padding inside a record, not the bytes
+ *     before d_records, not the bytes behind d_records + n * pitch, even where they share an aligned dword with a covered byte. No byte of
+ *     d_records is ever loaded: there is no read-modify-write of global memory.
+ *   - d_instances (DEVICE) or NULL: with a list, rows are read as by acvm_batch_export_device_list -- any order, repeats allowed, an entry at or
+ *     beyond the live count is an instance that assigned nothing -- and first must be 0, n the list's length. NULL: row i is instance first + i.
+ *     The instances of the exact path are found through the handle's lane map, with its rule for host-to-device traffic;
+ *     acvm_debug_export_h2d_bytes counts this call too.
+ *   - Refused with ACVM_E_INVALID, the message naming the field, nothing enqueued: a null descriptor; null fields with n_fields > 0; an unknown
+ *     encoding; offset + size > pitch or mask_offset >= pitch (judged without overflow); two covered byte ranges that overlap -- elements and
+ *     mask bytes alike, unlike the import, where overlapping reads are harmless; a range beyond the live instances; first != 0 with a list; a
+ *     null buffer while there is something to write.
+ *   - ACVM_E_STATE exactly where acvm_batch_export_device returns it for the same witness set: not solved; a witness that was not kept under
+ *     ACVM_BATCH_REUSE_SLOTS; after acvm_batch_solve_then_import.
+ *   - n_fields == 0 or n == 0 writes nothing and succeeds.
+ *   - Synchronous like the export. At most one small host-to-device copy is made -- the window and field tables -- which is reused while they
+ *     do not change.
+ * acvm_batch_witness_records is the host form: the device path runs into a zero-filled staging buffer, then n * pitch bytes are copied down.
+ * Here the padding IS written, as zero.
+ * Not here: a node form; an asynchronous variant; outcome columns (status, err) as record fields; a mask byte for the record import;
+ * big-endian or sign-extending narrow fields.
+ */
+#define ACVM_RECORD_NO_MASK UINT64_MAX
+typedef struct {
+    uint32_t witness;      /* witness index; one >= acvm_circuit_num_witnesses is unassigned, as in the export */
+    uint32_t encoding;     /* any ACVM_ENC_*: BE32, LE32, MONT256_LE, U8 .. U128 */
+    uint64_t offset;       /* byte offset of the element inside a record; ANY alignment */
+    uint64_t mask_offset;  /* byte offset of this field's mask byte inside the record, or ACVM_RECORD_NO_MASK */
+} acvm_record_out_field_t;
+typedef struct {
+    uint64_t pitch;                          /* bytes from one record to the next */
+    const acvm_record_out_field_t *fields;   /* HOST, copied before the call returns */
+    uint32_t n_fields;
+    uint32_t first, n;                       /* instances [first, first + n); with a list: first == 0, n = its length */
+} acvm_record_out_desc_t;
+int acvm_batch_export_device_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, const uint32_t *d_instances /* DEVICE, or NULL = the range */,
+                                     void *d_records);
+int acvm_batch_witness_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, void *records /* host, n * pitch bytes */);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):
