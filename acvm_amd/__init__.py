@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "acvm_tuning_set", "acvm_tuning_get", "acvm_tuning_key",
     "acvm_device_release_tables", "acvm_circuit_opcode_kinds", "acvm_batch_error_expression", "acvm_debug_stream_rate", "acvm_node_new", "acvm_node_free", "acvm_node_tile_instances", "acvm_node_num_devices", "acvm_node_solve", "acvm_node_stats",
     "acvm_debug_cpulist", "acvm_debug_device_locality", "acvm_debug_plan_fingerprint", "acvm_circuit_plans_built", "acvm_circuit_check_schedule", "acvm_batch_digest_blake2s",
-    "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch",
+    "acvm_batch_export_device", "acvm_device_download", "acvm_debug_fr", "acvm_debug_inverse_batch", "acvm_debug_inverse_batch_shared",
     "acvm_batch_import_device", "acvm_batch_solve_then_import_ex",
     "acvm_batch_import_device_parts", "acvm_debug_import_list_copies",
     "acvm_batch_import_device_masked", "acvm_batch_set_initial_witness_masked", "acvm_debug_import_missing",
@@ -502,6 +502,9 @@ def lib():
         L.acvm_debug_fr.argtypes = [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.acvm_debug_inverse_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint32)]
+    if hasattr(L, "acvm_debug_inverse_batch_shared"):
+        L.acvm_debug_inverse_batch_shared.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.acvm_debug_secp_rate.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     L.acvm_circuit_opcode_kinds.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.acvm_batch_error_expression.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(ExpressionHead), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -799,8 +802,9 @@ def debug_fr(what, items, uniform=None):
     return out
 
 
-def debug_inverse_batch(den, inv_chunk, slot_of=None):
+def debug_inverse_batch(den, inv_chunk, slot_of=None, inv_share=None):
     """The shipped inversion batch on denominators of the caller's (see include/acvm_amd.h): den = uint32 [n_jobs][B][8], canonical storage form.
+    inv_share: the waves that share one field inversion (None: the process-wide tuning's).
     Returns (inverse-table rows [n_jobs][B][8], row slot_of[k] for job k; event words [B]; the device's count of flagged instances; the host counter)."""
     import numpy as np
     d = np.ascontiguousarray(den, dtype=np.uint32)
@@ -809,8 +813,12 @@ def debug_inverse_batch(den, inv_chunk, slot_of=None):
     s = None if slot_of is None else np.ascontiguousarray(slot_of, dtype=np.uint32).reshape(n_jobs)
     inv, ev = np.zeros((n_jobs, B, 8), dtype=np.uint32), np.zeros(B, dtype=np.uint32)
     dc, hc = C.c_uint32(), C.c_uint32()
-    _check(lib().acvm_debug_inverse_batch(d.ctypes.data, n_jobs, B, inv_chunk, None if s is None else s.ctypes.data, inv.ctypes.data, ev.ctypes.data,
-                                          C.byref(dc), C.byref(hc)))
+    if inv_share is None:
+        _check(lib().acvm_debug_inverse_batch(d.ctypes.data, n_jobs, B, inv_chunk, None if s is None else s.ctypes.data, inv.ctypes.data, ev.ctypes.data,
+                                              C.byref(dc), C.byref(hc)))
+    else:
+        _check(lib().acvm_debug_inverse_batch_shared(d.ctypes.data, n_jobs, B, inv_chunk, inv_share, None if s is None else s.ctypes.data, inv.ctypes.data,
+                                                     ev.ctypes.data, C.byref(dc), C.byref(hc)))
     return inv, ev, dc.value, hc.value
 
 

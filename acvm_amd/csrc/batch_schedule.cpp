@@ -71,7 +71,8 @@ static int enqueue_level_schedule(acvm_batch *b, LaunchTimers *tm) {
                 if (int rc = run_host_blackbox(b, p.prog[p.cls_offset[k][st.first + r] + 1], false, 0)) return rc;
             break;
         case SO_INVERSE:
-            launch_inverse_batch(s, b->d_W, b->d_inv, b->Bp, b->B, b->d_gate_stream, b->d_dyn_offset + st.first, st.count, b->d_event, (uint32_t)p.tune.inv_chunk);
+            launch_inverse_batch(s, b->d_W, b->d_inv, b->Bp, b->B, b->d_gate_stream, b->d_dyn_offset + st.first, st.count, b->d_event, (uint32_t)p.tune.inv_chunk,
+                                 inverse_share_clamp(p.tune.inv_share));
             break;
         case SO_TRUNCATE: launch_event_truncate(s, b->d_event, b->B, p.truncated_at); break;
         }

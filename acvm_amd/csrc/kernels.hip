@@ -374,6 +374,32 @@ __global__ void __launch_bounds__(64) inverse_batch_kernel(const uint4 *__restri
     const uint32_t n = n_jobs - first < chunk ? n_jobs - first : chunk;
     inverse_batch_body<InverseDevicePolicy>(W, Inv, Bp, j, gate_stream, job_offset, first, n, event);
 }
+// The same with ONE field inversion for the corresponding lanes of the G waves of a workgroup (inverse_batch.hpp, the share step): wave w of block x
+// owns instances (x G + w) 64 + lane, every wave of the block works on chunk blockIdx.y (the same n for all of them). Global accesses are the
+// one-wave kernel's, row for row; the totals and 1 / (their product) pass through (G + 1) rows of LDS. Every thread reaches both barriers: a lane
+// (or a whole wave) past B is predicated off, contributes the Montgomery one as its total and loads and stores nothing. Wave 0 always has a live
+// lane (grid.x = ceil(waves / G)) and runs the inversion.
+template <int G>
+__global__ void __launch_bounds__(64 * G) inverse_batch_kernel_shared(const uint4 *__restrict__ W, uint4 *__restrict__ Inv, uint64_t Bp, uint32_t B,
+                                                                      const uint32_t *__restrict__ gate_stream, const uint32_t *__restrict__ job_offset,
+                                                                      uint32_t n_jobs, uint32_t chunk, uint32_t *__restrict__ event) {
+    __shared__ uint32_t rows[(G + 1) * INVERSE_SHARE_ROW_WORDS];
+    const uint32_t lane = threadIdx.x & 63u, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t j = (uint64_t)blockIdx.x * (64 * G) + threadIdx.x;
+    const bool live = j < B;
+    const uint32_t first = blockIdx.y * chunk;
+    const uint32_t n = n_jobs - first < chunk ? n_jobs - first : chunk;
+    Fr29 total = fr29_from(fr_one());
+    if (live) total = inverse_batch_forward<InverseDevicePolicy>(W, Inv, Bp, j, gate_stream, job_offset, first, n, event);
+    inverse_share_row_store(rows, w, lane, total);
+    __syncthreads();
+    const InverseShareRows totals{rows, lane};
+    if (w == 0) inverse_share_row_store(rows, G, lane, inverse_share_total_inverse<G>(totals));
+    __syncthreads();
+    if (live)
+        inverse_batch_backward<InverseDevicePolicy>(W, Inv, Bp, j, gate_stream, job_offset, first, n,
+                                                    inverse_share_own<G>(totals, inverse_share_row_load(rows, G, lane), w));
+}
 
 // ------------------------------------------------------------------------------------------ self test
 // Cross-checks the hand-scheduled field routines against the portable ones on pseudo-random operands:
@@ -679,15 +705,18 @@ void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const 
     }
 }
 void launch_inverse_batch(hipStream_t s, const uint4 *W, uint4 *inv, uint64_t Bp, uint32_t B, const uint32_t *gate_stream,
-                          const uint32_t *job_offset, uint32_t n_jobs, uint32_t *event, uint32_t inv_chunk) {
+                          const uint32_t *job_offset, uint32_t n_jobs, uint32_t *event, uint32_t inv_chunk, uint32_t inv_share) {
     if (!n_jobs || !B) return;
+    // waves to a field inversion (tuning.hpp inv_share): 1 = the one-wave kernel, else the workgroup of G waves of inverse_batch_kernel_shared<G>
+    const uint32_t G = inverse_share_clamp(inv_share), waves = (B + 63) / 64;
+    const auto kernel = G == 8 ? inverse_batch_kernel_shared<8> : G == 4 ? inverse_batch_kernel_shared<4> : G == 2 ? inverse_batch_kernel_shared<2> : inverse_batch_kernel;
     // jobs per wave: at most inv_chunk (the PLAN's snapshot of the tuning, like every other knob of a handle: one field inversion, ~13 500
     // instructions, is shared by a wave's jobs: ~1 000 each), spread evenly over the waves
     const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(inv_chunk, 1), 65536), n_chunks = (n_jobs + cap - 1) / cap;
     const uint32_t chunk = (n_jobs + n_chunks - 1) / n_chunks;
     for (uint32_t done = 0; done < n_jobs;) {  // (grid.y holds 65 535 chunks)
         const uint32_t n = (uint32_t)std::min<uint64_t>(n_jobs - done, (uint64_t)chunk * 65535u);
-        hipLaunchKernelGGL(inverse_batch_kernel, dim3((B + 63) / 64, (n + chunk - 1) / chunk), dim3(64), 0, s, W, inv, Bp, B, gate_stream, job_offset + done, n, chunk, event);
+        hipLaunchKernelGGL(kernel, dim3((waves + G - 1) / G, (n + chunk - 1) / chunk), dim3(64 * G), 0, s, W, inv, Bp, B, gate_stream, job_offset + done, n, chunk, event);
         done += n;
     }
 }

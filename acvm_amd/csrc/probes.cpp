@@ -263,8 +263,9 @@ int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uin
 
 // The shipped inverse_batch_kernel through its launcher on a table made for the call: row k of W = the denominators of job k, job k = {row k, opcode
 // k, inverse slot slot_of[k] (k when null)}, the batch's row stride, event words behind the header a batch gives them (event_words_new).
-int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
-                             uint32_t *event_out, uint32_t *device_count, uint32_t *host_count) try {
+// (inv_share: the waves to a field inversion, as the launcher takes them)
+static int debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, uint32_t inv_share, const uint32_t *slot_of, uint32_t *inv_out,
+                               uint32_t *event_out, uint32_t *device_count, uint32_t *host_count) {
     if (!den || !n_jobs || !B || !inv_out || !event_out || !device_count || !host_count) return set_err(ACVM_E_INVALID, "bad argument");
     if (slot_of) {  // a permutation of [0, n_jobs): every job owns one row of the inverse table
         std::vector<uint8_t> seen(n_jobs, 0);
@@ -306,7 +307,7 @@ int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, u
     if (int rc = event_words_new(B, &m.event_base, &m.event, &m.h_count)) return rc;
     *m.h_count = 0;
     launch_event_reset(nullptr, m.event, B);
-    launch_inverse_batch(nullptr, m.W, m.inv, Bp, B, m.stream, m.offset, n_jobs, m.event, inv_chunk);
+    launch_inverse_batch(nullptr, m.W, m.inv, Bp, B, m.stream, m.offset, n_jobs, m.event, inv_chunk, inv_share);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(hW.data(), m.inv, table_bytes, hipMemcpyDeviceToHost));
@@ -320,6 +321,16 @@ int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, u
             v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
         }
     return 0;
+}
+// ... with the process-wide inv_share (what a handle created now would snapshot): the shipped default unless the caller set another
+int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
+                             uint32_t *event_out, uint32_t *device_count, uint32_t *host_count) try {
+    return debug_inverse_batch(den, n_jobs, B, inv_chunk, inverse_share_clamp(tuning().inv_share), slot_of, inv_out, event_out, device_count, host_count);
+} ABI_CATCH
+// ... with inv_share of the caller's (1, 2, 4, 8; anything else: the next lower of those)
+int acvm_debug_inverse_batch_shared(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, uint32_t inv_share, const uint32_t *slot_of,
+                                    uint32_t *inv_out, uint32_t *event_out, uint32_t *device_count, uint32_t *host_count) try {
+    return debug_inverse_batch(den, n_jobs, B, inv_chunk, inverse_share_clamp(inv_share), slot_of, inv_out, event_out, device_count, host_count);
 } ABI_CATCH
 
 // The shipped selection kernels through their launcher on a status array of the caller's (kernels_select.hip launch_select). The device's list starts as the

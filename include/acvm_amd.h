@@ -252,9 +252,14 @@ int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uin
  * carries opcode index k and owns row slot_of[k] of the inverse table (null: row k; otherwise a permutation of [0, n_jobs)); the rows have the batch's
  * stride, the event words the header of a batch. inv_chunk: the tuning's jobs per wave. Out: inv_out [n_jobs][B] x 8 u32 = the RAW rows of the
  * inverse table (row slot_of[k] holds 1 / den[k]), event_out [B] event words, *device_count = the device's count of flagged instances (the word four in
- * front of the event words), *host_count = the host-mapped counter the same kernels keep. */
+ * front of the event words), *host_count = the host-mapped counter the same kernels keep. The waves that share one field inversion are the
+ * process-wide tuning's ("inv_share": what a handle created now would get). */
 int acvm_debug_inverse_batch(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, const uint32_t *slot_of, uint32_t *inv_out,
                              uint32_t *event_out, uint32_t *device_count, uint32_t *host_count);
+/* The same with inv_share of the caller's: 1 = the one-wave kernel, 2 / 4 / 8 = the workgroup of that many waves around one field inversion (anything
+ * else: the next lower of those). The rows of a lane without a zero denominator do not depend on it, bit for bit. */
+int acvm_debug_inverse_batch_shared(const uint32_t *den, uint32_t n_jobs, uint32_t B, uint32_t inv_chunk, uint32_t inv_share, const uint32_t *slot_of,
+                                    uint32_t *inv_out, uint32_t *event_out, uint32_t *device_count, uint32_t *host_count);
 /* The ordered selection of acvm_batch_outcomes_device (the shipped kernels through their launcher) on a status array of the caller's, host in and host
  * out: out_list[0 .. *n_selected) = the i < n, ascending, with bit status[i] of select_mask set (a status byte of 32 or more is never selected); what
  * lies behind *n_selected in out_list ([n] capacity) keeps the caller's bytes. out_list may be NULL: the count alone. */
