@@ -770,11 +770,12 @@ def debug_table_read(table, entries):
     return out
 
 
-SECP_PROBE_WORDS = ((2, 1), (1, 1), (2, 1), (2, 1), (1, 1), (1, 1), (3, 3), (5, 3), (1, 1), (2, 1), (2, 1), (1, 1))
+SECP_PROBE_WORDS = ((2, 1), (1, 1), (2, 1), (2, 1), (1, 1), (1, 1), (3, 3), (5, 3), (1, 1), (2, 1), (2, 1), (1, 1),
+                    (2, 1), (1, 1), (1, 4), (4, 3), (6, 2))
 
 
 def debug_secp(curve, what, items):
-    """Component probe of the ECDSA kernels (see include/acvm_amd.h): items = tuples of ints (values < p); returns one tuple of ints per item."""
+    """Component probe of the ECDSA kernels (see include/acvm_amd.h): items = tuples of ints (values < p; 12..16: below 2^256); returns one tuple of ints per item."""
     wi, wo = SECP_PROBE_WORDS[what]
     assert all(len(it) == wi for it in items)
     data = b"".join(int(v).to_bytes(32, "big") for it in items for v in it)

@@ -60,10 +60,16 @@ void launch_secp_rate(hipStream_t s, uint32_t curve, uint32_t *out, uint32_t blo
 // (8..11: compositions the point formulas and the square root are made of, see the code)
 // what: 0 a b -> a b | 1 a -> a^2 | 2 a b -> a + b | 3 a b -> a - b | 4 a -> 1 / a | 5 a -> a^((p + 1) / 4)      (mod p, one word out)
 //       6 X Y Z -> 2 (X, Y, Z) | 7 X Y Z x y -> (X, Y, Z) + (x, y)                                                  (Jacobian, three words out)
+//       12 a b -> a b | 13 a -> 1 / a (0 for 0)                                                                          (mod n, one word out)
+//       14 k -> |k1| neg1 |k2| neg2 of secp256k1's endomorphism split (curve 0 only: acvm_debug_secp refuses curve 1)  (four words out)
+//       15 u1 qx qy u2 -> X Y Z of u1 G + u2 (qx, qy) as secp_verify calls secp_mul2 (Q affine, canonical)               (Jacobian, three words out)
+//       16 r s x y n_msg z -> result panic of secp_verify with y given, as ecdsa_verify_values calls it                  (two words out)
+// gtab: the generator table of curve C (15, 16 only)
 template <int C>
-__device__ void secp_probe_item(uint32_t what, const uint32_t *in, uint32_t *out) {
+__device__ void secp_probe_item(uint32_t what, const uint32_t *in, uint32_t *out, const uint32_t *__restrict__ gtab) {
     auto ld = [&](uint32_t i) { Fr c; for (int k = 0; k < 8; k++) c.v[k] = in[8 * i + k]; return c; };
     auto st = [&](uint32_t i, const Fr &c) { for (int k = 0; k < 8; k++) out[8 * i + k] = c.v[k]; };
+    auto word = [&](uint32_t v) { Fr c = fr_zero(); c.v[0] = v; return c; };
     if (what == 0) st(0, sp_mul<C>(ld(0), ld(1)));
     else if (what == 1) st(0, sp_sqr<C>(ld(0)));
     else if (what == 2) st(0, sp_add<C>(ld(0), ld(1)));
@@ -80,17 +86,32 @@ __device__ void secp_probe_item(uint32_t what, const uint32_t *in, uint32_t *out
         const SJac p{sp_enter<C>(ld(0)), sp_enter<C>(ld(1)), sp_enter<C>(ld(2))};
         const SJac r = what == 6 ? sj_dbl<C>(p) : sj_add_aff<C>(p, SAff{sp_store<C>(sp_enter<C>(ld(3))), sp_store<C>(sp_enter<C>(ld(4)))});
         st(0, sp_leave<C>(r.X)); st(1, sp_leave<C>(r.Y)); st(2, sp_leave<C>(r.Z));
+    } else if (what == 12) st(0, sn_mul<C>(ld(0), ld(1)));
+    else if (what == 13) st(0, sn_inv<C>(ld(0)));
+    else if (what == 14) {
+        const SecpSplit sp = secp256k1_split_lambda(ld(0));
+        st(0, sp.k1); st(1, word(sp.neg1 ? 1u : 0u)); st(2, sp.k2); st(3, word(sp.neg2 ? 1u : 0u));
+    } else if (what == 15) {
+        const SJac r = secp_mul2<C>(ld(0), sp_load(sp_store<C>(sp_enter<C>(ld(1)))), sp_load(sp_store<C>(sp_enter<C>(ld(2)))), ld(3), gtab);
+        st(0, sp_leave<C>(r.X)); st(1, sp_leave<C>(r.Y)); st(2, sp_leave<C>(r.Z));
+    } else if (what == 16) {
+        const Fr y = ld(3);
+        uint32_t panic = 0;
+        const uint32_t ok = secp_verify<C>(ld(0), ld(1), ld(2), y.v[0] & 1u, ld(4).v[0], ld(5), gtab, &panic, &y);
+        st(0, word(ok)); st(1, word(panic));
     }
 }
 __global__ void __launch_bounds__(64) secp_probe_kernel(uint32_t curve, uint32_t what, const uint32_t *__restrict__ in, uint32_t n_items, uint32_t words_in, uint32_t words_out,
-                                                        uint32_t *__restrict__ out) {
+                                                        uint32_t *__restrict__ out, const uint32_t *__restrict__ gtabs) {
     const uint32_t t = blockIdx.x * 64 + threadIdx.x;
     if (t >= n_items) return;
-    if (curve == 0u) secp_probe_item<0>(what, in + (size_t)t * words_in * 8, out + (size_t)t * words_out * 8);
-    else secp_probe_item<1>(what, in + (size_t)t * words_in * 8, out + (size_t)t * words_out * 8);
+    if (curve == 0u) secp_probe_item<0>(what, in + (size_t)t * words_in * 8, out + (size_t)t * words_out * 8, gtabs);
+    else secp_probe_item<1>(what, in + (size_t)t * words_in * 8, out + (size_t)t * words_out * 8, gtabs ? gtabs + SECP_GTABLE_WORDS : nullptr);
 }
-void launch_secp_probe(hipStream_t s, uint32_t curve, uint32_t what, const uint32_t *in, uint32_t n_items, uint32_t words_in, uint32_t words_out, uint32_t *out) {
-    if (n_items) hipLaunchKernelGGL(secp_probe_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, curve, what, in, n_items, words_in, words_out, out);
+// gtabs: the generator tables of both curves (ecdsa_generator_tables) for what = 15, 16; the other probes read no table and take nullptr
+void launch_secp_probe(hipStream_t s, uint32_t curve, uint32_t what, const uint32_t *in, uint32_t n_items, uint32_t words_in, uint32_t words_out, uint32_t *out,
+                       const uint32_t *gtabs) {
+    if (n_items) hipLaunchKernelGGL(secp_probe_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, curve, what, in, n_items, words_in, words_out, out, gtabs);
 }
 
 // the tables of both curves (grumpkin_host.cpp keeps them in the device's table set and builds them on the set's stream)

@@ -104,10 +104,29 @@ int acvm_debug_stream_rate(size_t bytes, double *gb_per_s) {
 // 1 device hash_single(in[0], parity = param), 2 device hash-ladder compress(in[0..n_in)), 3 device fixed_base_mul(table
 // base param, integer in[0]), 4 device table point. in: n_in x 32 bytes big-endian; out: 64 bytes (x || y) big-endian.
 int acvm_debug_secp(uint32_t curve, uint32_t what, const uint8_t *in_be32, uint32_t n_items, uint8_t *out_be32) try {
-    static const uint32_t WIN[12] = {2, 1, 2, 2, 1, 1, 3, 5, 1, 2, 2, 1}, WOUT[12] = {1, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1};
-    if (curve > 1u || what > 11u || !in_be32 || !out_be32) return set_err(ACVM_E_INVALID, "bad argument");
+    static const uint32_t WIN[17] = {2, 1, 2, 2, 1, 1, 3, 5, 1, 2, 2, 1, 2, 1, 1, 4, 6}, WOUT[17] = {1, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 1, 1, 4, 3, 2};
+    if (curve > 1u || what > 16u || !in_be32 || !out_be32) return set_err(ACVM_E_INVALID, "bad argument");
+    if (what == 14u && curve != 0u) return set_err(ACVM_E_INVALID, "the endomorphism split (what = 14) is secp256k1's: curve 0 only");
     if (!n_items) return 0;
     const uint32_t wi = WIN[what], wo = WOUT[what];
+    // what = 15, 16 read the device's own generator tables (the set dp.ecdsa_g points into): held while the probe runs, from BEFORE it asks for their
+    // address, like acvm_debug_grumpkin holds its tables
+    struct Hold {
+        int d = -1;
+        void take(int dev_) { d = dev_; device_tables_retain(d); }
+        ~Hold() { if (d >= 0) device_tables_unref(d); }
+    } hold;
+    const uint32_t *gtabs = nullptr;
+    if (what >= 15u) {
+        int dev = 0;
+        HIPCHK(hipGetDevice(&dev));
+        hold.take(dev);
+        gtabs = ecdsa_generator_tables();
+        if (!gtabs) {
+            (void)hipGetLastError();
+            return set_err(ACVM_E_DEVICE, "could not build the ECDSA generator tables on the device");
+        }
+    }
     std::vector<uint32_t> in((size_t)n_items * wi * 8, 0), out((size_t)n_items * wo * 8, 0);
     for (size_t i = 0; i < (size_t)n_items * wi; i++)
         for (int k = 0; k < 32; k++) in[8 * i + k / 4] |= (uint32_t)in_be32[32 * i + 31 - k] << (8 * (k % 4));
@@ -116,7 +135,7 @@ int acvm_debug_secp(uint32_t curve, uint32_t what, const uint8_t *in_be32, uint3
     HIPCHK(hipMalloc((void **)&d_out, out.size() * 4));
     HIPCHK(hipMemcpy(d_in, in.data(), in.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(d_out, 0, out.size() * 4));
-    launch_secp_probe(nullptr, curve, what, d_in, n_items, wi, wo, d_out);
+    launch_secp_probe(nullptr, curve, what, d_in, n_items, wi, wo, d_out, gtabs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out.data(), d_out, out.size() * 4, hipMemcpyDeviceToHost));

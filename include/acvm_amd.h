@@ -231,8 +231,13 @@ int acvm_debug_batch_tables(const acvm_batch_t *b, uint32_t *mask);
  * the tests compare with Python): curve 0 = secp256k1, 1 = secp256r1; one device lane per item. what: 0 a b -> a b; 1 a -> a^2; 2 a b -> a + b; 3 a b -> a - b;
  * 4 a -> 1 / a (0 for 0); 5 a -> a^((p + 1) / 4), all mod p; 6 X Y Z -> the Jacobian double; 7 X Y Z x y -> the Jacobian sum with the affine point (x, y);
  * compositions the formulas are made of: 8 a -> a^4 (a product fed to a product); 9 a b -> (a + b)^2 (an unreduced sum into a product); 10 a b -> a - 4 b
- * (a difference against a multiple of p); 11 a -> a^32 (the squaring loop of the square-root chains).
- * in: n_items x (2, 1, 2, 2, 1, 1, 3, 5, 1, 2, 2, 1) x 32 bytes big-endian, values < p; out: n_items x (1, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1) x 32 bytes. */
+ * (a difference against a multiple of p); 11 a -> a^32 (the squaring loop of the square-root chains);
+ * what a verification is made of above the base field: 12 a b -> a b mod n; 13 a -> 1 / a mod n (0 for 0); 14 k -> |k1|, neg1, |k2|, neg2 of secp256k1's
+ * endomorphism split (curve 0 only: ACVM_E_INVALID for curve 1); 15 u1 qx qy u2 -> X Y Z of u1 G + u2 (qx, qy) (Jacobian, Z = 0 for the identity; Q affine and
+ * canonical); 16 r s x y n_msg z -> result, panic code of the whole verification with public_key_y = y, as the opcodes call it. 15 and 16 read the device's
+ * own generator tables (the ones the handles of this device read; built on first use, ACVM_E_DEVICE when they cannot be).
+ * in: n_items x (2, 1, 2, 2, 1, 1, 3, 5, 1, 2, 2, 1, 2, 1, 1, 4, 6) x 32 bytes big-endian, values < p (12..16: any 256-bit value the routine takes);
+ * out: n_items x (1, 1, 1, 1, 1, 1, 3, 3, 1, 1, 1, 1, 1, 1, 4, 3, 2) x 32 bytes. */
 int acvm_debug_secp(uint32_t curve, uint32_t what, const uint8_t *in_be32, uint32_t n_items, uint8_t *out_be32);
 /* Component probe of the BN254-Fr field library (acvm_amd/csrc/fr_device.hpp and the byte helpers of ops_common.hpp run ON THE DEVICE against integers:
  * the tests compare every word with Python, tests/fr_ref.py): one device lane per item, RAW limbs in and out -- S = the storage form, 8 x u32 little-endian,

@@ -216,8 +216,27 @@ def test_ecdsa_black_box_ops(oracle, curve):
         rows.append(be(z) + be(Q[0]) + be(Q[1]) + be(rr) + be(ss))
         rows.append(be(z ^ 2) + be(Q[0]) + be(Q[1]) + be(rr) + be(ss))
     rows.append(be(5) + be(c["p"]) + be(1) + be(1) + be(1))  # x >= p: the reference panics
+    # the eight special rows of tests/secp_cases.py (the generator window that doubles inside the complete addition, the one that cancels and re-enters
+    # from the identity, the sum that IS the identity, z = 0, the extreme recodings of u2): the VM's black-box op is a third inlining context of
+    # secp_device.hpp beside the level kernel and the exact kernel. verify_model is asserted on the oracle's rows, the device against the oracle.
+    import secp_cases as sc
+    from test_secp_device_on_host import CURVES as CV, verify_model
+    from acvm_amd.synth import values_from_rows
+    special = sc.special_rows(curve, 16)
+    for x in special:
+        rr, ss, qx, qy, z = x.sig
+        rows.append(be(z) + be(qx) + be(qy) + be(rr) + be(ss))
+    ores, oasg, ovals = oracle.solve_batch(oracle.Circuit(circ.to_bytes()), ids, values_from_rows(rows), len(rows))
+    for j, x in enumerate(special, start=13):
+        rr, ss, qx, qy, z = x.sig
+        res, panic = verify_model(CV[curve], rr, ss, qx, qy & 1, 32, z)
+        assert (res, panic) == ((0, 5) if j == 15 else (1, 0)), (j, x.label)
+        if panic:
+            assert ores[j].status == 2 and ores[j].err == oracle.E_PANIC and b"identity" in ores[j].message, (j, ores[j].as_tuple(), ores[j].message)
+        else:
+            assert ores[j].status == 0 and oasg[j, 165] and int(ovals[j, 165, 31]) == res, (j, x.label, ores[j].as_tuple())
     ores, _ = both_paths(oracle, circ, ids, rows)
-    assert ores[0].status == 0 and ores[12].err == oracle.E_PANIC
+    assert ores[0].status == 0 and ores[12].err == oracle.E_PANIC and ores[15].err == oracle.E_PANIC
     # wrong array size -> BlackBoxResolutionError::Failed -> BrilligFunctionFailed
     bad = [("Const", 4, 32), ("BlackBox", name, 0, 4, 1, 31, 2, 32, 3, 64, 5), ("Mov", 0, 5), ("Stop",)]
     ores, _ = both_paths(oracle, Circuit(170, [Brillig(inputs=inputs, outputs=[165], bytecode=bad)]), ids, rows[:2])

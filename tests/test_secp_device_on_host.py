@@ -236,3 +236,47 @@ def test_verification(exe, c):
             wants.append(want)
     for l, g, want in zip(lines, ask(exe, lines), wants):
         assert tuple(int(t) for t in g.split()) == want, (l, g, want)
+
+
+# ---- the cases random signatures never reach (tests/secp_cases.py, built for this run's 8-bit generator windows; the device runs them with 16-bit ones)
+def test_endomorphism_split_word_for_word(exe):
+    """every output of secp256k1_split_lambda against libsecp256k1's rounding in integers: the 2 000-sample (40 / 20 scalars at least use digit 128 of
+    k1 / k2, 40 each sign combination) and the fixed shapes"""
+    import secp_cases as sc
+    ks = sc.split_shapes() + list(sc.split_sample()[0])
+    for k, g in zip(ks, ask(exe, [f"0 split {k:x}" for k in ks])):
+        k1, s1, k2, s2 = g.split()
+        assert (int(k1, 16), int(s1), int(k2, 16), int(s2)) == sc.split_lambda(k), hex(k)
+
+
+@pytest.mark.parametrize("c", [0, 1])
+def test_exceptional_sums(exe, c):
+    """u1 G + u2 Q of families A..E through secp_mul2: collisions with the generator windows (doubling inside the addition, cancel and re-entry
+    from the identity, the identity as the result), the shapes of u1, the extreme recodings of u2, the special keys"""
+    import secp_cases as sc
+    cv = CURVES[c]
+    cs = sc.cases(c, 8)
+    lines = [f"{c} mul2 {x.u1:x} {x.Q[0]:x} {x.Q[1]:x} {x.u2:x}" for x in cs]
+    n = cv["n"]
+    extra = [(0, 0), (1, 0), (n - 1, 0), (0, 1), (n - 1, 1), (1, n - 1)]  # u2 = 0 makes no signature; with Q = G
+    lines += [f"{c} mul2 {u1:x} {cv['g'][0]:x} {cv['g'][1]:x} {u2:x}" for u1, u2 in extra]
+    want = [x.R for x in cs] + [ec_mul(cv, (u1 + u2) % n, cv["g"]) for u1, u2 in extra]
+    assert sum(w is None for w in want) >= 3
+    for l, g, w, label in zip(lines, ask(exe, lines), want, [x.label for x in cs] + ["Q = G"] * len(extra)):
+        X, Y, Z = (int(t, 16) for t in g.split())
+        assert affine(cv, X, Y, Z) == w and (Z == 0) == (w is None), (label, l, g)
+
+
+@pytest.mark.parametrize("c", [0, 1])
+def test_exceptional_verifications(exe, c):
+    """the signatures of families A..E (three forms of y, high-S mirror, flipped digest bit) and the panic shapes through secp_verify, with the
+    parity of y alone and with y given. Panic 6 needs R.x in [n, p), a 2^-128 event nobody can construct: it is not among the outcomes."""
+    import secp_cases as sc
+    rows = sc.verification_rows(c, 8)
+    lines = [f"{c} verify {r:x} {s:x} {x:x} {y & 1} {nm} {z:x}" for _, (r, s, x, y, nm, z), _ in rows]
+    lines += [f"{c} verifyy {r:x} {s:x} {x:x} {y:x} {nm} {z:x}" for _, (r, s, x, y, nm, z), _ in rows]
+    seen = set()
+    for l, g, (label, _, want) in zip(lines, ask(exe, lines), rows + rows):
+        assert tuple(int(t) for t in g.split()) == want, (label, l, g, want)
+        seen.add(want)
+    assert {(1, 0), (0, 0), (0, 1), (0, 2), (0, 3), (0, 4), (0, 5)} <= seen

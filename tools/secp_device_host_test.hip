@@ -4,6 +4,7 @@
 //   <c> dbl X Y Z | addaff X Y Z x y                                                  -> X Y Z (Jacobian, hex)
 //   0 split k                                                                         -> |k1| neg1 |k2| neg2 (secp256k1's endomorphism split)
 //   <c> gtab j d                                                                      -> x y
+//   <c> mul2 u1 qx qy u2                                                              -> X Y Z of u1 G + u2 (qx, qy), Z = 0 for the identity (secp_mul2 as secp_verify calls it)
 //   <c> verify r s x y_odd n_msg z                                                    -> result panic      (table of the generator built on first use;
 //                                                                                        build with -DSECP_GWIN_BITS=8: the device's 16-bit table takes minutes on the host)
 #include "../acvm_amd/csrc/secp_device.hpp"
@@ -59,6 +60,10 @@ static void serve(const std::vector<std::string> &w) {
         put(sp_leave<C>(r.X)); printf(" "); put(sp_leave<C>(r.Y)); printf(" "); put(sp_leave<C>(r.Z));
     }
     else if (op == "gtab") { const SAff e = secp_gtable_entry<C>((uint32_t)atoi(w[2].c_str()), (uint32_t)atoi(w[3].c_str())); put(sp_leave<C>(sp_load(e.x))); printf(" "); put(sp_leave<C>(sp_load(e.y))); }
+    else if (op == "mul2") {
+        const SJac r = secp_mul2<C>(A(2), sp_load(sp_store<C>(sp_enter<C>(A(3)))), sp_load(sp_store<C>(sp_enter<C>(A(4)))), A(5), gtable<C>());
+        put(sp_leave<C>(r.X)); printf(" "); put(sp_leave<C>(r.Y)); printf(" "); put(sp_leave<C>(r.Z));
+    }
     else if (op == "verify") {
         uint32_t panic = 0;
         const uint32_t ok = secp_verify<C>(A(2), A(3), A(4), (uint32_t)atoi(w[5].c_str()), (uint32_t)atoi(w[6].c_str()), A(7), gtable<C>(), &panic);
