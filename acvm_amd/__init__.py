@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
     "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
     "acvm_batch_export_device_records", "acvm_batch_witness_records",
+    "acvm_debug_lin_add", "acvm_debug_lin_plan",
 ]
 
 
@@ -466,6 +467,9 @@ def lib():
     L.acvm_circuit_plans_built.restype = C.c_uint64
     L.acvm_circuit_plans_built.argtypes = [C.c_void_p]
     L.acvm_circuit_check_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    if hasattr(L, "acvm_debug_lin_plan"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has neither)
+        L.acvm_debug_lin_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+        L.acvm_debug_lin_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.acvm_batch_new.restype = C.c_void_p
     L.acvm_batch_new.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.acvm_batch_new_ex.restype = C.c_void_p
@@ -803,6 +807,22 @@ def debug_fr(what, items, uniform=None):
     return out
 
 
+def debug_lin_add(n_terms, coef, rows, h):
+    """fr29_lin_add<1 / 2> on the device (acvm_debug_lin_add): n_terms = uint32 [n_groups], coef = uint32 [n_groups][2][8] canonical little-endian words,
+    rows = uint32 [n][2][8], h = uint32 [n][9]; the 64 items of a group share their coefficients. Returns (tables [n_groups][2][81], result limbs [n][9])."""
+    import numpy as np
+    nt = np.ascontiguousarray(n_terms, dtype=np.uint32).reshape(-1)
+    r = np.ascontiguousarray(rows, dtype=np.uint32)
+    n = r.shape[0]
+    n_groups = (n + 63) // 64
+    cf = np.ascontiguousarray(coef, dtype=np.uint32)
+    hh = np.ascontiguousarray(h, dtype=np.uint32)
+    assert nt.shape == (n_groups,) and cf.shape == (n_groups, 2, 8) and r.shape == (n, 2, 8) and hh.shape == (n, 9)
+    tables, out = np.zeros((n_groups, 2, 81), dtype=np.uint32), np.zeros((n, 9), dtype=np.uint32)
+    _check(lib().acvm_debug_lin_add(nt.ctypes.data, cf.ctypes.data, r.ctypes.data, hh.ctypes.data, n, tables.ctypes.data, out.ctypes.data))
+    return tables, out
+
+
 def debug_inverse_batch(den, inv_chunk, slot_of=None, inv_share=None):
     """The shipped inversion batch on denominators of the caller's (see include/acvm_amd.h): den = uint32 [n_jobs][B][8], canonical storage form.
     inv_share: the waves that share one field inversion (None: the process-wide tuning's).
@@ -925,6 +945,22 @@ class Circuit:
         _check(rc)
         return {"ok": rc == 0, "n_launches": counts[0], "n_waits": counts[1], "n_accesses": counts[2], "n_records": counts[3], "n_findings": counts[4],
                 "report": text.value.decode()}
+
+    def lin_plan(self, initial_ids, n_instances=4096, fold_digest=False, reuse_slots=False, keep=(), mutation=0) -> dict:
+        """Host-only: the plan's linear tables under the hazard checker, after mutation 1 (two tables change places) or 2 (a wave program's offset
+        moves by one) of a copy of the plan if asked (acvm_debug_lin_plan). Returns {ok, n_wave_programs, n_programs_with_tables, n_gate_records,
+        n_lin_records, n_lin_terms, n_findings, report}."""
+        ids = list(initial_ids)
+        arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+        keep = list(keep)
+        karr = (C.c_uint32 * max(len(keep), 1))(*keep)
+        counts = (C.c_uint64 * 8)()
+        text = C.create_string_buffer(1 << 14)
+        rc = lib().acvm_debug_lin_plan(self._h, arr, len(ids), (1 if fold_digest else 0) | (2 if reuse_slots else 0), karr, len(keep), n_instances, mutation,
+                                       counts, text, len(text))
+        _check(rc)
+        return {"ok": rc == 0, "n_wave_programs": counts[0], "n_programs_with_tables": counts[1], "n_gate_records": counts[2], "n_lin_records": counts[3],
+                "n_lin_terms": counts[4], "n_findings": counts[5], "report": text.value.decode()}
 
     def plan_fingerprint(self, initial_ids, fold_digest=False, reuse_slots=False, keep=(), host_solver=False) -> list:
         """Host-only: 64-bit fingerprints of the static plan, one per component (acvm_debug_plan_fingerprint)."""

@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 #include "batch_internal.hpp"
+#include "gate_record.hpp"
 
 static thread_local std::string g_last_error;
 int set_err(int code, const std::string &msg) {
@@ -230,7 +231,7 @@ int acvm_circuit_plan_stats_ex(const acvm_circuit_t *c, const uint32_t *initial_
 // same plan meanwhile plans too -- the node driver asks once, before its lanes start).
 static size_t plan_bytes(const Plan &p) {
     size_t words = p.gate_stream.size() + p.gate_offset.size() + p.prog.size() + p.prog_offset.size() + p.prog_scratch.size() + p.bytecode.size() + p.slot_of.size() + p.kbound.size() +
-                   p.unscale_index.size() + p.scaled_ids.size() + p.producer.size() + p.byte_plane_of.size() + p.dyn_offset.size();
+                   p.unscale_index.size() + p.scaled_ids.size() + p.producer.size() + p.byte_plane_of.size() + p.dyn_offset.size() + p.lin_tables.size() + p.lin_offset.size();
     for (int k = 0; k < (int)N_CLS; k++) words += 2 * p.cls_offset[k].size();
     return words * 4 + (p.constants.size() + p.unscale.size()) * sizeof(FrH);
 }
@@ -294,6 +295,52 @@ int acvm_circuit_check_schedule(const acvm_circuit_t *c, const uint32_t *initial
     const LevelSchedule sched = level_schedule(*sp, lay);
     const ScheduleReport rep = check_level_schedule(*sp, lay, sched, drop_wait);
     if (counts) { counts[0] = rep.n_launches; counts[1] = rep.n_waits; counts[2] = rep.n_accesses; counts[3] = rep.n_records; counts[4] = rep.n_findings; }
+    if (report && report_len) snprintf(report, report_len, "%s", rep.text.c_str());
+    return rep.ok ? 0 : 1;
+} ABI_CATCH
+
+// Host-only: the linear tables of a plan (gate_record.hpp) under the hazard checker, optionally after a mutation of a COPY of the plan: 1 = the first
+// two tables that differ change places, 2 = the first wave program that has tables starts one table later. counts: wave programs, wave programs
+// with tables, gate records, records that take the table form, tables, findings. Returns like acvm_circuit_check_schedule; ACVM_E_INVALID when the
+// plan offers nothing to mutate.
+int acvm_debug_lin_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                        uint32_t n_instances, uint32_t mutation, uint64_t *counts, char *report, size_t report_len) try {
+    if (!c || (n_initial && !initial_ids) || (n_keep && !keep_ids)) return set_err(ACVM_E_INVALID, "null argument");
+    PlanOpts opts;
+    opts.fold_digest = (flags & (ACVM_BATCH_FOLD_DIGEST | ACVM_BATCH_REUSE_SLOTS)) != 0;
+    opts.reuse_slots = (flags & ACVM_BATCH_REUSE_SLOTS) != 0;
+    opts.host_blackbox = (flags & 0x100u) != 0;
+    opts.keep.assign(keep_ids, keep_ids + n_keep);
+    const std::shared_ptr<const Plan> sp = plan_for(c, initial_ids, n_initial, opts);
+    if (!sp->unsupported.empty()) return set_err(ACVM_E_UNSUPPORTED, sp->unsupported);
+    Plan p = *sp;
+    const size_t n_tables = p.lin_tables.size() / GATE_LIN_TABLE_WORDS;
+    if (mutation == 1) {
+        size_t other = 0;
+        for (size_t t = 1; t < n_tables && !other; t++)
+            if (memcmp(&p.lin_tables[0], &p.lin_tables[t * GATE_LIN_TABLE_WORDS], GATE_LIN_TABLE_WORDS * 4) != 0) other = t;
+        if (!other) return set_err(ACVM_E_INVALID, "the plan has no two tables that differ");
+        std::swap_ranges(p.lin_tables.begin(), p.lin_tables.begin() + GATE_LIN_TABLE_WORDS, p.lin_tables.begin() + other * GATE_LIN_TABLE_WORDS);
+    } else if (mutation == 2) {
+        size_t q = 0;
+        while (q < p.lin_offset.size() && p.lin_offset[q] == GATE_LIN_NONE) q++;
+        if (q == p.lin_offset.size()) return set_err(ACVM_E_INVALID, "the plan has no table");
+        p.lin_offset[q]++;
+    } else if (mutation) return set_err(ACVM_E_INVALID, "no such mutation");
+    const LaunchLayout lay = layout_launches(p, ((uint64_t)n_instances + 63) / 64 * 64);
+    const LevelSchedule sched = level_schedule(p, lay);
+    const ScheduleReport rep = check_level_schedule(p, lay, sched, 0xFFFFFFFFu);
+    if (counts) {
+        uint64_t with = 0, records = 0;
+        for (size_t q = 0; q < p.gate_offset.size(); q++) {
+            with += q < p.lin_offset.size() && p.lin_offset[q] != GATE_LIN_NONE;
+            for (size_t pos = p.gate_offset[q];; pos += gate_record_words(GATE_WORDS(&p.gate_stream[pos]))) {
+                records++;
+                if (!(p.gate_stream[pos] & GATE_TAIL_FLAG)) break;
+            }
+        }
+        counts[0] = p.gate_offset.size(); counts[1] = with; counts[2] = records; counts[3] = p.n_lin_records; counts[4] = p.n_lin_terms; counts[5] = rep.n_findings;
+    }
     if (report && report_len) snprintf(report, report_len, "%s", rep.text.c_str());
     return rep.ok ? 0 : 1;
 } ABI_CATCH
@@ -363,6 +410,8 @@ static int batch_init(acvm_batch *b) {
     HIPCHK(hipMalloc((void **)&b->d_W, w_bytes ? w_bytes : 16));
     if (int rc = upload(&b->d_gate_stream, p.gate_stream)) return rc;
     if (int rc = upload(&b->d_gate_offset, p.gate_offset)) return rc;
+    if (int rc = upload(&b->d_lin_tables, p.lin_tables)) return rc;
+    if (int rc = upload(&b->d_lin_offset, p.lin_offset)) return rc;
     std::vector<uint32_t> consts(p.constants.size() * 8);
     for (size_t i = 0; i < p.constants.size(); i++) {
         const FrH d = frh::to_device_form(p.constants[i]);

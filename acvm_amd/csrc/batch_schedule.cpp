@@ -51,11 +51,12 @@ static int enqueue_level_schedule(acvm_batch *b, LaunchTimers *tm) {
             b->events_fresh = false;
             break;
         case SO_GATES:
-            launch_arith_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_gate_offset + st.first, st.count, b->d_consts, b->d_event, b->d_inv);
+            launch_arith_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_gate_offset + st.first, st.count, b->d_consts, b->d_event, b->d_inv, b->d_lin_tables,
+                               b->d_lin_offset + st.first);
             break;
         case SO_GATES_LIGHT:
             launch_arith_light_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_gate_offset + st.first, st.count, b->d_inv, b->dp,
-                                     b->d_cls_offset[CLS_LIGHT] + st.first2, st.count2, b->d_event);
+                                     b->d_cls_offset[CLS_LIGHT] + st.first2, st.count2, b->d_event, b->d_lin_tables, b->d_lin_offset + st.first);
             break;
         case SO_LIGHT: launch_light_level(s, b->d_W, b->Bp, b->B, b->dp, off, st.count, b->d_event); break;
         case SO_LIGHT_SL: launch_light_sl_level(s, b->d_W, b->Bp, b->B, b->dp, off, st.count, b->d_event); break;

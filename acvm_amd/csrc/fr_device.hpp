@@ -400,6 +400,72 @@ FR_HD __forceinline__ Fr29 fr29_dot(const Fr29 (&a)[N], const Fr29 (&b)[N]) { re
 template <int N>
 FR_HD __forceinline__ Fr29 fr29_dot_add(const Fr29 (&a)[N], const Fr29 (&b)[N], const Fr29 &h) { return fr29_dot_impl<N, true>(a, b, &h); }
 
+// ---- coefficient x row with the reduction precomputed: h + sum_t c_t x_t for N rows x_t (Montgomery representatives, like every row)
+// and N coefficients c_t known on the host (plain field elements: c (x R) = (c x) R, no Montgomery factor on the coefficient's side).
+// tab: N tables of 81 words one behind the other (lin_table.hpp): word [9 k + i] = limb k of C_i = c 2^(29 i + 58) mod p, canonical.
+// S = sum_t sum_i x_t[i] C_t,i is congruent to 2^58 sum_t c_t x_t and has nine columns of 9 N products; two Montgomery columns (m_0,
+// m_1: the shift trick of fr29_mul, 16 multiply-adds with p) divide by 2^58 and leave T = (S + m p) / 2^58 in columns 2..10, which the
+// scan hands out normalised: 81 N + 16 multiply-adds where fr29_dot_add spends 81 N + 72 (and its nine m_k).
+// Contract: rows normalised, below 2^256 (limbs below 2^29, the top one below 2^24); table limbs below 2^29, C_i < p; h limbs below
+// 2^32, riding in the upper columns exactly as in fr29_dot_impl. Then S < N (2^32 + 2^24) p and m < 2^58, so
+//     result < p (1 + N (2^-26 + 2^-34)) + h      (N = 2: p (1 + 2^-25 + 2^-33); one unit of the planner's p / 256 covers it many times),
+// and a column's accumulator stays below (9 N + 2) 2^58 + the carry of the column before (< 2^35 + 2^32): 20 * 2^58 < 2^63 for N = 2.
+template <int N, class T>
+FR_HD __forceinline__ Fr29 fr29_lin_add(T tab, const Fr29 (&x)[N], const Fr29 &h) {
+    static_assert(N == 1 || N == 2, "column accumulator budget");
+    constexpr uint32_t M = 0x1fffffffu;
+    uint64_t acc = 0;
+    uint32_t m[2];
+    Fr29 r;
+    // The table words are wave-uniform (scalar registers on the device) and a column needs only its own 9 N of them. Left alone, hipcc
+    // issues all 81 N loads ahead of the scan: 46 scalar registers spilled and a wave of occupancy lost in the gate kernel (N = 2). So
+    // the words stay close to the sums that use them: before column k the pointer is made opaque together with the accumulator as it
+    // stands (an empty asm: no instruction), and the loads that go through it -- column k + 1 of the first table, column k of the
+    // second: 27 words live at most -- can then not be issued ahead of column k - 1. (Both tables one column ahead, 36 words: 14 scalar
+    // registers spilled in arith_light_level_kernel; a second fence between the tables, 18 words: 6 there, and more scratch. This
+    // form: none in arith_level_kernel, the saved exec mask of the bounds check in arith_light_level_kernel.)
+    uint32_t c[9 * N], nx[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) c[i] = tab[i];
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        T next = tab;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(next), "+v"(acc));
+#endif
+        if (k < 8) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) nx[i] = next[9 * (k + 1) + i];
+        }
+        if (N == 2) {
+#pragma unroll
+            for (int i = 0; i < 9; i++) c[9 + i] = next[81 + 9 * k + i];
+        }
+#pragma unroll
+        for (int t = 0; t < N; t++)
+#pragma unroll
+            for (int i = 0; i < 9; i++) acc += (uint64_t)x[t].v[i] * c[9 * t + i];
+#pragma unroll
+        for (int i = 0; i < 9; i++) c[i] = nx[i];
+        if (k >= 1) acc += (uint64_t)m[0] * fr_p29(k);
+        if (k >= 2) acc += (uint64_t)m[1] * fr_p29(k - 1);
+        if (k < 2) {
+            const uint32_t lo = (uint32_t)acc;
+            m[k] = (((lo & 1u) << 28) - lo) & M;
+            acc += ((uint64_t)m[k] << 28) + m[k];
+        } else {
+            acc += h.v[k - 2];
+            r.v[k - 2] = (uint32_t)acc & M;
+        }
+        acc >>= 29;
+    }
+    acc += (uint64_t)m[1] * fr_p29(8) + h.v[7];
+    r.v[7] = (uint32_t)acc & M;
+    acc >>= 29;
+    r.v[8] = (uint32_t)acc + h.v[8];
+    return r;
+}
+
 // ---- the same scans as asm blocks (device pass; generated: tools/gen_mul_blocks.py > fr_blocks.inc, which says why). hipcc's form of the scan above
 // joins every column with the carry of the one before by a 64-bit add -- 17 of a product's 221 VALU instructions; a column whose first multiply-add
 // takes the carry needs none. For kernels that keep four or more waves per SIMD (the gate kernels, gate_eval.hpp): at two waves per SIMD the serial

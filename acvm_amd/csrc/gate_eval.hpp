@@ -76,12 +76,15 @@ FR_HD __forceinline__ Fr29 gate_mac_operand(const L &ld, GateWords c, bool produ
 
 // Value of a record: normalised limbs, below the planner's bound for the record (plan.cpp mirrors this walk term by term).
 //   L: loader with  Fr29 load(uint32_t slot) const  (GATE_LOCAL never reaches it),  Fr29 load_inverse(uint32_t slot) const,
-//      GateWords constant(uint32_t idx) const  (8 words of the constant pool),  bool any(bool) const  (wave-wide OR: the ballot)
+//      GateWords constant(uint32_t idx) const  (8 words of the constant pool),  bool any(bool) const  (wave-wide OR: the ballot),
+//      bool has_lin() const  and  GateWords lin: whether the wave program has linear tables (gate_record.hpp), and the cursor into them. The
+//      cursor is the one thing a record leaves behind for the next one of its wave program: a qualifying record moves it past its
+//      nl_mac tables, every other record leaves it alone (the tables of a wave program lie in record order, plan.cpp build_lin_tables).
 // Order: the terms that are only added or subtracted go into the lazy sum h first; then every Montgomery reduction of the record --
 // two multiplied terms apiece -- takes the running sum along in its upper columns (fr29_dot_add), so the sum comes out of the last one
 // with its carries propagated. An ASSERT record's value is canonical (zero test by the caller, arithmetic.rs:92-102).
 template <class L>
-FR_HD __forceinline__ Fr29 gate_eval(const L &ld, GateWords g, const Fr29 &local) {
+FR_HD __forceinline__ Fr29 gate_eval(L &ld, GateWords g, const Fr29 &local) {
     const uint32_t w0 = g[0], w5 = g[5], qc = g[3], kind = w0 & 0xff;
     const uint32_t np_mac = (w0 >> 8) & 0xff, nl_mac = (w0 >> 16) & 0xff, n_mac = np_mac + nl_mac;
     const uint32_t np_pos = w5 & 0xff, np_neg = (w5 >> 8) & 0xff, nl_pos = (w5 >> 16) & 0xff, nl_neg = w5 >> 24;
@@ -128,9 +131,23 @@ FR_HD __forceinline__ Fr29 gate_eval(const L &ld, GateWords g, const Fr29 &local
         h = fr29_dot_add_b<2, 2u>(l, m, h);  // (fr_device.hpp: the asm-block scan; bit t of the mask = m[t] is a coefficient, wave-uniform)
         GATE_AFTER_REDUCTION();
     }
+    // Coefficient terms that share their reductions with no witness product (gate_lin_terms: none of the loop above, none of the one below) take the
+    // precomputed form where the wave program has tables: 81 multiply-adds per term and 16 per reduction instead of 72 (fr29_lin_add). Same residue, and
+    // a result below p + 1 / 256 p + h where the planner counted p + at least 1 / 256 p + h: every bound of the record stands.
+    const bool lin = ld.has_lin() && gate_lin_terms(w0, w5) != 0;
     for (; im < n_mac; im += 2) {
         GateWords c0 = gate_mac_entry(t0, np_mac, im);
-        if (n_mac - im == 1) {
+        if (lin) {
+            if (n_mac - im == 1) {
+                const Fr29 l[1] = {gate_operand(ld, c0[8], local)};
+                h = fr29_lin_add<1>(ld.lin, l, h);
+                ld.lin += GATE_LIN_TABLE_WORDS;
+            } else {
+                const Fr29 l[2] = {gate_operand(ld, c0[8], local), gate_operand(ld, gate_mac_entry(t0, np_mac, im + 1)[8], local)};
+                h = fr29_lin_add<2>(ld.lin, l, h);
+                ld.lin += 2 * GATE_LIN_TABLE_WORDS;
+            }
+        } else if (n_mac - im == 1) {
             const Fr29 l[1] = {gate_mac_operand(ld, c0, im < np_mac, local)}, m[1] = {gate_coef29(c0)};
             h = fr29_dot_add_b<1, 1u>(l, m, h);
         } else {

@@ -58,6 +58,18 @@ GATE_HD inline uint32_t gate_k_product(uint32_t ka, uint32_t kb) {
     return (uint32_t)(((uint64_t)ka * kb * 1549u + ((1ull << 26) - 1)) >> 26);
 }
 
+// LINEAR TABLES (plan.hpp Plan::lin_tables, fr_device.hpp fr29_lin_add). A record whose multiplied terms are all coefficient x witness and
+// that has no +1 product -- np_mac == 0 && np_pos == 0 && nl_mac >= 1 -- shares no reduction with a witness product, so its reductions
+// can be precomputed but for two columns: each of its nl_mac terms has a table of GATE_LIN_TABLE_WORDS words beside the stream. The
+// record itself says nothing about it (no word, no flag moves): the shape decides, and the wave program's entry in Plan::lin_offset
+// says whether tables exist at all (GATE_LIN_NONE: none -- tuning lin_table = 0, or no qualifying record in the program).
+static constexpr uint32_t GATE_LIN_TABLE_WORDS = 81;
+static constexpr uint32_t GATE_LIN_NONE = 0xFFFFFFFFu;
+// terms of a record that have a table (0: the record does not qualify)
+GATE_HD inline uint32_t gate_lin_terms(uint32_t w0, uint32_t w5) {
+    return ((w0 >> 8) & 0xff) == 0 && (w5 & 0xff) == 0 ? (w0 >> 16) & 0xff : 0u;
+}
+
 // words of a gate record
 GATE_HD inline uint32_t gate_record_words(GateWords g) {
     const uint32_t w0 = g[0], w5 = g[5];

@@ -346,8 +346,9 @@ __global__ void __launch_bounds__(256) unscale_slow_kernel(uint4 *__restrict__ W
 #endif
 __global__ void __launch_bounds__(ARITH_BLOCK) __attribute__((amdgpu_waves_per_eu(ARITH_WAVES_MIN, 8)))
 arith_level_kernel(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_t *__restrict__ gate_stream, const uint32_t *__restrict__ gate_offset,
-                   const uint32_t *__restrict__ consts, uint32_t *__restrict__ event, const uint4 *__restrict__ Inv) {
-    arith_level_body(W, Bp, B, gate_stream, gate_offset, consts, event, Inv, blockIdx.y);
+                   const uint32_t *__restrict__ consts, uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, const uint32_t *__restrict__ lin_tables,
+                   const uint32_t *__restrict__ lin_offset) {
+    arith_level_body(W, Bp, B, gate_stream, gate_offset, consts, event, Inv, lin_tables, lin_offset, blockIdx.y);
 }
 
 // Denominators of the gates whose unknown is multiplied by a known witness (arithmetic.rs:68-91): 1 / partner for a batch of
@@ -514,6 +515,35 @@ void launch_fr_probe(hipStream_t s, uint32_t what, const uint32_t *in, uint32_t 
     FrProbeUniform un;
     for (int k = 0; k < 18; k++) un.u[k / 9].v[k % 9] = uniform18 ? uniform18[k] : 0u;
     hipLaunchKernelGGL(fr_probe_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, what, in, n_items, fr_probe_words_in(what), fr_probe_words_out(what), un, out);
+}
+
+// ---- the same for fr29_lin_add (acvm_debug_lin_add): one lane per item; the 64 items of a wave share their tables, which are read through the
+// constant address space with a wave-uniform address as the gate kernel reads them (scalar loads). tables: per wave 2 x 81 words; rows: per item
+// 2 x 8 words of the storage form; h: per item 9 limbs; out: per item 9 limbs.
+__global__ void __launch_bounds__(64) lin_add_probe_kernel(const uint32_t *__restrict__ n_terms, const uint32_t *__restrict__ tables, const uint32_t *__restrict__ rows,
+                                                           const uint32_t *__restrict__ hs, uint32_t n_items, uint32_t *__restrict__ out) {
+    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
+    if (t >= n_items) return;
+    GateWords tab = GATE_WORDS(tables) + (uint64_t)blockIdx.x * 2 * GATE_LIN_TABLE_WORDS;
+    Fr a, b;
+    Fr29 h, r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { a.v[i] = rows[(size_t)t * 16 + i]; b.v[i] = rows[(size_t)t * 16 + 8 + i]; }
+#pragma unroll
+    for (int i = 0; i < 9; i++) h.v[i] = hs[(size_t)t * 9 + i];
+    if (n_terms[blockIdx.x] == 1) {
+        const Fr29 x[1] = {fr29_from(a)};
+        r = fr29_lin_add<1>(tab, x, h);
+    } else {
+        const Fr29 x[2] = {fr29_from(a), fr29_from(b)};
+        r = fr29_lin_add<2>(tab, x, h);
+    }
+#pragma unroll
+    for (int i = 0; i < 9; i++) out[(size_t)t * 9 + i] = r.v[i];
+}
+void launch_lin_add_probe(hipStream_t s, const uint32_t *n_terms, const uint32_t *tables, const uint32_t *rows, const uint32_t *hs, uint32_t n_items, uint32_t *out) {
+    if (!n_items) return;
+    hipLaunchKernelGGL(lin_add_probe_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, n_terms, tables, rows, hs, n_items, out);
 }
 
 // ------------------------------------------------------------------------------------------ modmul rate probe
@@ -696,11 +726,12 @@ void launch_unscale_slow(hipStream_t s, uint4 *W, uint64_t Bp, const uint32_t *s
                        u.consts, producer, start_opcode);
 }
 void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset,
-                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv) {
+                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv, const uint32_t *lin_tables, const uint32_t *lin_offset) {
     // gridDim.y is limited to 65535
     for (uint32_t done = 0; done < n_gates;) {
         uint32_t n = n_gates - done > 65535u ? 65535u : n_gates - done;
-        hipLaunchKernelGGL(arith_level_kernel, dim3((B + ARITH_BLOCK - 1) / ARITH_BLOCK, n), dim3(ARITH_BLOCK), 0, s, W, Bp, B, gate_stream, gate_offset + done, consts, event, inv);
+        hipLaunchKernelGGL(arith_level_kernel, dim3((B + ARITH_BLOCK - 1) / ARITH_BLOCK, n), dim3(ARITH_BLOCK), 0, s, W, Bp, B, gate_stream, gate_offset + done, consts, event, inv, lin_tables,
+                           lin_offset + done);
         done += n;
     }
 }

@@ -199,20 +199,23 @@ void launch_gather_columns(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *
 void launch_unscale_slow(hipStream_t s, uint4 *W, uint64_t Bp, const uint32_t *slow_ids, uint32_t n_slow, const Unscale &u, const uint32_t *producer,
                          const uint32_t *start_opcode);
 void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset,
-                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv);
+                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv, const uint32_t *lin_tables, const uint32_t *lin_offset);  // lin_offset: parallel to gate_offset
 void launch_inverse_batch(hipStream_t s, const uint4 *W, uint4 *inv, uint64_t Bp, uint32_t B, const uint32_t *gate_stream,
                           const uint32_t *job_offset, uint32_t n_jobs, uint32_t *event, uint32_t inv_chunk, uint32_t inv_share);
 // waves that share one field inversion (tuning.hpp inv_share): 1, 2, 4 or 8; anything else is the next lower of those
 inline uint32_t inverse_share_clamp(int64_t v) { return v >= 8 ? 8u : v >= 4 ? 4u : v >= 2 ? 2u : 1u; }
 // gates [0, n_gates) of a level and n_light light records of the same level in one launch (n_gates + n_light <= 65535)
 void launch_arith_light_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset, uint32_t n_gates,
-                              const uint4 *inv, const DeviceProgram &dp, const uint32_t *light_offsets, uint32_t n_light, uint32_t *event);
+                              const uint4 *inv, const DeviceProgram &dp, const uint32_t *light_offsets, uint32_t n_light, uint32_t *event, const uint32_t *lin_tables,
+                              const uint32_t *lin_offset);
 void launch_modmul_rate(hipStream_t s, uint32_t *out, uint32_t blocks, uint32_t iters);
 void launch_secp_rate(hipStream_t s, uint32_t curve, uint32_t *out, uint32_t blocks, uint32_t iters);  // kernels_ecdsa.hip
 void launch_stream_rate(hipStream_t s, const uint4 *a, const uint4 *b, uint4 *out, uint64_t n);  // n: multiple of 256
 void launch_fr_selftest(hipStream_t s, uint64_t seed, uint32_t n, uint32_t *mismatches);
 // acvm_debug_fr (fr_probe.hpp): words per item of `what` going in / coming out (0: no such routine); one lane per item, in / out on the device,
 // uniform18: host memory, the two wave-uniform working-form factors of the "U" forms (null: zeros)
+// acvm_debug_lin_add: fr29_lin_add<1 / 2> per lane; n_terms, tables (2 x 81 words) per wave of 64 items; rows 2 x 8, hs 9, out 9 words per item; all on the device
+void launch_lin_add_probe(hipStream_t s, const uint32_t *n_terms, const uint32_t *tables, const uint32_t *rows, const uint32_t *hs, uint32_t n_items, uint32_t *out);
 uint32_t fr_probe_words(uint32_t what, bool out);
 void launch_fr_probe(hipStream_t s, uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out);
 void launch_fill_u32(hipStream_t s, uint32_t *p, uint32_t v, uint64_t n);

@@ -90,6 +90,8 @@ struct GateDeviceLoader {
     const uint4 *__restrict__ Inv;
     const uint32_t *__restrict__ consts;
     uint64_t Bp, j;
+    GateWords lin;  // cursor into the wave program's linear tables (gate_eval.hpp), null = it has none: wave-uniform, read by scalar loads like the record
+    __device__ __forceinline__ bool has_lin() const { return lin != GATE_WORDS(nullptr); }
     __device__ __forceinline__ Fr29 load(uint32_t slot) const {
         // nontemporal (streaming) loads: an operand row is read by this launch and then not again for levels (5.53 -> 5.55 M witnesses/s)
 #ifdef GATE_EXP_NO_LOADS  // measurement only (tools/build_variant.sh): operands made up from the lane and the row, no memory access
@@ -108,11 +110,14 @@ struct GateDeviceLoader {
 };
 __device__ __forceinline__ void arith_level_body(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_t *__restrict__ gate_stream,
                                                  const uint32_t *__restrict__ gate_offset, const uint32_t *__restrict__ consts,
-                                                 uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, uint32_t gate_index) {
+                                                 uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, const uint32_t *__restrict__ lin_tables,
+                                                 const uint32_t *__restrict__ lin_offset, uint32_t gate_index) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= B) return;
     GateWords g = GATE_WORDS(gate_stream) + gate_offset[gate_index];
-    const GateDeviceLoader ld{W, Inv, consts, Bp, j};
+    // the wave program's first linear table (in tables; GATE_LIN_NONE: it has none): gate_eval moves the cursor from record to record
+    const uint32_t lin_at = lin_offset[gate_index];
+    GateDeviceLoader ld{W, Inv, consts, Bp, j, lin_at != GATE_LIN_NONE ? GATE_WORDS(lin_tables) + (uint64_t)lin_at * GATE_LIN_TABLE_WORDS : GATE_WORDS(nullptr)};
     Fr29 local = fr29_from(fr_zero());
     bool host = true;
     for (;;) {  // the record, then the records fused behind it (they read this one's output as GATE_LOCAL)

@@ -1,6 +1,7 @@
 // plan.cpp -- static replay of the reference's assigned-set bookkeeping + levelisation (see plan.hpp).
 #include "plan.hpp"
 #include "gate_record.hpp"
+#include "lin_table.hpp"
 #include "tuning.hpp"
 #include "scratch_layout.hpp"
 #include <algorithm>
@@ -339,6 +340,36 @@ void order_level_records(Plan &p) {
                 for (uint32_t r = lo; r < hi; r++)
                     if ((pg[p.cls_offset[k][r]] == PK_BRILLIG_SL) == (pass == 1)) recs.push_back({p.cls_offset[k][r], p.cls_scratch[k][r]});
             for (uint32_t r = lo; r < hi; r++) { p.cls_offset[k][r] = recs[r - lo].first; p.cls_scratch[k][r] = recs[r - lo].second; }
+        }
+    }
+}
+
+// =========================================================================== linear tables (gate_record.hpp; tuning lin_table)
+// The last pass: the record stream and the order of the wave programs are final (fuse_gate_pairs, assign_rows -- whose row remap touches
+// operand words only -- and lay_out have run), so the tables are emitted in exactly the order the gate kernel's cursor walks: per wave
+// program of gate_offset, its records from the host to the last fused tail, per qualifying record its nl_mac terms in the order of the
+// record's list. The coefficient is read back from the record's own inline words (what push_coef wrote): one source for the kernel's
+// old form, the table and the checker (schedule_check.cpp). Nothing the fingerprint hashes is touched.
+void build_lin_tables(Plan &p) {
+    p.lin_tables.clear();
+    p.lin_offset.assign(p.gate_offset.size(), GATE_LIN_NONE);
+    p.n_lin_records = p.n_lin_terms = 0;
+    if (!p.tune.lin_table) return;
+    const std::vector<uint32_t> &gs = p.gate_stream;
+    for (size_t q = 0; q < p.gate_offset.size(); q++) {
+        for (size_t pos = p.gate_offset[q];;) {
+            const uint32_t w0 = gs[pos], n_terms = gate_lin_terms(w0, gs[pos + 5]);
+            if (n_terms) {
+                if (p.lin_offset[q] == GATE_LIN_NONE) p.lin_offset[q] = p.n_lin_terms;
+                p.n_lin_records++;
+                for (uint32_t i = 0; i < n_terms; i++) {  // (np_mac == 0: the coefficient terms start the record's lists)
+                    p.lin_tables.resize(p.lin_tables.size() + GATE_LIN_TABLE_WORDS);
+                    lin_table_of(&gs[pos + 6 + 9 * (size_t)i], &p.lin_tables[(size_t)p.n_lin_terms * GATE_LIN_TABLE_WORDS]);
+                    p.n_lin_terms++;
+                }
+            }
+            if (!(w0 & GATE_TAIL_FLAG)) break;
+            pos += gate_record_words(GATE_WORDS(&gs[pos]));
         }
     }
 }
@@ -1974,6 +2005,7 @@ Plan build_plan(const Circuit &c, const uint32_t *initial_ids, uint32_t n_initia
     b.lay_out();                                        // the streams and the level-major lists
     if (v) b.check_layout();
     order_level_records(b.p);                           // placement inside a level
+    build_lin_tables(b.p);                              // precomputed reductions of the coefficient terms, beside the stream
     return b.finish();
 }
 

@@ -70,6 +70,12 @@ struct Plan {
     // ---- arithmetic level program
     std::vector<uint32_t> gate_stream;          // all gate records
     std::vector<uint32_t> gate_offset;          // per scheduled ASSERT/SOLVE gate: offset into gate_stream (level-major)
+    // Linear tables (gate_record.hpp, lin_table.hpp; tuning lin_table): 81 words per coefficient term of every qualifying record, in the order the
+    // gate kernel's cursor meets them -- wave programs in gate_offset order, inside one the host's terms, then each fused tail's. Outside
+    // the record stream (no record word knows of them) and outside acvm_debug_plan_fingerprint.
+    std::vector<uint32_t> lin_tables;
+    std::vector<uint32_t> lin_offset;           // per wave program, parallel to gate_offset: its first table (index in tables), GATE_LIN_NONE = it has none
+    uint32_t n_lin_records = 0, n_lin_terms = 0; // statistics: records that take the table form, their terms (= tables)
     std::vector<uint32_t> level_start;          // size n_levels + 1, indexes gate_offset
     std::vector<uint32_t> dyn_offset;           // per inversion job (denominator of a SOLVE_DYN gate), level-major
     std::vector<uint32_t> dyn_level_start;      // size n_levels + 1, indexes dyn_offset

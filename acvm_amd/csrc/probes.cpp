@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 #include "batch_internal.hpp"
+#include "lin_table.hpp"
 
 int acvm_selftest(uint32_t n, uint64_t seed) {
     uint32_t *d = nullptr, h = 0;
@@ -277,6 +278,43 @@ int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uin
     step(hipMemcpy(out, d_out, (size_t)n_items * wo * 4, hipMemcpyDeviceToHost), "hipMemcpy");
     hipFree(d_in);
     hipFree(d_out);
+    return rc;
+} ABI_CATCH
+
+// fr29_lin_add<1 / 2> on the device over tables the planner's builder makes for the call (include/acvm_amd.h). The coefficient takes the planner's
+// road: field element -> the record's inline words (plan.cpp push_coef) -> lin_table_of.
+int acvm_debug_lin_add(const uint32_t *n_terms, const uint32_t *coef, const uint32_t *rows, const uint32_t *h, uint32_t n_items, uint32_t *tables_out, uint32_t *out) try {
+    if (!n_items) return 0;
+    if (!n_terms || !coef || !rows || !h || !out) return set_err(ACVM_E_INVALID, "null argument");
+    const size_t n_groups = ((size_t)n_items + 63) / 64;
+    std::vector<uint32_t> tables(n_groups * 2 * GATE_LIN_TABLE_WORDS, 0);
+    for (size_t g = 0; g < n_groups; g++) {
+        if (n_terms[g] != 1 && n_terms[g] != 2) return set_err(ACVM_E_INVALID, "a group has one or two terms");
+        for (uint32_t t = 0; t < n_terms[g]; t++) {
+            uint64_t c[4];
+            for (int i = 0; i < 4; i++) c[i] = coef[g * 16 + t * 8 + 2 * i] | (uint64_t)coef[g * 16 + t * 8 + 2 * i + 1] << 32;
+            if (frh::geq_p(c)) return set_err(ACVM_E_INVALID, "a coefficient is not canonical");
+            const FrH d = frh::to_device_form(frh::from_canonical(c));
+            uint32_t inline_words[8];
+            for (int i = 0; i < 4; i++) { inline_words[2 * i] = (uint32_t)d.l[i]; inline_words[2 * i + 1] = (uint32_t)(d.l[i] >> 32); }
+            lin_table_of(inline_words, &tables[(g * 2 + t) * GATE_LIN_TABLE_WORDS]);
+        }
+    }
+    if (tables_out) memcpy(tables_out, tables.data(), tables.size() * 4);
+    const size_t bytes[5] = {n_groups * 4, tables.size() * 4, (size_t)n_items * 16 * 4, (size_t)n_items * 9 * 4, (size_t)n_items * 9 * 4};
+    const void *src[4] = {n_terms, tables.data(), rows, h};
+    uint32_t *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    auto step = [&](hipError_t e, const char *what_) { if (!rc && e != hipSuccess) rc = set_err(ACVM_E_DEVICE, std::string(what_) + ": " + hipGetErrorString(e)); };
+    for (int k = 0; k < 5; k++) step(hipMalloc((void **)&d[k], bytes[k]), "hipMalloc");
+    for (int k = 0; k < 4 && !rc; k++) step(hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice), "hipMemcpy");
+    if (!rc) step(hipMemset(d[4], 0, bytes[4]), "hipMemset");
+    if (!rc) launch_lin_add_probe(nullptr, d[0], d[1], d[2], d[3], n_items, d[4]);
+    step(hipGetLastError(), "lin_add_probe_kernel");
+    step(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (!rc) step(hipMemcpy(out, d[4], bytes[4], hipMemcpyDeviceToHost), "hipMemcpy");
+    for (int k = 0; k < 5; k++)
+        if (d[k]) hipFree(d[k]);
     return rc;
 } ABI_CATCH
 

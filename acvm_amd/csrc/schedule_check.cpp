@@ -19,6 +19,7 @@
 // in-order replay of the assigned set -- not from the planner's dependency tables (level_needs_*, lane_needs_*, slot liveness), which
 // are exactly what is being checked.
 #include "gate_record.hpp"
+#include "lin_table.hpp"
 #include "schedule.hpp"
 #include <array>
 #include <cstdio>
@@ -402,9 +403,27 @@ struct Checker {
         size_t pos = p.gate_offset[gate_index];
         uint32_t local_kb = GATE_K_CANON, local_witness = NONE;
         bool host = true;
+        // the kernel's cursor into the linear tables (ops_common.hpp arith_level_body, gate_eval.hpp): where the wave program's entry puts it, then
+        // past the tables of every qualifying record
+        uint64_t lin_at = gate_index < p.lin_offset.size() ? p.lin_offset[gate_index] : GATE_LIN_NONE;
+        const bool has_lin = lin_at != GATE_LIN_NONE;
         for (;;) {
             if (pos + 6 > gs.size()) { finding("gate record runs past the stream"); return; }
             const uint32_t w0 = gs[pos], kind = w0 & 0xff, opcode = gs[pos + 1], w5 = gs[pos + 5];
+            if (const uint32_t n_terms = gate_lin_terms(w0, w5)) {
+                // LINEAR TABLES: what the kernel would read for this record is the table of the record's own inline coefficient, term by term
+                if (pos + 6 + 9 * (size_t)n_terms > gs.size()) { finding("gate record runs past the stream"); return; }
+                if (!has_lin) {
+                    if (p.tune.lin_table) finding("LINEAR TABLES: gate of opcode " + std::to_string(opcode) + " qualifies for the table form but its wave program (" + std::to_string(gate_index) + ") lists no table");
+                } else {
+                    for (uint32_t i = 0; i < n_terms; i++, lin_at++) {
+                        if ((lin_at + 1) * GATE_LIN_TABLE_WORDS > p.lin_tables.size()) { finding("LINEAR TABLES: gate of opcode " + std::to_string(opcode) + ", term " + std::to_string(i) + ": the cursor (table " + std::to_string(lin_at) + ") runs past the tables"); break; }
+                        uint32_t want[GATE_LIN_TABLE_WORDS];
+                        lin_table_of(&gs[pos + 6 + 9 * (size_t)i], want);
+                        if (memcmp(want, &p.lin_tables[lin_at * GATE_LIN_TABLE_WORDS], sizeof want) != 0) finding("LINEAR TABLES: gate of opcode " + std::to_string(opcode) + ", term " + std::to_string(i) + ": table " + std::to_string(lin_at) + " at the kernel's cursor is not the table of the record's coefficient (wave program " + std::to_string(gate_index) + ")");
+                    }
+                }
+            }
             const uint32_t np_mac = (w0 >> 8) & 0xff, nl_mac = (w0 >> 16) & 0xff, n_mac = np_mac + nl_mac;
             const uint32_t np_pos = w5 & 0xff, np_neg = (w5 >> 8) & 0xff, nl_pos = (w5 >> 16) & 0xff, nl_neg = w5 >> 24;
             const uint32_t sub_k = (w0 >> GATE_SUBK_SHIFT) & 3u;
@@ -598,6 +617,7 @@ struct Checker {
             write(RK_W, row, w, "import");
             if (!p.byte_plane_of.empty() && p.byte_plane_of[w] != NONE) write(RK_BYTE_PLANE, p.byte_plane_of[w], w, "import");
         }
+        if (p.lin_offset.size() != p.gate_offset.size()) finding("LINEAR TABLES: " + std::to_string(p.lin_offset.size()) + " table offsets for " + std::to_string(p.gate_offset.size()) + " wave programs (the gate kernel reads one per program)");
         int reset_launch = -1;
         uint32_t wait_index = 0;
         for (size_t si = 0; si < sch.steps.size(); si++) {

@@ -20,7 +20,10 @@ struct Tuning {
     int64_t inv_chunk = 128;       // denominators per wave of an inversion batch at most (they share ONE field inversion; 64 -> 128: +0.9 % on the headline, NOTEBOOK.md section 9)
     int64_t inv_share = 4;         // waves of an inversion batch that share ONE field inversion through LDS (inverse_batch_kernel_shared): 1 (the one-wave kernel), 2, 4 or 8; anything else: the next lower of those.
                                    // The rows are the same bit for bit. Headline, one box, three rounds in turn: parent 6.110-6.124 M witnesses/s, 1: 6.102-6.114, 2: 6.162-6.176, 4: 6.207-6.226 (+1.6 %), 8: 6.167-6.186 (NOTEBOOK.md, "Inversion batches: one field inversion for G waves")
-    int64_t inv_latency = 1;      // levels of slack between an inversion batch and the first gate that reads it
+    int64_t lin_table = 1;         // coefficient x witness terms that share a reduction with no witness product carry a precomputed table (gate_record.hpp "linear tables"): 81 + 16 multiply-adds
+                                   // instead of 81 + 72. 0: no tables, the gate kernel evaluates every record as before. The rows' residues are the same either way.
+                                   // Headline, one box, three rounds in turn: parent 6.044-6.056 M witnesses/s, 1: 6.156-6.171 (+1.7 %), 0: 6.007-6.034 (NOTEBOOK.md, "Linear tables")
+    int64_t inv_latency = 1;     // levels of slack between an inversion batch and the first gate that reads it
     int64_t heavy_epoch = 1;       // heavy records launched every K-th level only
     int64_t heavy_latency = 0;     // levels the main stream waits before it reads a heavy output
     // Pedersen records are launched every 8th level only and the main stream reads their outputs 4 levels behind the launch at the earliest: a

@@ -252,6 +252,17 @@ int acvm_debug_secp(uint32_t curve, uint32_t what, const uint8_t *in_be32, uint3
  * uniform18: the wave-uniform factors u0, u1 of 35..37 (2 x W; null: zeros) -- ONE value per call, handed to the kernel as an argument, because those forms
  * read them from scalar registers. in: n_items x words-in u32, out: n_items x words-out u32, host memory. */
 int acvm_debug_fr(uint32_t what, const uint32_t *in, uint32_t n_items, const uint32_t *uniform18, uint32_t *out);
+/* The precomputed coefficient x row reduction of the gate kernel (fr_device.hpp fr29_lin_add<1 / 2>, lin_table.hpp) ON THE DEVICE against integers: one lane
+ * per item, and the 64 items of a wave share their coefficients, as in the gate kernel (the tables are read by scalar loads). With n_groups =
+ * ceil(n_items / 64): n_terms [n_groups] = 1 | 2; coef [n_groups][2][8] = the coefficients as canonical integers, little-endian words (the second unused for
+ * one term); rows [n_items][2][8] = any 256-bit patterns (the storage form); h [n_items][9] = any limbs. tables_out (may be NULL) [n_groups][2][81]: the
+ * tables the planner's builder made -- word [9 k + i] = limb k of c 2^(29 i + 58) mod p; out [n_items][9]: the routine's raw limbs. Host memory. */
+int acvm_debug_lin_add(const uint32_t *n_terms, const uint32_t *coef, const uint32_t *rows, const uint32_t *h, uint32_t n_items, uint32_t *tables_out, uint32_t *out);
+/* Host-only: the linear tables of the plan a handle of these options would get, under the hazard checker (acvm_circuit_check_schedule: same arguments, same
+ * return), optionally after a mutation of a copy of the plan: 0 none, 1 the first two tables that differ change places, 2 the first wave program with
+ * tables starts one table later. counts[6]: wave programs, wave programs with tables, gate records, records that take the table form, tables, findings. */
+int acvm_debug_lin_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                        uint32_t n_instances, uint32_t mutation, uint64_t *counts, char *report, size_t report_len);
 /* The inversion batch of the level schedule (inverse_batch_kernel through its launcher, exactly as a solve starts it) on a table made for the call.
  * den: [n_jobs][B] canonical denominators in the storage form (8 x u32; zero = the instance leaves the generic path at that job). Job k reads row k,
  * carries opcode index k and owns row slot_of[k] of the inverse table (null: row k; otherwise a permutation of [0, n_jobs)); the rows have the batch's

@@ -91,6 +91,8 @@ struct HostLoader {
     const std::vector<uint32_t> *consts;
     uint32_t B, j;
     bool force_any;
+    GateWords lin;  // the cursor into the wave program's linear tables, as arith_level_body sets it up (ops_common.hpp)
+    bool has_lin() const { return lin != nullptr; }
     Fr29 load(uint32_t slot) const { return fr29_from((*W)[(size_t)slot * B + j]); }
     Fr29 load_inverse(uint32_t slot) const { return fr29_from((*Inv)[(size_t)slot * B + j]); }
     GateWords constant(uint32_t idx) const { return consts->data() + (size_t)idx * 8; }
@@ -150,7 +152,8 @@ int main(int argc, char **argv) {
         for (uint32_t q = p.level_start[L]; q < p.level_start[L + 1]; q++) {
             for (uint32_t j = 0; j < B; j++) {
                 const uint32_t *g = &p.gate_stream[p.gate_offset[q]];
-                HostLoader ld{&W, &Inv, &consts, B, j, (sm() & 3) == 0};
+                const uint32_t lin_at = p.lin_offset[q];
+                HostLoader ld{&W, &Inv, &consts, B, j, (sm() & 3) == 0, lin_at != GATE_LIN_NONE ? p.lin_tables.data() + (size_t)lin_at * GATE_LIN_TABLE_WORDS : nullptr};
                 Fr29 local = fr29_from(fr_zero());
                 bool host = true;
                 for (;;) {
