@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
     "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
     "acvm_batch_export_device_records", "acvm_batch_witness_records",
+    "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
     "acvm_debug_lin_add", "acvm_debug_lin_plan",
 ]
 
@@ -134,6 +135,43 @@ def record_out_desc(pitch, fields, first, n):
         fl.append(f)
     arr = (RecordOutField * max(len(fl), 1))(*fl)
     return RecordOutDesc(pitch=pitch, fields=arr, n_fields=len(fl), first=first, n=n), arr
+
+
+class RecordMaskedField(C.Structure):
+    """acvm_record_masked_field_t: RecordField with the byte `mask_offset` of the record saying whether the instance holds the element at all
+    (1: yes, 0: no; RECORD_NO_MASK: always). The layout of RecordOutField, witness -> position."""
+    _fields_ = [("position", C.c_uint32), ("encoding", C.c_uint32), ("offset", C.c_uint64), ("mask_offset", C.c_uint64)]
+
+
+class RecordMaskedDesc(C.Structure):
+    """acvm_record_masked_desc_t"""
+    _fields_ = [("pitch", C.c_uint64), ("fields", C.POINTER(RecordMaskedField)), ("n_fields", C.c_uint32)]
+
+
+def record_masked_desc(pitch, fields):
+    """(RecordMaskedDesc, the array its field pointer refers to) from the bytes between two records and (position, encoding, offset) or (position,
+    encoding, offset, mask_offset) tuples (mask_offset None: no mask byte) or RecordMaskedField objects"""
+    fl = []
+    for f in fields:
+        if not isinstance(f, RecordMaskedField):
+            f = tuple(f)
+            f = RecordMaskedField(f[0], f[1], f[2], RECORD_NO_MASK if len(f) < 4 or f[3] is None else f[3])
+        fl.append(f)
+    arr = (RecordMaskedField * max(len(fl), 1))(*fl)
+    return RecordMaskedDesc(pitch=pitch, fields=arr, n_fields=len(fl)), arr
+
+
+def record_masked_fields_from_out(out_fields, position_of):
+    """The masked import list of the next circuit from the field list of a record export: out_fields as record_out_desc takes them -- (witness,
+    encoding, offset[, mask_offset]) -- and position_of {witness of the exporting circuit: position among the importing circuit's initial ids}.
+    A field whose witness the map does not name is padding to the import; a witness exported in several fields is imported from the first."""
+    fields, seen = [], set()
+    for f in out_fields:
+        f = (f.witness, f.encoding, f.offset, None if f.mask_offset == RECORD_NO_MASK else f.mask_offset) if isinstance(f, RecordOutField) else tuple(f)
+        if f[0] in position_of and f[0] not in seen:
+            seen.add(f[0])
+            fields.append((position_of[f[0]], f[1], f[2], f[3] if len(f) > 3 else None))
+    return fields
 
 
 def record_fields_from_dtype(dtype, positions):
@@ -553,6 +591,10 @@ def lib():
         L.acvm_batch_set_initial_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordDesc), C.c_void_p]
         L.acvm_node_solve_records.restype = C.c_longlong
         L.acvm_node_solve_records.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(RecordDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_records_masked"):
+        L.acvm_batch_import_device_records_masked.argtypes = [C.c_void_p, C.POINTER(RecordMaskedDesc), C.c_void_p]
+        L.acvm_batch_set_initial_witness_records_masked.argtypes = [C.c_void_p, C.POINTER(RecordMaskedDesc), C.c_void_p]
+        L.acvm_debug_import_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "acvm_batch_export_device_records"):
         L.acvm_batch_export_device_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p, C.c_void_p]
         L.acvm_batch_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p]
@@ -1313,6 +1355,35 @@ class Batch:
             raise ValueError("records has the wrong size")
         desc, _keep = record_desc(pitch, fields)
         _check(lib().acvm_batch_set_initial_witness_records(self._h, C.byref(desc), buf.ctypes.data if buf.size else None))
+
+    def import_device_records_masked(self, d_ptr: int, pitch: int, fields):
+        """import_device_records for instances that do not all hold every initial witness (acvm_batch_import_device_records_masked). fields:
+        (position, encoding, offset, mask_offset) tuples or RecordMaskedField objects -- byte `mask_offset` of the record is 1 where the instance
+        holds the element and 0 where it does not (None, or a triple: always held). Several fields may share a mask byte. Any other byte raises,
+        and the batch is then without initial witnesses until another import. With no mask at all this is import_device_records.
+        record_masked_fields_from_out makes the list from the field list of another circuit's export_device_records."""
+        desc, _keep = record_masked_desc(pitch, fields)
+        _check(lib().acvm_batch_import_device_records_masked(self._h, C.byref(desc), d_ptr))
+
+    def set_initial_witness_records_masked(self, records, pitch: int, fields):
+        """import_device_records_masked from host memory (acvm_batch_set_initial_witness_records_masked): records as
+        set_initial_witness_records takes them"""
+        import numpy as np
+        buf = np.frombuffer(records, dtype=np.uint8) if not isinstance(records, np.ndarray) else np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+        if buf.size != self.B * pitch:
+            raise ValueError("records has the wrong size")
+        desc, _keep = record_masked_desc(pitch, fields)
+        _check(lib().acvm_batch_set_initial_witness_records_masked(self._h, C.byref(desc), buf.ctypes.data if buf.size else None))
+
+    def import_state(self) -> dict:
+        """what the last import left on the device (acvm_debug_import_state), as uint32 arrays: rows [n_initial][2][B][4], planes [n_initial][B],
+        events [2 + B], missing [ceil(n_initial / 32)][B]"""
+        import numpy as np
+        n = len(self.ids)
+        out = {"rows": np.zeros((n, 2, self.B, 4), dtype=np.uint32), "planes": np.zeros((n, self.B), dtype=np.uint32),
+               "events": np.zeros(2 + self.B, dtype=np.uint32), "missing": np.zeros(((n + 31) // 32, self.B), dtype=np.uint32)}
+        _check(lib().acvm_debug_import_state(self._h, *(out[k].ctypes.data for k in ("rows", "planes", "events", "missing"))))
+        return out
 
     def import_list_copies(self) -> int:
         """host-to-device copies of the imports' lists -- a descriptor's column list, the lists of import_device_parts -- this handle has made

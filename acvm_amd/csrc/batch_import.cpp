@@ -47,6 +47,11 @@ uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b) { return b ? b->n_
 // The parts one after the other, each with the rows, planes and columns of ITS inputs: from the list buffer, or -- a descriptor -- the handle's
 // resident tables.
 bool batch_launch_import(acvm_batch *b, const ImportPlan &plan, const uint32_t *gate) {
+    if (plan.record_masks) {  // (the masked tables and the masked kernel; import_masked_and_wait made the missing set ready and is never gated)
+        const uint32_t *windows = b->d_import_lists, *fields = windows + (size_t)plan.record_windows * RECORD_MWINDOW_WORDS;
+        return launch_import_records_masked(b->stream, plan.d_records, plan.record_pitch, windows, plan.record_windows, fields, b->d_W, b->Bp, b->B,
+                                            (uint32_t)b->plan().initial_ids.size(), b->d_byte_plane, b->d_event, b->d_missing, b->d_mask_result);
+    }
     if (plan.records) {  // (no parts: one launch over the window and field tables of the list buffer)
         const uint32_t *windows = b->d_import_lists, *fields = windows + (size_t)plan.record_windows * RECORD_WINDOW_WORDS;
         return launch_import_records(b->stream, plan.d_records, plan.record_pitch, windows, plan.record_windows, fields, b->d_W, b->Bp, b->B, gate, b->d_byte_plane, b->d_event);
@@ -152,16 +157,20 @@ static int missing_set_ready(acvm_batch *b) {
     }
     return 0;
 }
-static int import_masked_and_wait(acvm_batch *b, const ImportPlan &plan) {
-    if (!plan.masked()) return import_and_wait(b, plan);
+// what: whose bytes a refusal speaks of ("d_assigned", "record mask bytes"). A masked record plan carries its masks inside the import's own launch
+// (batch_launch_import); a descriptor's mask pass follows the value import here. Both end in the same wait, refusal and bookkeeping.
+static int import_masked_and_wait(acvm_batch *b, const ImportPlan &plan, const char *what = "d_assigned") {
+    if (!plan.masked() && !plan.record_masks) return import_and_wait(b, plan);
     HIPCHK(hipSetDevice(b->device));
     if (int rc = missing_set_ready(b)) return rc;  // (in front of everything: a refusal so far leaves the handle as it was)
     if (int rc = batch_import_plan_async(b, plan, nullptr, nullptr)) return rc;
-    const ImportPlanPart &pt = plan.parts[0];  // (a descriptor's plan: one resident part)
-    const uint32_t *columns = pt.columns_at != IMPORT_NO_LIST ? b->d_import_lists + pt.columns_at : nullptr;
     // (d_mask_result is zero here: since its allocation, or since the memset the previous masked import left behind on the stream)
-    launch_import_mask(b->stream, ImportMaskSource{plan.d_assigned, pt.layout, columns, pt.stride}, b->d_W, b->Bp, b->B, b->reuse() ? b->d_init_rows : b->d_init_ids, pt.n,
-                       b->d_byte_plane_of_input, b->d_byte_plane, b->d_missing, b->d_mask_result);
+    if (plan.masked()) {
+        const ImportPlanPart &pt = plan.parts[0];  // (a descriptor's plan: one resident part)
+        const uint32_t *columns = pt.columns_at != IMPORT_NO_LIST ? b->d_import_lists + pt.columns_at : nullptr;
+        launch_import_mask(b->stream, ImportMaskSource{plan.d_assigned, pt.layout, columns, pt.stride}, b->d_W, b->Bp, b->B, b->reuse() ? b->d_init_rows : b->d_init_ids, pt.n,
+                           b->d_byte_plane_of_input, b->d_byte_plane, b->d_missing, b->d_mask_result);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(b->h_mask_result, b->d_mask_result, IMPORT_MASK_RESULT_WORDS * 8, hipMemcpyDeviceToHost, b->stream));
     HIPCHK(hipStreamSynchronize(b->stream));
@@ -172,7 +181,7 @@ static int import_masked_and_wait(acvm_batch *b, const ImportPlan &plan) {
         // The host could not see the bytes beforehand and the rows are written: the handle is left without initial witnesses.
         b->inputs_set = false;
         const uint32_t j = import_mask_key_instance(result[IMPORT_MASK_BAD_KEY]), k = import_mask_key_position(result[IMPORT_MASK_BAD_KEY]);
-        return set_err(ACVM_E_INVALID, "d_assigned: " + std::to_string(result[IMPORT_MASK_BAD]) + " elements are neither 0 nor 1, the first of them instance " + std::to_string(j) +
+        return set_err(ACVM_E_INVALID, std::string(what) + ": " + std::to_string(result[IMPORT_MASK_BAD]) + " elements are neither 0 nor 1, the first of them instance " + std::to_string(j) +
                                            ", position " + std::to_string(k) + " (initial witness " + std::to_string(b->plan().initial_ids[k]) +
                                            "); the handle is left without initial witnesses");
     }
@@ -241,4 +250,64 @@ int acvm_batch_set_initial_witness_records(acvm_batch_t *b, const acvm_record_de
     if (bytes) HIPCHK(hipMemcpyAsync(b->d_stage, records, bytes, hipMemcpyHostToDevice, b->stream));
     plan.d_records = b->d_stage;
     return import_and_wait(b, plan);
+} ABI_CATCH
+
+// ---- the masked record import (include/acvm_amd.h acvm_batch_import_device_records_masked): record_plan.cpp checks and cuts, the masked kernel
+// reads values and presence bytes in one pass, and the call ends as the masked column import ends (import_masked_and_wait). No field with a mask:
+// the plan is the unmasked call's, and so is everything behind it.
+static int import_plan_records_masked_of(const acvm_batch *b, const acvm_record_masked_desc_t *d, const void *d_records, ImportPlan *out) {
+    const ImportView view = b ? import_view(b) : ImportView{};
+    std::string err;
+    const int rc = import_plan_records_masked(b ? &view : nullptr, d, d_records, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+// staged: the records lie in the caller's HOST memory and go through the staging buffer first (a refused descriptor copies nothing)
+static int import_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *records, bool staged) {
+    ImportPlan plan;
+    if (int rc = import_plan_records_masked_of(b, d, records, &plan)) return rc;
+    if (staged) {
+        const size_t bytes = d->n_fields ? (size_t)b->B * d->pitch : 0;
+        HIPCHK(hipSetDevice(b->device));
+        if (int rc = stage_reserve(b, bytes)) return rc;
+        if (bytes) HIPCHK(hipMemcpyAsync(b->d_stage, records, bytes, hipMemcpyHostToDevice, b->stream));
+        plan.d_records = b->d_stage;
+    }
+    return import_masked_and_wait(b, plan, "record mask bytes");
+}
+int acvm_batch_import_device_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *d_records) try {
+    return import_records_masked(b, d, d_records, false);
+} ABI_CATCH
+int acvm_batch_set_initial_witness_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *records) try {
+    return import_records_masked(b, d, records, true);
+} ABI_CATCH
+
+// What the last import left (include/acvm_amd.h): rows, planes, event words and missing set of the live instances, for the tests that compare two
+// import entry points bit for bit.
+int acvm_debug_import_state(acvm_batch_t *b, uint32_t *rows, uint32_t *planes, uint32_t *events, uint32_t *missing) try {
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipStreamSynchronize(b->stream));
+    const Plan &p = b->plan();
+    const uint32_t n_in = (uint32_t)p.initial_ids.size(), B = b->B;
+    for (uint32_t k = 0; k < n_in && B; k++) {
+        const uint32_t row = b->reuse() ? b->init_rows[k] : p.initial_ids[k];
+        if (rows)
+            for (uint32_t half = 0; half < 2; half++)
+                HIPCHK(hipMemcpy(rows + ((size_t)k * 2 + half) * B * 4, b->d_W + ((uint64_t)row * 2 + half) * b->Bp, (size_t)B * 16, hipMemcpyDeviceToHost));
+        if (planes) {
+            const uint32_t pl = p.n_byte_planes ? b->plane_of_input[k] : 0xFFFFFFFFu;
+            if (pl == 0xFFFFFFFFu) std::fill(planes + (size_t)k * B, planes + (size_t)(k + 1) * B, 0u);
+            else HIPCHK(hipMemcpy(planes + (size_t)k * B, b->d_byte_plane + (uint64_t)pl * b->Bp, (size_t)B * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    if (events) {
+        HIPCHK(hipMemcpy(events, b->d_event - 4, 8, hipMemcpyDeviceToHost));
+        if (B) HIPCHK(hipMemcpy(events + 2, b->d_event, (size_t)B * 4, hipMemcpyDeviceToHost));
+    }
+    if (missing)
+        for (uint32_t word = 0; word < import_missing_words(n_in) && B; word++) {
+            if (!b->d_missing) std::fill(missing + (size_t)word * B, missing + (size_t)(word + 1) * B, 0u);
+            else HIPCHK(hipMemcpy(missing + (size_t)word * B, b->d_missing + (uint64_t)word * b->Bp, (size_t)B * 4, hipMemcpyDeviceToHost));
+        }
+    return 0;
 } ABI_CATCH

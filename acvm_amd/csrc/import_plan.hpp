@@ -62,11 +62,14 @@ struct ImportPlan {
     // pitch, window count and tables are, and the solve_then_import entry points take none: it never counts as the import that ran behind a
     // solve. (Like d_values the pointer d_records is not compared.)
     bool records = false;
+    // acvm_batch_import_device_records_masked (record_plan.hpp import_plan_records_masked) with at least one mask byte: a record plan whose
+    // tables are the wider masked ones and whose launch is the masked kernel's (kernels_records_masked.hip). Never equal to an unmasked plan.
+    bool record_masks = false;
     uint64_t record_pitch = 0;
     uint32_t record_windows = 0;
     const void *d_records = nullptr;
     bool operator==(const ImportPlan &o) const {
-        return masked() == o.masked() && plain == o.plain && records == o.records && record_pitch == o.record_pitch && record_windows == o.record_windows && parts == o.parts &&
+        return masked() == o.masked() && plain == o.plain && records == o.records && record_masks == o.record_masks && record_pitch == o.record_pitch && record_windows == o.record_windows && parts == o.parts &&
                lists == o.lists;
     }
 };

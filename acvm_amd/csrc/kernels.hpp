@@ -127,6 +127,11 @@ bool launch_import_typed(hipStream_t s, const ImportDevice &x, uint4 *W, uint64_
 // launch_import.
 bool launch_import_records(hipStream_t s, const void *in, uint64_t pitch, const uint32_t *windows, uint32_t n_windows, const uint32_t *fields, uint4 *W, uint64_t Bp,
                            uint32_t B, const uint32_t *gate, uint32_t *plane, uint32_t *event_reset);
+// ---- kernels_records_masked.hip (acvm_batch_import_device_records_masked): launch_import_records over the masked tables of record_plan.hpp. In
+// front of the kernel the words of the missing set of the live instances are zeroed on the stream, behind it the instances with an absent input
+// are counted into result (import_mask.hpp: three words, zero before the call). Never gated. Returns what launch_import returns.
+bool launch_import_records_masked(hipStream_t s, const void *in, uint64_t pitch, const uint32_t *windows, uint32_t n_windows, const uint32_t *fields, uint4 *W, uint64_t Bp,
+                                  uint32_t B, uint32_t n_in, uint32_t *plane, uint32_t *event_reset, uint32_t *missing, uint64_t *result);
 // ---- kernels_import_mask.hip (acvm_batch_import_device_masked; import_mask.hpp: where a mask byte lies, the missing set, the result words)
 struct ImportMaskSource {
     const uint8_t *mask;      // the caller's d_assigned: one byte per element in the values' layout, stride and column list; any alignment

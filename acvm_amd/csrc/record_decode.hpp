@@ -59,6 +59,22 @@ FR_HD __forceinline__ void record_assemble(const uint32_t *words, uint32_t byte,
     hi = make_uint4(v[4], v[5], v[6], v[7]);
 }
 
+// ---- the masked record import (kernels_records_masked.hip, include/acvm_amd.h acvm_batch_import_device_records_masked)
+// The presence byte of a field whose mask byte lies in the block's window: byte `byte` (phase + offset in the window) of a record's word image.
+FR_HD __forceinline__ uint32_t record_presence_byte(const uint32_t *words, uint32_t byte) { return (words[byte / 4u] >> (8u * (byte & 3u))) & 0xffu; }
+// A block ORs the missing-set bits (import_mask.hpp) of its window's fields in LDS before anything goes to global memory: RECORD_MISS_SLOTS words
+// per instance, slot s for the missing word `base + s`, base the lowest word a field of the window has (the window table carries it). A field
+// whose word lies further up has no slot -- RECORD_MISS_NO_SLOT -- and its absent lanes go to global memory one by one. Slot-major: lane i of a
+// wave falls on bank i, whatever the slot.
+constexpr uint32_t RECORD_MISS_SLOTS = 8u;  // 8 x 64 words = 2 KiB beside the image's 16 640 bytes: eight blocks of 256 threads still fill a CU
+constexpr uint32_t RECORD_MISS_LDS_WORDS = RECORD_MISS_SLOTS * RECORD_BLOCK_INSTANCES;
+constexpr uint32_t RECORD_MISS_NO_SLOT = 0xFFFFFFFFu;
+FR_HD __forceinline__ uint32_t record_miss_slot(uint32_t position, uint32_t base_word) {
+    const uint32_t s = (position >> 5) - base_word;  // (position >> 5 >= base_word by the table's construction; a wrap is above the slots too)
+    return s < RECORD_MISS_SLOTS ? s : RECORD_MISS_NO_SLOT;
+}
+FR_HD __forceinline__ uint32_t record_miss_lds_word(uint32_t slot, uint32_t instance_in_block) { return slot * RECORD_BLOCK_INSTANCES + instance_in_block; }
+
 // One element of a record, everything (the kernel takes a wave of bytes from fr_mont_of_byte instead of the product: the same row)
 FR_HD __forceinline__ ImportDecoded record_decode(const uint32_t *words, uint32_t byte, uint32_t encoding) {
     const uint32_t size = export_element_size(encoding);

@@ -813,8 +813,8 @@ uint64_t acvm_debug_import_list_copies(const acvm_batch_t *b);
  *     host-to-device copy is made: the field table, which is reused while it does not change (acvm_debug_import_list_copies counts it).
  *     Works with ACVM_BATCH_REUSE_SLOTS (rows are not ids), with a caller's solver, and after acvm_batch_set_instances.
  * acvm_batch_set_initial_witness_records is the host form: B * pitch bytes go through the handle's staging buffer, then the device path runs.
- * Not here: a mask byte inside the record (the record EXPORT below writes one); an acvm_batch_solve_then_import form; records for the lanes
- * of acvm_node_solve_device; big-endian or sign-extending narrow fields.
+ * Not here: a mask byte inside the record (acvm_batch_import_device_records_masked below reads one); an acvm_batch_solve_then_import form;
+ * records for the lanes of acvm_node_solve_device; big-endian or sign-extending narrow fields.
  */
 typedef struct {
     uint32_t position;   /* which initial witness: position in the initial_ids given to acvm_batch_new */
@@ -858,8 +858,8 @@ int acvm_batch_set_initial_witness_records(acvm_batch_t *b, const acvm_record_de
  *     do not change.
  * acvm_batch_witness_records is the host form: the device path runs into a zero-filled staging buffer, then n * pitch bytes are copied down.
  * Here the padding IS written, as zero.
- * Not here: a node form; an asynchronous variant; outcome columns (status, err) as record fields; a mask byte for the record import;
- * big-endian or sign-extending narrow fields.
+ * Not here: a node form; an asynchronous variant; outcome columns (status, err) as record fields; big-endian or sign-extending narrow fields.
+ * (The mask bytes written here are read by acvm_batch_import_device_records_masked below.)
  */
 #define ACVM_RECORD_NO_MASK UINT64_MAX
 typedef struct {
@@ -877,6 +877,52 @@ typedef struct {
 int acvm_batch_export_device_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, const uint32_t *d_instances /* DEVICE, or NULL = the range */,
                                      void *d_records);
 int acvm_batch_witness_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, void *records /* host, n * pitch bytes */);
+/*
+ * Masked record import: the record import for per-instance PARTIAL initial witness maps. A field may name a presence byte inside the record -- a
+ * Rust Option<T> laid out as { valid: u8, value: T }, a nullable database column, and what the record export above writes: its field list with
+ * witness -> position IS this call's field list, so the records of one circuit feed the next without a pass in between.
+ *   - Values and checks: those of acvm_batch_import_device_records on (pitch, position, encoding, offset), unchanged and in the same order.
+ *   - Mask byte 1: the instance holds that initial witness, with the decoded value. 0: it does not -- the row is zero afterwards, its byte-plane
+ *     word is 0x80000000, the bit of (instance, position) is set in the handle's missing set, and the bytes of the absent element influence
+ *     nothing, non-canonical 256-bit strings included. A field with ACVM_RECORD_NO_MASK is always held.
+ *   - Any other byte is refused exactly as acvm_batch_import_device_masked refuses it -- the 2 the record export writes for a narrow value that
+ *     did not fit too: behind the import, ACVM_E_INVALID, the message gives the number of offending elements (a mask byte that several fields
+ *     name counts once per field) and names the one of the lowest instance and, in it, the lowest position, and the handle is left WITHOUT
+ *     initial witnesses.
+ *   - mask_offset >= pitch is refused on the host, naming the field, behind the checks of the unmasked call; the handle is left as it was.
+ *   - Several fields may name the same mask byte (one `valid` byte for a whole struct). A mask byte may lie anywhere in the record, inside another
+ *     field's bytes included; reads may overlap, as the import allows anyway.
+ *   - No field has a mask: the call IS acvm_batch_import_device_records -- word for word the same tables, the same kernel, nothing else launched,
+ *     and acvm_debug_import_missing is 0.
+ *   - Leaves the handle exactly as acvm_batch_import_device_masked leaves it for the same values and presence bits: rows, planes, the event
+ *     words reset once, every word of the missing set of the live instances rewritten (a bit of an earlier masked import does not survive),
+ *     acvm_debug_import_missing. Everything behind it -- the solve of an instance with an absent input, reset, stepping, slot reuse, a caller's
+ *     solver -- is what is described there. Every other import entry point leaves every instance holding every input again.
+ *   - No load touches a 4-byte-aligned word that holds no byte of [d_records, d_records + B * pitch). A mask byte further than 256 bytes from its
+ *     element in a longer record is read with a byte load of its own; every other one comes with the lines the element needs anyway.
+ *   - Synchronous. What comes back from the device is three words, nothing per instance.
+ * acvm_batch_set_initial_witness_records_masked is the host form: B * pitch bytes go through the handle's staging buffer, then the device path.
+ * acvm_debug_import_state reads back what any import left: for the tests that compare two entry points bit for bit.
+ * Not here: masks for acvm_node_solve_records; an acvm_batch_solve_then_import form; big-endian or sign-extending narrow fields.
+ */
+typedef struct {
+    uint32_t position;     /* as acvm_record_field_t */
+    uint32_t encoding;
+    uint64_t offset;
+    uint64_t mask_offset;  /* byte offset of this field's presence byte inside the record, or ACVM_RECORD_NO_MASK */
+} acvm_record_masked_field_t;      /* same layout as acvm_record_out_field_t, witness -> position */
+typedef struct {
+    uint64_t pitch;
+    const acvm_record_masked_field_t *fields;   /* HOST, copied before the call returns */
+    uint32_t n_fields;
+} acvm_record_masked_desc_t;
+int acvm_batch_import_device_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *d_records);
+int acvm_batch_set_initial_witness_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *records /* host */);
+/* What the last import left on the device, copied down (each pointer may be NULL): rows [n_initial][2][B][4] words -- the two 16-byte halves of
+ * each initial witness' row as the kernels keep them; planes [n_initial][B] -- the byte-plane word, 0 for an input without a plane; events
+ * [2 + B] -- the two header words, then one word per live instance; missing [(n_initial + 31) / 32][B] -- the missing set, zero for a handle no
+ * masked import has touched. B: the live instances. Waits for the batch's stream. */
+int acvm_debug_import_state(acvm_batch_t *b, uint32_t *rows, uint32_t *planes, uint32_t *events, uint32_t *missing);
 
 /*
  * WitnessMap wire format (acir/src/native_types/witness_map.rs:108-146; acvm_js compressWitness / decompressWitness):

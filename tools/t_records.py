@@ -9,6 +9,14 @@
     turn: instances/s, the host-to-device bytes of the inputs (instances x row size: what the upload thread copies), and whether results and
     kept witnesses agree (checked on a separate, smaller call that asks for them).
 
+ 4. the masked record import (acvm_batch_import_device_records_masked) in alternating legs, 2^16 and 2^17 instances of config 3's 64 byte inputs
+    and of a 64 x Field record, each with the mask bytes beside their elements ({valid, value} pairs) and gathered at the record's head (for
+    the Field record that is the far form): (i) the unmasked record import of the same buffer, (ii) masked with nothing absent, (iii) with one
+    instance in 1 000 absent and with everyone absent, (iv) what a caller did before: (i) plus the mask pass of acvm_batch_import_device_masked
+    over a column mask of the same bits -- the mask pass is not callable alone, so its time is the masked column import minus the unmasked
+    column import of the same values. The legs are timed twice: rotated (a leg then pays for what its predecessor left on the stream) and each
+    on its own, back to back. `--only-masked` runs this section alone.
+
 Wall time of the synchronous call: a launch and a stream synchronisation, tens of microseconds of which are not the kernel's. For kernel times
 run under `rocprofv3 --kernel-trace --stats` and read import_records_kernel / import_narrow_im_kernel / import_witness_kernel.
     python tools/t_records.py [--log2-tile 16] [--rounds 21] [--pairs 3] [--log2-total 20] [--e2e-rounds 3]"""
@@ -30,6 +38,8 @@ ap.add_argument("--rounds", type=int, default=21, help="timed calls per run")
 ap.add_argument("--pairs", type=int, default=3, help="A-B pairs of section 1")
 ap.add_argument("--log2-total", type=int, default=20, help="instances of the end-to-end section (0: skip it)")
 ap.add_argument("--e2e-rounds", type=int, default=3)
+ap.add_argument("--only-masked", action="store_true", help="section 4 alone")
+ap.add_argument("--masked-rounds", type=int, default=15, help="rotations of section 4's legs")
 args = ap.parse_args()
 U8, U32, BE32, IM = acvm_amd.ENC_U8, acvm_amd.ENC_U32, acvm_amd.ENC_BE32, acvm_amd.LAYOUT_INSTANCE_MAJOR
 
@@ -56,6 +66,90 @@ def be32_rows(values):
     out[..., 24:] = values.astype(">u8")[..., None].view(np.uint8).reshape(values.shape + (8,))
     return out
 
+
+# ---- 4. the masked record import (defined here, run last -- or alone)
+def masked_section():
+    L = acvm_amd.lib()
+    rng = np.random.default_rng(0x4EC04D6)
+    ceiling = acvm_amd.stream_rate()
+    print(f"4. masked record import; streaming ceiling of this device {ceiling:.0f} GB/s; wall us of the synchronous call, median (min) of "
+          f"{args.masked_rounds} rotations of the legs, then of {args.masked_rounds} calls of each leg back to back", flush=True)
+    n = 64
+    hash_circ, hash_ids = synth.hash_circuit(n_msg=32)
+    circuits = {"bytes": (acvm_amd.Circuit(hash_circ.to_bytes()), hash_ids, U8, 1),
+                "fields": (acvm_amd.Circuit(Circuit(2 * n, [E([], [(3, k), (P - 1, n + k)], 1) for k in range(1, n + 1)]).to_bytes()), list(range(1, n + 1)), BE32, 32)}
+    for log2 in (16, 17):
+        B = 1 << log2
+        for shape, (gc4, ids4, enc, size) in circuits.items():
+            assert len(ids4) == n
+            batch4 = acvm_amd.Batch(gc4, B, ids4)
+            planes4 = batch4.stats()["n_byte_planes"]
+            vals = rng.integers(0, 256, (B, n, size), dtype=np.uint8)
+            if size == 32:
+                vals[:, :, 0] &= 0x1F  # (below p)
+            held = {"none": np.ones((B, n), dtype=np.uint8), "1 in 1000": np.ones((B, n), dtype=np.uint8), "everyone": np.ones((B, n), dtype=np.uint8)}
+            j = np.arange(B)
+            held["1 in 1000"][j[::1000], j[::1000] % n] = 0
+            held["everyone"][j, j % n] = 0
+            written = B * n * 32 + B * planes4 * 4 + B * 4
+            d_cols, d_mask = acvm_amd.DeviceBuffer(vals.tobytes()), {k: acvm_amd.DeviceBuffer(h.tobytes()) for k, h in held.items()}
+            cdesc = acvm_amd.ImportDesc(encoding=enc, layout=IM)
+            for where in ("beside", "head"):
+                pitch = n * (size + 1)
+                if where == "beside":
+                    fl = [(k, enc, k * (size + 1) + 1, k * (size + 1)) for k in range(n)]
+                else:
+                    fl = [(k, enc, n + k * size, k) for k in range(n)]
+                far = sum(max(f[2] + size, f[3] + 1) - min(f[2], f[3]) > 256 for f in fl) if pitch > 256 else 0
+                bufs = {}
+                for k, h in held.items():
+                    rec = np.zeros((B, pitch), dtype=np.uint8)
+                    for f in fl:
+                        rec[:, f[2]:f[2] + size] = vals[:, f[0]]
+                        rec[:, f[3]] = h[:, f[0]]
+                    bufs[k] = acvm_amd.DeviceBuffer(rec.tobytes())
+                    del rec
+                udesc4, _k1 = acvm_amd.record_desc(pitch, [f[:3] for f in fl])
+                mdesc4, _k2 = acvm_amd.record_masked_desc(pitch, fl)
+                legs = {
+                    "(i) unmasked record import": lambda: L.acvm_batch_import_device_records(batch4._h, udesc4, bufs["none"].ptr),
+                    "(ii) masked, nothing absent": lambda: L.acvm_batch_import_device_records_masked(batch4._h, mdesc4, bufs["none"].ptr),
+                    "(iii) masked, 1 in 1000 absent": lambda: L.acvm_batch_import_device_records_masked(batch4._h, mdesc4, bufs["1 in 1000"].ptr),
+                    "(iii) masked, everyone absent": lambda: L.acvm_batch_import_device_records_masked(batch4._h, mdesc4, bufs["everyone"].ptr),
+                    "column import, no mask": lambda: L.acvm_batch_import_device(batch4._h, cdesc, d_cols.ptr),
+                    "column import + mask pass, nothing absent": lambda: L.acvm_batch_import_device_masked(batch4._h, cdesc, d_cols.ptr, d_mask["none"].ptr),
+                    "column import + mask pass, everyone absent": lambda: L.acvm_batch_import_device_masked(batch4._h, cdesc, d_cols.ptr, d_mask["everyone"].ptr),
+                }
+                times = {k: [] for k in legs}
+                for fn in legs.values():
+                    assert fn() == 0
+                for _ in range(args.masked_rounds):
+                    for k, fn in legs.items():
+                        t0 = time.perf_counter()
+                        fn()
+                        times[k].append((time.perf_counter() - t0) * 1e6)
+                med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+                # ... and each leg on its own, back to back as sections 1 and 2 time theirs: what a rotation adds to a leg is its predecessor's
+                alone = {k: timed(fn, args.masked_rounds) for k, fn in legs.items()}
+                print(f"  2^{log2} x {shape}, mask bytes {where} ({far} of {n} far), pitch {pitch}: {B * pitch / 1e6:.1f} MB read, {written / 1e6:.1f} MB written", flush=True)
+                for k, v in times.items():
+                    moved = written + (B * pitch if k.startswith("(") else B * n * size + (B * n if "mask pass" in k else 0))
+                    solo = alone[k][len(alone[k]) // 2]
+                    print(f"    {k:44s} {med[k]:8.1f} ({min(v):8.1f}) us | {moved / med[k] / 1e3:6.0f} GB/s, {moved / med[k] / 1e3 / ceiling:5.2f} of the ceiling"
+                          f" | back to back {solo:8.1f} ({alone[k][0]:8.1f}) us, {moved / solo / 1e3 / ceiling:5.2f}", flush=True)
+                for tag in ("nothing", "everyone"):
+                    pass_us = med[f"column import + mask pass, {tag} absent"] - med["column import, no mask"]
+                    print(f"    (iv) record import + the mask pass, {tag} absent: {med['(i) unmasked record import']:.1f} + {pass_us:.1f} = "
+                          f"{med['(i) unmasked record import'] + pass_us:.1f} us", flush=True)
+                for x in bufs.values():
+                    x.free()
+            for x in [d_cols, batch4] + list(d_mask.values()):
+                x.free()
+
+
+if args.only_masked:
+    masked_section()
+    sys.exit(0)
 
 # ---- 1. dense byte records on config 3's tile
 B = 1 << args.log2_tile
@@ -138,3 +232,5 @@ if args.log2_total:
     same = a[0] == b[0] and [r.as_tuple() for r in a[1]] == [r.as_tuple() for r in b[1]] and all(np.array_equal(a[k], b[k]) for k in (2, 3, 4))
     print(f"  results, kept witnesses, assigned bytes and digests of the first {n_check} instances agree: {bool(same)}", flush=True)
     node.free()
+
+masked_section()
