@@ -6,6 +6,7 @@
 //   Directive::ToLeRadix   acvm/src/pwg/directives/mod.rs:60-87
 //   MemoryInit / MemoryOp  acvm/src/pwg/memory_op.rs:16-124
 // Record layouts are produced by plan.cpp (emit_* functions) and documented there.
+// Edge inputs of the integer routines with their expected values in integers: tests/int_cases.py, run by tests/test_gpu_int_edges.py.
 #pragma once
 #include "ops_common.hpp"
 

@@ -5,6 +5,7 @@ import pytest
 
 from acvm_amd.acir import (Arithmetic, BlackBoxFuncCall, Brillig, Circuit, Expression, FunctionInput, MemoryInit,
                            MemoryOp, P, QuotientDirective, ToLeRadix)
+from int_cases import ref_int_op
 
 M1 = P - 1
 
@@ -276,37 +277,6 @@ def test_config1_fixture(oracle):
     assert hashlib.sha256(vals[0, 1:fx["n_witnesses"] + 1].tobytes()).hexdigest() == fx["sha256_of_witnesses_1_to_n"]
     for w, v in fx["witnesses"].items():
         assert vals[0, int(w)].tobytes().hex() == v
-
-
-def ref_int_op(op, a, b, bits):
-    """evaluate_binary_bigint_op (brillig_vm/src/arithmetic.rs:23-98) with Python integers, then FieldElement::from_be_bytes_reduce: the
-    reference's BigUint arithmetic takes ANY bit_size. Returns the field value, or None where the reference panics."""
-    m = 1 << bits
-
-    def signed(x):
-        return x if x < (1 << (bits - 1)) else x - 2 * (1 << (bits - 1))
-    if op == "Add":
-        r = (a + b) % m
-    elif op == "Sub":
-        r = (m + a - b) % m if m + a - b >= 0 else None
-    elif op == "Mul":
-        r = (a * b) % m
-    elif op == "UnsignedDiv":
-        r = (a % m) // (b % m) if b % m else None
-    elif op == "SignedDiv":
-        if bits == 0 or signed(b) == 0:
-            return None
-        sa, sb = signed(a), signed(b)
-        q = abs(sa) // abs(sb) * (1 if (sa < 0) == (sb < 0) else -1)  # BigInt division truncates toward zero
-        r = q if q >= 0 else (m + q if m + q >= 0 else None)
-    elif op in ("Equals", "LessThan", "LessThanEquals"):
-        x, y = a % m, b % m
-        r = int(x == y if op == "Equals" else x < y if op == "LessThan" else x <= y)
-    elif op in ("And", "Or", "Xor"):
-        r = (a & b if op == "And" else a | b if op == "Or" else a ^ b) % m
-    else:
-        return None
-    return None if r is None else r % P
 
 
 @pytest.mark.parametrize("bits", [255, 256, 257, 300, 400, 507, 508, 509, 512, 1000, (1 << 20) + 3])
