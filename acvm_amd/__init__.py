@@ -29,7 +29,7 @@ LAYOUT_BROADCAST = 16  # parts of import_device_parts only: one element per colu
 # every symbol include/acvm_amd.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
     "acvm_last_error", "acvm_abi_version", "acvm_device_count", "acvm_set_device", "acvm_device_synchronize",
-    "acvm_device_arch", "acvm_selftest", "acvm_debug_grumpkin", "acvm_debug_secp", "acvm_circuit_from_bytes", "acvm_circuit_free", "acvm_circuit_num_opcodes",
+    "acvm_device_arch", "acvm_selftest", "acvm_debug_grumpkin", "acvm_debug_grumpkin_items", "acvm_debug_secp", "acvm_circuit_from_bytes", "acvm_circuit_free", "acvm_circuit_num_opcodes",
     "acvm_circuit_num_witnesses", "acvm_circuit_plan_stats", "acvm_batch_new", "acvm_batch_free", "acvm_batch_set_initial_witness",
     "acvm_batch_set_initial_witness_device", "acvm_batch_solve", "acvm_batch_solve_then_import", "acvm_batch_reset", "acvm_batch_set_instances", "acvm_batch_set_force_slow_path",
     "acvm_batch_results", "acvm_batch_witness", "acvm_batch_witness_map", "acvm_batch_stats",
@@ -490,6 +490,8 @@ def lib():
     L.acvm_device_arch.argtypes = [C.c_char_p, C.c_size_t]
     L.acvm_selftest.argtypes = [C.c_uint32, C.c_uint64]
     L.acvm_debug_grumpkin.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p]
+    if hasattr(L, "acvm_debug_grumpkin_items"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has no such probe)
+        L.acvm_debug_grumpkin_items.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     if hasattr(L, "acvm_debug_secp"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has no such probe)
         L.acvm_debug_secp.argtypes = [C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p]
     L.acvm_circuit_from_bytes.restype = C.c_void_p
@@ -793,6 +795,23 @@ def debug_grumpkin(what, param, inputs=()):
     data = b"".join(int(v).to_bytes(32, "big") for v in inputs)
     _check(lib().acvm_debug_grumpkin(what, param, data, len(inputs), out))
     return int.from_bytes(out.raw[:32], "big"), int.from_bytes(out.raw[32:], "big")
+
+
+# acvm_debug_grumpkin_items: u32 words per item (in, out) of every `what` (acvm_amd/csrc/kernels_grumpkin.hip grumpkin_items_words)
+GRUMPKIN_ITEM_WORDS = ((27, 27), (45, 36), (54, 27), (27, 17), (8, 62), (8, 17), (32, 17), (32, 17))
+
+
+def debug_grumpkin_items(what, items, param=0):
+    """One routine of the Grumpkin device header per call, one device lane per item (see include/acvm_amd.h): items = an array [n][words in] of raw u32
+    words; returns the raw result words as a uint32 array [n][words out]."""
+    import numpy as np
+    if not 0 <= what < len(GRUMPKIN_ITEM_WORDS):
+        _check(lib().acvm_debug_grumpkin_items(what, param, None, 0, None))
+    wi, wo = GRUMPKIN_ITEM_WORDS[what]
+    a = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, wi)
+    out = np.zeros((a.shape[0], wo), dtype=np.uint32)
+    _check(lib().acvm_debug_grumpkin_items(what, param, a.ctypes.data, a.shape[0], out.ctypes.data))
+    return out
 
 
 # acvm_debug_table_info / _read: the lookup tables by number; acvm_debug_batch_tables: the bits of the mask

@@ -261,6 +261,10 @@ struct ExactScratch { uint32_t *hash, *grumpkin, *brillig; };
 void launch_exact_run(hipStream_t s, uint4 *W, uint64_t Bp, const DeviceProgram &dp, const ExactLanes &L, uint32_t op_begin, uint32_t op_end, bool replay_memory,
                       const uint8_t *prog_class, const ExactScratch &sc);
 void launch_grumpkin_probe(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_in, uint32_t *out);
+// one lane per item (acvm_debug_grumpkin_items); scratch: Bp x GRUMPKIN_VARBASE_SCRATCH_WORDS words for what = 6, Bp a multiple of 64 that covers n_items
+uint32_t grumpkin_items_words(uint32_t what, bool out);
+void launch_grumpkin_items(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_items, uint32_t *out, uint32_t *scratch,
+                           uint64_t Bp);
 void launch_table_gather(hipStream_t s, const uint4 *table, const uint64_t *entries, uint32_t n, uint4 *out);  // (acvm_debug_table_read)
 // ECDSA (kernels_ecdsa.hip; the generator tables d * 2^(16 j) * G of both curves: grumpkin_host.hpp ecdsa_generator_tables)
 void launch_secp_probe(hipStream_t s, uint32_t curve, uint32_t what, const uint32_t *in, uint32_t n_items, uint32_t words_in, uint32_t words_out, uint32_t *out,

@@ -401,6 +401,71 @@ __global__ void grumpkin_probe_kernel(GrumpkinTables T, uint32_t what, uint32_t 
 void launch_grumpkin_probe(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_in, uint32_t *out) {
     hipLaunchKernelGGL(grumpkin_probe_kernel, dim3(1), dim3(64), 0, s, T, what, param, in, n_in, out);
 }
+// ---- one lane per item (acvm_debug_grumpkin_items): raw u32 words in and out, `wi` / `wo` words per item (grumpkin_items_words below). Field elements of
+// what 0..3 travel as the nine 29-bit limbs of the working form, AS GIVEN: the caller picks the representative (class A: below 2p), and results leave as
+// the limbs the routine returned, unreduced. Integers (what 4..7) are canonical 8 x u32, little-endian.
+//   0  X Y Z              -> gj_dbl                                                   27 -> 27
+//   1  X Y Z x2 y2        -> gj_add_aff29, then zr (zero limbs where the routine leaves it alone)   45 -> 36
+//   2  X1 Y1 Z1 X2 Y2 Z2  -> gj_add                                                   54 -> 27
+//   3  X Y Z              -> gj_to_aff: x, y in the storage form as returned, then the infinity flag   27 -> 17
+//   4  k                  -> glv_split: |k1| (4), |k2| (4), neg1, neg2, then signed_windows5 of each: 26 + 26 digits, magnitude | 32 if negative   8 -> 62
+//   5  v                  -> ladder_term(v, param) as a canonical affine point, then the infinity flag   8 -> 17
+//   6, 7  pkx pky s e     -> grumpkin_schnorr_point after reduce_mod_q(s), reduce_mod_q(e): canonical x, y, then the infinity flag; 6 with the lane's window
+//                            table in `scratch` (GRUMPKIN_VARBASE_SCRATCH_WORDS words per lane, Bp lanes), 7 with nullptr: the Brillig path   32 -> 17
+uint32_t grumpkin_items_words(uint32_t what, bool out) {
+    static const uint32_t WI[8] = {27, 45, 54, 27, 8, 8, 32, 32}, WO[8] = {27, 36, 27, 17, 62, 17, 17, 17};
+    return what < 8u ? (out ? WO[what] : WI[what]) : 0u;
+}
+__global__ void __launch_bounds__(64) grumpkin_items_kernel(GrumpkinTables T, uint32_t what, uint32_t param, const uint32_t *__restrict__ in, uint32_t n_items, uint32_t wi,
+                                                           uint32_t wo, uint32_t *__restrict__ out, uint32_t *scratch, uint64_t Bp) {
+    const uint32_t lane = blockIdx.x * 64 + threadIdx.x;
+    if (lane >= n_items) return;
+    const uint32_t *src = in + (uint64_t)lane * wi;
+    uint32_t *dst = out + (uint64_t)lane * wo;
+    auto ld29 = [&](uint32_t i) { Fr29 c; for (int k = 0; k < 9; k++) c.v[k] = src[9 * i + k]; return c; };
+    auto st29 = [&](uint32_t i, const Fr29 &c) { for (int k = 0; k < 9; k++) dst[9 * i + k] = c.v[k]; };
+    auto ld = [&](uint32_t i) { Fr c; for (int k = 0; k < 8; k++) c.v[k] = src[8 * i + k]; return c; };
+    auto st = [&](uint32_t i, const Fr &c) { for (int k = 0; k < 8; k++) dst[8 * i + k] = c.v[k]; };
+    auto st_point = [&](const GJac &p) {  // canonical affine coordinates and the flag
+        bool inf;
+        const GAff a = gj_to_aff(p, &inf);
+        st(0, fr_to_canonical(a.x));
+        st(1, fr_to_canonical(a.y));
+        dst[16] = inf ? 1u : 0u;
+    };
+    if (what == 0) {
+        const GJac r = gj_dbl(GJac{ld29(0), ld29(1), ld29(2)});
+        st29(0, r.X); st29(1, r.Y); st29(2, r.Z);
+    } else if (what == 1) {
+        Fr29 zr = g29_zero();
+        const GJac r = gj_add_aff29(GJac{ld29(0), ld29(1), ld29(2)}, ld29(3), ld29(4), &zr);
+        st29(0, r.X); st29(1, r.Y); st29(2, r.Z); st29(3, zr);
+    } else if (what == 2) {
+        const GJac r = gj_add(GJac{ld29(0), ld29(1), ld29(2)}, GJac{ld29(3), ld29(4), ld29(5)});
+        st29(0, r.X); st29(1, r.Y); st29(2, r.Z);
+    } else if (what == 3) {
+        bool inf;
+        const GAff a = gj_to_aff(GJac{ld29(0), ld29(1), ld29(2)}, &inf);
+        st(0, a.x); st(1, a.y);
+        dst[16] = inf ? 1u : 0u;
+    } else if (what == 4) {
+        const GlvSplit sp = glv_split(ld(0));
+        for (int k = 0; k < 4; k++) { dst[k] = sp.k1[k]; dst[4 + k] = sp.k2[k]; }
+        dst[8] = sp.neg1 ? 1u : 0u;
+        dst[9] = sp.neg2 ? 1u : 0u;
+        const SignedDigits d1 = signed_windows5(sp.k1), d2 = signed_windows5(sp.k2);
+        for (uint32_t i = 0; i < 26; i++) { dst[10 + i] = signed_digit(d1, i); dst[36 + i] = signed_digit(d2, i); }
+    } else if (what == 5) {
+        st_point(ladder_term(T, ld(0), param));
+    } else if (what == 6 || what == 7) {
+        st_point(grumpkin_schnorr_point(T, fr_from_canonical(ld(0)), fr_from_canonical(ld(1)), reduce_mod_q(ld(2)), reduce_mod_q(ld(3)), what == 6 ? scratch : nullptr, Bp, lane));
+    }
+}
+void launch_grumpkin_items(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_items, uint32_t *out, uint32_t *scratch,
+                           uint64_t Bp) {
+    if (n_items) hipLaunchKernelGGL(grumpkin_items_kernel, dim3((n_items + 63) / 64), dim3(64), 0, s, T, what, param, in, n_items, grumpkin_items_words(what, false),
+                                    grumpkin_items_words(what, true), out, scratch, Bp);
+}
 // read-back of a lookup table (acvm_debug_table_read): one lane per requested entry, the raw 16 words as they lie in the table -- no arithmetic, no change of
 // form. The host has checked every index against the table's size.
 __global__ void __launch_bounds__(64) table_gather_kernel(const uint4 *__restrict__ table, const uint64_t *__restrict__ entries, uint32_t n, uint4 *__restrict__ out) {

@@ -345,8 +345,13 @@ __device__ __forceinline__ void bn_mul(const uint32_t (&a)[N], const uint32_t (&
 //   c1 = floor(k g1 / 2^384), g1 = floor(2^384 A / q);   c2 = floor(k g2 / 2^384), g2 = floor(2^384 B / q)
 //   k1 = k - c1 A - c2 B',   k2 = c1 B - c2 A            =>  k1 + k2 lambda = k (mod q) for ANY integers c1, c2,
 // and with these c1, c2 (each within 1 of the exact quotient) |k1|, |k2| < |A| + |B'| < 2^127. Returns the magnitudes
-// (4 limbs each) and the signs. Checked against a big-integer model over random and edge scalars (tests/test_gpu_grumpkin.py
-// drives it through SchnorrVerify against the oracle's plain double-and-add).
+// (4 limbs each) and the signs. SIGN CLASSES: c1 and c2 are floors (g1 and g2 are floors too, which only lowers them), so with
+// d1 = k A / q - c1 >= 0 and d2 = k B / q - c2 >= 0 the halves are k1 = d1 A + d2 B' and k2 = d2 A - d1 B exactly (A A + B B' = q):
+// k1 is NEVER negative, so neg1 is false for every k and its branch below is unreachable (it stays: the routine is then right for any
+// c1, c2); k2 is negative unless d1 < d2 A / B < 2^-63, i.e. for every scalar but crafted ones (k a hair above a multiple of q / A gives
+// k2 > 0; k < 2^127 gives k2 = 0). Checked on the device, magnitudes, signs and all 2 x 26 digits, against the restatement of these
+// definitions in Python integers (tests/grumpkin_ref.py glv_split, signed_windows5) over scalars of all three classes
+// (tests/test_gpu_grumpkin_edges.py through acvm_debug_grumpkin_items; tests/test_grumpkin_cases.py asserts the classes).
 struct GlvSplit {
     uint32_t k1[4], k2[4];
     bool neg1, neg2;
@@ -398,6 +403,7 @@ static_assert(GRUMPKIN_VARBASE_SCRATCH_WORDS == VARBASE_TABLE_ENTRIES * 27u + VA
 // Signed 5-bit windows of a magnitude below 2^127: k = sum d_i 32^i with d_i in [-15, 16], i < 26 (a window above 16 borrows 32 from the
 // next one). Digit i sits in word i / 5 at bit 6 (i % 5): bits 0..4 the magnitude, bit 5 the sign. 26 windows instead of the 32 unsigned
 // 4-bit ones: 52 additions + 130 doublings instead of 64 + 128 for one more table entry.
+// (A window of 31 plus a carry is 32: magnitude 0 WITH the sign bit, a borrowed zero. The ladder tests the magnitude, so it is skipped like any zero.)
 struct SignedDigits { uint32_t w[6]; };
 __device__ __forceinline__ SignedDigits signed_windows5(const uint32_t (&k)[4]) {
     SignedDigits r;
@@ -527,6 +533,15 @@ __device__ __forceinline__ GJac grumpkin_var_base_mul(const GAff &P, const Fr &e
     return a;
 }
 
+// R = e pk + s G for s and e already reduced (mod q); the final addition doubles when s = e sk and returns infinity when s = -e sk (pk = sk G).
+// window_table, Bp, j: as grumpkin_var_base_mul takes them (nullptr: double-and-add)
+__device__ __forceinline__ GJac grumpkin_schnorr_point(const GrumpkinTables &T, const Fr &pkx, const Fr &pky, const Fr &s, const Fr &e, uint32_t *window_table, uint64_t Bp,
+                                                       uint64_t j) {
+    const GJac a = grumpkin_var_base_mul(GAff{pkx, pky}, e, window_table, Bp, j);
+    const GJac b = fixed_base_mul(T, 0, s);
+    return gj_add(a, b);
+}
+
 // s, e: the two halves of the signature as 256-bit integers (big-endian bytes 0..31 and 32..63); the message bytes are staged in `m` behind the
 // 32 bytes of the compressed point by `fill_msg(put)`, put(i, byte) storing message byte i
 template <class FillMsg>
@@ -539,9 +554,7 @@ __device__ __forceinline__ bool grumpkin_schnorr_verify_values(const GrumpkinTab
     Fr seventeen = fr_from_u32(17u);
     if (!fr_eq(fr_sqr(pky), fr_sub(fr_mul(fr_sqr(pkx), pkx), seventeen))) return false;
     if (fr_is_zero(s) || fr_is_zero(e)) return false;
-    const GJac a = grumpkin_var_base_mul(GAff{pkx, pky}, e, window_table, m.Bp, m.j);
-    const GJac b = fixed_base_mul(T, 0, s);
-    const GJac rr = gj_add(a, b);
+    const GJac rr = grumpkin_schnorr_point(T, pkx, pky, s, e, window_table, m.Bp, m.j);
     if (gj_is_inf(rr)) return false;
     bool inf;
     const GAff R = gj_to_aff(rr, &inf);

@@ -181,6 +181,46 @@ int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, u
     return 0;
 } ABI_CATCH
 
+// One routine of ops_grumpkin.hpp per call, one device lane per item, raw u32 words in and out (kernels_grumpkin.hip grumpkin_items_kernel). The probe holds
+// the device's tables like acvm_debug_grumpkin, and owns the per-lane window tables of what = 6.
+int acvm_debug_grumpkin_items(uint32_t what, uint32_t param, const uint32_t *in_words, uint32_t n_items, uint32_t *out_words) try {
+    const uint32_t wi = grumpkin_items_words(what, false), wo = grumpkin_items_words(what, true);
+    if (!wi || !wo) return set_err(ACVM_E_INVALID, "no such routine");
+    if (what == 5u && param > 2u) return set_err(ACVM_E_INVALID, "ladder_term: param is the position 0..2");
+    if (!n_items) return 0;
+    if (!in_words || !out_words) return set_err(ACVM_E_INVALID, "null argument");
+    if (n_items > (1u << 20)) return set_err(ACVM_E_INVALID, "at most 2^20 items a call");
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    struct Hold {
+        int d;
+        explicit Hold(int dev_) : d(dev_) { device_tables_retain(d); }
+        ~Hold() { device_tables_unref(d); }
+    } hold(dev);
+    GrumpkinTables tabs;
+    if (!grumpkin_tables(&tabs)) return set_err(ACVM_E_DEVICE, "could not build the Grumpkin tables on the device");
+    struct Mem {
+        uint32_t *in = nullptr, *out = nullptr, *scratch = nullptr;
+        ~Mem() {
+            for (void *p : {(void *)in, (void *)out, (void *)scratch})
+                if (p) hipFree(p);
+        }
+    } m;
+    const uint64_t Bp = ((uint64_t)n_items + 63) / 64 * 64;
+    int rc = 0;
+    auto step = [&](hipError_t e, const char *what_) { if (!rc && e != hipSuccess) rc = set_err(ACVM_E_DEVICE, std::string(what_) + ": " + hipGetErrorString(e)); };
+    step(hipMalloc((void **)&m.in, (size_t)n_items * wi * 4), "hipMalloc");
+    step(hipMalloc((void **)&m.out, (size_t)n_items * wo * 4), "hipMalloc");
+    if (what == 6u) step(hipMalloc((void **)&m.scratch, (size_t)Bp * GRUMPKIN_VARBASE_SCRATCH_WORDS * 4), "hipMalloc");
+    if (!rc) step(hipMemcpy(m.in, in_words, (size_t)n_items * wi * 4, hipMemcpyHostToDevice), "hipMemcpy");
+    if (!rc) step(hipMemset(m.out, 0, (size_t)n_items * wo * 4), "hipMemset");
+    if (!rc) launch_grumpkin_items(nullptr, tabs, what, param, m.in, n_items, m.out, m.scratch, Bp);
+    step(hipGetLastError(), "grumpkin_items_kernel");
+    step(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    if (!rc) step(hipMemcpy(out_words, m.out, (size_t)n_items * wo * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+    return rc;
+} ABI_CATCH
+
 // Read-back of the lookup tables (grumpkin_host.hpp: TABLE_*), entry by entry and in the form they are stored in. The table is built by the function the
 // product builds it with; the probe holds the device's set like acvm_debug_grumpkin.
 int acvm_debug_table_info(uint32_t table, uint64_t *n_entries, int *built) try {

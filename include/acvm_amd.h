@@ -212,6 +212,16 @@ int acvm_selftest(uint32_t n, uint64_t seed);
  * 8 / 9 = in[0] * (in[1], in[2]) for a 256-bit integer and an affine point: 8 through SchnorrVerify's GLV + window-table path, 9 by double-and-add.
  * in: n_in x 32 bytes big-endian; out: 64 bytes (x || y) big-endian. */
 int acvm_debug_grumpkin(uint32_t what, uint32_t param, const uint8_t *in_be32, uint32_t n_in, uint8_t *out_be64);
+/* One routine of the Grumpkin device header per call, ONE DEVICE LANE PER ITEM, raw u32 words in and out (tests/test_gpu_grumpkin_edges.py compares with
+ * Python integers). Field elements of what 0..3 are the nine 29-bit limbs of the lazy working form (the Montgomery residue v 2^261 mod p or that plus p:
+ * the caller picks the representative, values below 2p) and leave as the limbs the routine returned; integers are 8 x u32, little-endian, canonical.
+ * what (words in -> out per item): 0 X Y Z -> gj_dbl (27 -> 27); 1 X Y Z x2 y2 -> gj_add_aff29, then zr = Z3 / Z1, zero limbs off the ordinary path
+ * (45 -> 36); 2 two Jacobian points -> gj_add (54 -> 27); 3 X Y Z -> gj_to_aff: x, y in the storage form, the infinity flag (27 -> 17); 4 k < q ->
+ * glv_split: |k1|, |k2| (4 words each), neg1, neg2, then the 26 + 26 digits of signed_windows5, magnitude | 32 if negative (8 -> 62); 5 v < p ->
+ * ladder_term(v, param), param = 0..2: canonical x, y, the infinity flag (8 -> 17); 6 / 7 pkx pky s e -> R = e pk + s G as SchnorrVerify forms it
+ * (s, e reduced mod q first): canonical x, y, the infinity flag, 6 with a per-lane window table the probe allocates, 7 without one, the Brillig
+ * VM's path (32 -> 17). ACVM_E_INVALID for another `what`, a ladder position above 2 or more than 2^20 items; nothing is launched for n_items = 0. */
+int acvm_debug_grumpkin_items(uint32_t what, uint32_t param, const uint32_t *in_words, uint32_t n_items, uint32_t *out_words);
 /* Read-back of the lookup tables of the Grumpkin and ECDSA kernels, entry by entry (tests/test_gpu_curve_tables.py compares every word with integers).
  * table: 0 ped [30][512], 1 win [4][32][255], 2 small [3][15], 3 skew [3], 4 ped2 [30][512][512], 5 win16 [4][16][65535], 6 pedw [2][11][2^24],
  * 7 / 8 the generator table [16][65536] of secp256k1 / secp256r1 (definitions and storage forms: acvm_amd/csrc/grumpkin_host.hpp). An entry is one affine

@@ -31,6 +31,20 @@ def test_abi_version_and_error_string():
     assert acvm_amd.Circuit  # python mirror present
 
 
+def test_grumpkin_items_probe_checks_its_arguments_before_it_touches_the_device():
+    """acvm_debug_grumpkin_items refuses an unknown routine and a ladder position above 2, and does nothing for zero items: all on the host"""
+    import numpy as np
+    import pytest
+    import acvm_amd
+    assert len(acvm_amd.GRUMPKIN_ITEM_WORDS) == 8
+    with pytest.raises(acvm_amd.AcvmError, match="no such routine"):
+        acvm_amd.debug_grumpkin_items(8, np.zeros((1, 8), dtype=np.uint32))
+    with pytest.raises(acvm_amd.AcvmError, match="position"):
+        acvm_amd.debug_grumpkin_items(5, np.zeros((1, 8), dtype=np.uint32), param=3)
+    for what, (wi, wo) in enumerate(acvm_amd.GRUMPKIN_ITEM_WORDS):
+        assert acvm_amd.debug_grumpkin_items(what, np.zeros((0, wi), dtype=np.uint32)).shape == (0, wo)
+
+
 def test_no_device_fails_loudly():
     """Without a gfx950 device batch creation must raise; there is no CPU fallback."""
     import acvm_amd
