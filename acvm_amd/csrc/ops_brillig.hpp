@@ -65,6 +65,17 @@ struct BrVm {
         if ((uint32_t)ptr + 1u > n_mem) n_mem = (uint32_t)ptr + 1u;
         return true;
     }
+    // memory.rs:32-39 with NO values: resize(max(len, ptr + 0)) grows the memory to ptr cells all the same
+    __device__ __forceinline__ bool mem_grow(uint64_t ptr) {
+        if (ptr <= n_mem) return true;
+        if (ptr > mem_cap) {
+            if (!status) { status = 5; code = DM_BRILLIG_MEM_CAP; x0 = ptr - 1u > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(ptr - 1u); }
+            return false;
+        }
+        for (uint32_t c = n_mem; c < (uint32_t)ptr; c++) fr_store(slots, n_regs + c, Bp, j, fr_zero());
+        n_mem = (uint32_t)ptr;
+        return true;
+    }
 };
 
 // evaluate_binary_bigint_op through the VM: a panic of the reference stops the lane (ops_light.hpp int_op_core)
@@ -189,9 +200,10 @@ static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const 
         found = st.desc && k < st.desc[vm.ij];
     }
     if (!found) {
-        vm.status = 3;
-        if (!L) return;
-        // ForeignCallWaitInfo inputs: registers as one value, heap arrays / vectors as their memory slice
+        if (!L) { vm.status = 3; return; }  // (the level kernels only hand the instance to the exact path)
+        // ForeignCallWaitInfo inputs: registers as one value, heap arrays / vectors as their memory slice. The VM waits only once every input
+        // is resolved (lib.rs:198-202): a slice past the memory's end or a pointer above u64 panics instead, so status 3 is set LAST
+        // (BrVm::panic records nothing once a status stands).
         uint32_t nv = 0;
         if (1u + n_in > L->fc.pend_desc_words) { vm.status = 5; vm.code = DM_FC_PENDING_CAP; return; }
         L->fc.pend_desc[t] = n_in;
@@ -216,6 +228,7 @@ static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const 
                 fr_store(L->fc.pend_vals, nv++, n_slow, t, v);
             }
         }
+        vm.status = 3;
         return;
     }
     // walk to result k
@@ -249,6 +262,7 @@ static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const 
             uint64_t dst = 0;
             const Fr pv = vm.reg_get(rg);
             if (vm.status == 4 || !vm.to_usize(pv, dst)) return;
+            if (n == 0u && !vm.mem_grow(dst)) return;
             for (uint32_t c = 0; c < n; c++)
                 if (!vm.mem_write(dst + c, value(vpos + c))) return;
         }
@@ -411,10 +425,10 @@ __device__ __forceinline__ OpResult op_brillig(const P &p, const uint32_t *__res
                 continue;
             }
             const Fr cb = fr_to_canonical(rv);
-            if (cb.v[2] | cb.v[3] | cb.v[4] | cb.v[5] | cb.v[6] | cb.v[7]) return op_fail_msg(DE_PANIC, 0, DM_BRILLIG_PANIC, BP_U64);
             const uint64_t base = (uint64_t)cb.v[1] << 32 | cb.v[0];
-            for (uint32_t k = 0; k < n; k++, q += 2) {
-                if (base + k >= vm.n_mem) return op_fail_msg(DE_PANIC, 0, DM_BRILLIG_PANIC, BP_OUT_MEM_OOB);
+            for (uint32_t k = 0; k < n; k++, q += 2) {  // (brillig.rs:104-105: to_usize stands inside the loop; an empty array never converts its register)
+                if (cb.v[2] | cb.v[3] | cb.v[4] | cb.v[5] | cb.v[6] | cb.v[7]) return op_fail_msg(DE_PANIC, 0, DM_BRILLIG_PANIC, BP_U64);
+                if (base >= vm.n_mem || k >= vm.n_mem - base) return op_fail_msg(DE_PANIC, 0, DM_BRILLIG_PANIC, BP_OUT_MEM_OOB);
                 if (!p.insert(q[0], vm.mem_get((uint32_t)(base + k)), q[1])) return op_fail(DE_UNSATISFIED);
             }
         }

@@ -598,10 +598,10 @@ int brillig_solve(oracle_acvm_t *a, const brillig_t *b, size_t acir_index) {
                 fr_t rv = reg_get(&vm, i);
                 if (!b->outputs[i].is_array) rc = pwg_insert_value(a, b->outputs[i].w, &rv);
                 else {
-                    uint64_t base;
-                    if (!fr_try_to_u64(&rv, &base)) { pwg_fail(a, E_PANIC, 0, 0, "register does not fit into u64"); rc = 1; break; }
-                    for (size_t j = 0; j < b->outputs[i].n; j++) {
-                        if (base + j >= vm.n_mem) { pwg_fail(a, E_PANIC, 0, 0, "index out of bounds: brillig memory"); rc = 1; break; }
+                    uint64_t base = 0;
+                    for (size_t j = 0; j < b->outputs[i].n; j++) { /* :104-105: to_usize stands inside the loop; an empty array never converts */
+                        if (!fr_try_to_u64(&rv, &base)) { pwg_fail(a, E_PANIC, 0, 0, "register does not fit into u64"); rc = 1; break; }
+                        if (base >= vm.n_mem || j >= vm.n_mem - base) { pwg_fail(a, E_PANIC, 0, 0, "index out of bounds: brillig memory"); rc = 1; break; }
                         if (pwg_insert_value(a, b->outputs[i].arr[j], &vm.mem[base + j])) { rc = 1; break; }
                     }
                 }

@@ -16,8 +16,7 @@ The rules restated by model() below:
   Directive::ToLeRadix    acvm/src/pwg/directives/mod.rs:60-87, num-bigint BigUint::to_radix_le (0 -> [0], radix outside 2..=256 panics)
   RANGE                   acvm/src/pwg/blackbox/range.rs:7-18, acir_field/src/generic_ark.rs:214-221 (num_bits)
   AND / XOR               acvm/src/pwg/blackbox/logic.rs:11-56, acir_field/src/generic_ark.rs:322-355,446-473
-  Brillig BinaryIntOp     brillig_vm/src/arithmetic.rs:23-98 (ref_int_op), acvm/src/pwg/brillig.rs:46-111 (input i in register i, register i
-                          into output i)"""
+  Brillig BinaryIntOp     brillig_vm/src/arithmetic.rs:23-98 (ref_int_op); the VM around it is tests/brillig_ref.py"""
 import collections
 import functools
 import random
@@ -154,13 +153,11 @@ def _step(op, wm):
         assert l.num_bits == r.num_bits
         x, y = mask_bits(wm[l.witness], l.num_bits), mask_bits(wm[r.witness], r.num_bits)
         return None if _insert(wm, op.args["output"], (x ^ y if op.name == "XOR" else x & y) % P) else unsat
-    if isinstance(op, Brillig):  # one BinaryIntOp of registers 0 and 1 into register 0 (whatever follows it leaves register 0 alone)
-        kind, dst, name, bits, ra, rb = op.bytecode[0]
-        assert (kind, dst, ra, rb) == ("BinaryIntOp", 0, 0, 1) and op.predicate is None and len(op.outputs) == 1
-        v = ref_int_op(name, _value(op.inputs[0], wm), _value(op.inputs[1], wm), bits)
-        if v is None:
-            return (E_PANIC, None)
-        return None if _insert(wm, op.outputs[0], v) else unsat
+    if isinstance(op, Brillig):  # the whole VM: tests/brillig_ref.py (imported here: that module takes ref_int_op from this one)
+        import brillig_ref
+        out = brillig_ref.run(op, wm)
+        assert out.kind in (brillig_ref.SOLVED, brillig_ref.PANIC, brillig_ref.UNSATISFIED), out
+        return None if out.kind == brillig_ref.SOLVED else (E_PANIC, None) if out.kind == brillig_ref.PANIC else unsat
     raise AssertionError(f"no model for {op!r}")
 
 
