@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
     "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
     "acvm_batch_export_device_records", "acvm_batch_witness_records",
+    "acvm_batch_wire_bound", "acvm_batch_witness_maps_wire_device", "acvm_batch_witness_maps_wire",
     "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
     "acvm_debug_lin_add", "acvm_debug_lin_plan",
 ]
@@ -135,6 +136,26 @@ def record_out_desc(pitch, fields, first, n):
         fl.append(f)
     arr = (RecordOutField * max(len(fl), 1))(*fl)
     return RecordOutDesc(pitch=pitch, fields=arr, n_fields=len(fl), first=first, n=n), arr
+
+
+WIRE_BINCODE, WIRE_GZIP_STORED = 0, 1  # ACVM_WIRE_*
+
+
+class WireDesc(C.Structure):
+    """acvm_wire_desc_t"""
+    _fields_ = [("container", C.c_uint32), ("first", C.c_uint32), ("n", C.c_uint32), ("witnesses", C.POINTER(C.c_uint32)), ("n_witnesses", C.c_uint32),
+                ("pitch", C.c_uint64)]
+
+
+def wire_desc(container, first, n, witnesses=None, pitch=0):
+    """(WireDesc, the array its witness pointer refers to); witnesses None: the whole map"""
+    desc = WireDesc(container=container, first=first, n=n, pitch=pitch)
+    arr = None
+    if witnesses is not None:
+        ws = list(witnesses)
+        arr = (C.c_uint32 * max(len(ws), 1))(*ws)
+        desc.witnesses, desc.n_witnesses = arr, len(ws)
+    return desc, arr
 
 
 class RecordMaskedField(C.Structure):
@@ -600,6 +621,11 @@ def lib():
     if hasattr(L, "acvm_batch_export_device_records"):
         L.acvm_batch_export_device_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p, C.c_void_p]
         L.acvm_batch_witness_records.argtypes = [C.c_void_p, C.POINTER(RecordOutDesc), C.c_void_p]
+    if hasattr(L, "acvm_batch_wire_bound"):
+        L.acvm_batch_wire_bound.restype = C.c_longlong
+        L.acvm_batch_wire_bound.argtypes = [C.c_void_p, C.POINTER(WireDesc)]
+        L.acvm_batch_witness_maps_wire_device.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.acvm_batch_witness_maps_wire.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1531,6 +1557,37 @@ class Batch:
         out = np.zeros((n, pitch), dtype=np.uint8)
         _check(lib().acvm_batch_witness_records(self._h, C.byref(desc), out.ctypes.data if out.size else None))
         return out
+
+    def wire_bound(self, container=WIRE_GZIP_STORED, witnesses=None) -> int:
+        """The bytes of the longest map witness_maps_wire_device can write for this container and witness list (None: the whole map), rounded up
+        to 16 (acvm_batch_wire_bound): the smallest pitch it accepts."""
+        desc, _keep = wire_desc(container, 0, 0, witnesses)
+        return _check(lib().acvm_batch_wire_bound(self._h, C.byref(desc)))
+
+    def witness_maps_wire_device(self, d_ptr: int, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None, pitch=0, d_instances=None, d_lengths=None):
+        """The WitnessMap of every output row in the reference's wire format, written on the device (acvm_batch_witness_maps_wire_device): row i's
+        map goes to d_ptr + i * pitch (d_ptr 16-byte aligned; pitch a multiple of 16, 0 = wire_bound) -- WIRE_BINCODE: the bincode body,
+        WIRE_GZIP_STORED: one gzip member of stored blocks around it, what decompress_witness and every inflater read. One entry per witness the
+        instance assigned, of the whole map or of `witnesses` (strictly ascending). d_lengths: device pointer of uint64 [n] that receives each
+        row's length, or None; nothing at or behind a row's length is written. Row i is instance first + i, or instance d_instances[i] of a
+        device array of n absolute instance numbers as export_device_list reads it. Nothing is copied to the host."""
+        if n is None:
+            if d_instances is not None:
+                raise ValueError("a list export needs n, the list's length")
+            n = self.B - first
+        desc, _keep = wire_desc(container, first, n, witnesses, pitch)
+        _check(lib().acvm_batch_witness_maps_wire_device(self._h, C.byref(desc), d_instances, d_ptr, d_lengths))
+
+    def witness_maps_wire(self, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None):
+        """witness_maps_wire_device into host memory (acvm_batch_witness_maps_wire): a list of n bytes objects, one serialised map per instance."""
+        import numpy as np
+        n = self.B - first if n is None else n
+        pitch = self.wire_bound(container, witnesses)
+        desc, _keep = wire_desc(container, first, n, witnesses, pitch)
+        out = np.zeros(max(n * pitch, 1), dtype=np.uint8)
+        lengths = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(lib().acvm_batch_witness_maps_wire(self._h, C.byref(desc), out.ctypes.data, lengths.ctypes.data))
+        return [out[i * pitch:i * pitch + int(lengths[i])].tobytes() for i in range(n)]
 
     def outcomes_device(self, first=0, n=None, d_status=None, d_err=None, d_opcode_index=None, select_mask=0, d_selected=None, count=True):
         """The outcomes of instances [first, first + n) as device columns (acvm_batch_outcomes_device): d_status / d_err uint8 [n], d_opcode_index uint32 [n],

@@ -15,6 +15,7 @@
 #include "batch_internal.hpp"
 #include "export_encode.hpp"
 #include "record_out_plan.hpp"
+#include "wire_plan.hpp"
 
 static const uint8_t DIGEST_G[32] = {0x23, 0x35, 0x53, 0x18, 0xdb, 0xff, 0xab, 0x2f, 0xb7, 0x72, 0x11, 0x7c, 0x57, 0x5c, 0x61, 0xb1,
                                      0x79, 0xf8, 0xc9, 0x83, 0x3c, 0x83, 0xba, 0x65, 0x59, 0x7e, 0x17, 0x3c, 0x35, 0xc4, 0xbb, 0xe3};
@@ -518,6 +519,91 @@ int acvm_batch_export_device_records(acvm_batch_t *b, const acvm_record_out_desc
 } ABI_CATCH
 int acvm_batch_witness_records(acvm_batch_t *b, const acvm_record_out_desc_t *d, void *records) try {
     return export_records(b, d, nullptr, records, true);
+} ABI_CATCH
+
+// ---- the map in the reference's wire format for many instances (include/acvm_amd.h acvm_batch_witness_maps_wire_device): wire_plan.cpp checks
+// the descriptor and makes the generic instance's rank table and the CRC power table, which go up with the witness list into the staging arena
+// (nothing per instance); a pre-pass makes the exact lanes' ranks from their assigned bitmap; kernels_wire.hip writes the slots. Range and list
+// are the same kernels, and both find the exact lanes through the lane map. Host form: the slots are made in the staging arena in chunks of
+// instances, one copy down per chunk, and row i's bytes [0, lengths[i]) reach the caller's buffer.
+static constexpr size_t WIRE_HOST_CHUNK_BYTES = (size_t)64 << 20;
+static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *bytes, uint64_t *lengths, bool host) {
+    WirePlan plan;
+    std::string refusal;
+    if (int rc = wire_plan(b ? &b->B : nullptr, b ? b->plan().producer.data() : nullptr, b ? b->plan().n_witnesses : 0u, d, d_instances != nullptr, bytes, !host, &plan, &refusal))
+        return set_err(rc, refusal);
+    if (host && plan.n && !lengths) return set_err(ACVM_E_INVALID, "null lengths");
+    if (int rc = finish_pending_and_require_solved(b)) return rc;
+    if (plan.whole) {
+        if (b->side()) return set_err(ACVM_E_STATE, "the batch recycles witness rows (ACVM_BATCH_REUSE_SLOTS) or solved its exact lanes in the side table: full maps are not kept; read the kept witnesses and the digest");
+        if (int rc = refuse_if_next_imported(b, nullptr, 0, true)) return rc;
+    } else {
+        if (int rc = refuse_if_next_imported(b, plan.witnesses.data(), plan.n_positions, false)) return rc;
+        if (int rc = reuse_check_kept(b, plan.witnesses.data(), plan.n_positions)) return rc;
+    }
+    if (!plan.n) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    const bool gzip = plan.container == ACVM_WIRE_GZIP_STORED;
+    const uint32_t n_slow = (uint32_t)b->slow_ids.size(), n_words = (uint32_t)plan.list_mask.size();
+    const bool map_stale = !(b->d_lane_map && b->lane_map_epoch == b->slow_epoch);
+    // the rows of one pass: all of them into the caller's device buffer, or what fits the chunk of the staging arena (whole blocks of 64 rows)
+    uint32_t chunk = plan.n;
+    if (host) chunk = (uint32_t)std::min<uint64_t>(plan.n, std::max<uint64_t>(64, WIRE_HOST_CHUNK_BYTES / plan.pitch / 64 * 64));
+    // the arena: [witness list][rank][list mask][crc powers][slow ids][lane prefix][crc words][host: lengths, slots]
+    size_t at = 0;
+    auto carve = [&](size_t n_bytes) { const size_t begin = at; at += align256(n_bytes); return begin; };
+    const size_t at_sel = carve(plan.whole ? 0 : (size_t)plan.n_positions * 4), at_rank = carve(plan.rank.size() * 4), at_mask = carve((size_t)n_words * 4);
+    const size_t at_pow = carve(plan.crc_pow.size() * 4), at_ids = carve(map_stale ? (size_t)n_slow * 4 : 0), at_prefix = carve(((size_t)n_words + 1) * n_slow * 4);
+    const size_t at_crc = carve(gzip ? (size_t)chunk * 4 : 0), at_lengths = carve(host ? (size_t)chunk * 8 : 0), at_slots = carve(host ? (size_t)chunk * plan.pitch : 0);
+    if (int rc = stage_reserve(b, at)) return rc;
+    hipStream_t s = b->stream;
+    auto put = [&](size_t where, const std::vector<uint32_t> &v) -> hipError_t {
+        if (v.empty()) return hipSuccess;
+        b->n_export_h2d_bytes += (uint64_t)v.size() * 4;
+        return hipMemcpyAsync(b->d_stage + where, v.data(), v.size() * 4, hipMemcpyHostToDevice, s);
+    };
+    HIPCHK(put(at_sel, plan.witnesses));
+    HIPCHK(put(at_rank, plan.rank));
+    HIPCHK(put(at_mask, plan.list_mask));
+    HIPCHK(put(at_pow, plan.crc_pow));
+    if (int rc = lane_map_ready(b, s, (uint32_t *)(b->d_stage + at_ids))) return rc;
+    uint32_t *d_prefix = n_slow ? (uint32_t *)(b->d_stage + at_prefix) : nullptr;
+    launch_wire_lane_prefix(s, b->d_assigned, n_slow, n_words, (const uint32_t *)(b->d_stage + at_mask), d_prefix);
+    std::vector<uint8_t> slots;
+    if (host) slots.resize((size_t)chunk * plan.pitch);
+    for (uint32_t done = 0; done < plan.n; done += chunk) {
+        const uint32_t m = std::min(chunk, plan.n - done);
+        uint32_t *d_crc = gzip ? (uint32_t *)(b->d_stage + at_crc) : nullptr;
+        if (gzip) launch_fill_u32(s, d_crc, 0u, m);
+        const WireExport x{b->d_W, b->Bp, plan.first + done, m,
+                           ExportListSource{d_instances, b->B, b->d_lane_map, b->side() ? b->d_Wx : b->d_W, b->side() ? b->x_cap : b->Bp, b->side(), b->d_assigned, n_slow},
+                           b->plan().n_witnesses, b->d_slot_of, b->d_producer, b->unscale.index, b->unscale.consts_plain,
+                           plan.whole ? nullptr : (const uint32_t *)(b->d_stage + at_sel), plan.n_positions,
+                           (const uint32_t *)(b->d_stage + at_rank), (const uint32_t *)(b->d_stage + at_mask), d_prefix, (const uint32_t *)(b->d_stage + at_pow), plan.crc_x64, d_crc,
+                           plan.container, host ? b->d_stage + at_slots : (uint8_t *)bytes, plan.pitch, host ? (uint64_t *)(b->d_stage + at_lengths) : lengths};
+        launch_wire_export(s, x, plan.n_windows);
+        HIPCHK(hipGetLastError());
+        if (host) {
+            HIPCHK(hipMemcpyAsync(lengths + done, x.lengths, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(slots.data(), x.out, (size_t)m * plan.pitch, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (uint32_t i = 0; i < m; i++) memcpy((uint8_t *)bytes + (size_t)(done + i) * plan.pitch, &slots[(size_t)i * plan.pitch], (size_t)lengths[done + i]);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps the plan's tables and slow_ids alive for their copies)
+    return 0;
+}
+long long acvm_batch_wire_bound(const acvm_batch_t *b, const acvm_wire_desc_t *d) try {
+    if (!d) return set_err(ACVM_E_INVALID, "null argument");
+    if (!b) return set_err(ACVM_E_INVALID, "null batch");
+    if (d->container != ACVM_WIRE_BINCODE && d->container != ACVM_WIRE_GZIP_STORED) return set_err(ACVM_E_INVALID, "unknown container " + std::to_string(d->container));
+    return (long long)wire_plan_bound(d->container, d->witnesses ? d->n_witnesses : b->plan().n_witnesses);
+} ABI_CATCH
+int acvm_batch_witness_maps_wire_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *d_bytes, uint64_t *d_lengths) try {
+    return export_wire(b, d, d_instances, d_bytes, d_lengths, false);
+} ABI_CATCH
+int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out, uint64_t *lengths) try {
+    return export_wire(b, d, nullptr, out, lengths, true);
 } ABI_CATCH
 
 uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b) { return b ? b->n_export_h2d_bytes : 0; }

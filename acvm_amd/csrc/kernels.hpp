@@ -184,6 +184,32 @@ struct RecordExport {
     const uint32_t *windows, *fields;
 };
 void launch_export_records(hipStream_t s, const RecordExport &x, uint32_t n_windows);
+// ---- kernels_wire.hip (acvm_batch_witness_maps_wire_device): output row i writes the serialised WitnessMap of its instance into the slot at
+// out + i * pitch (16-aligned, pitch a multiple of 16); row i is instance src.list[i], or first + i where src.list is null. sel: the device
+// copy of the witness list (n_positions entries) or null = position k is witness k; rank / list_mask / crc_pow / crc_x64: wire_plan.hpp's
+// tables; lane_prefix: [(n_witnesses + 31) / 32 + 1][n_slow], made by launch_wire_lane_prefix (null while no instance left the generic path);
+// crc: n zeroed words (GZIP_STORED; else unused); lengths: n device words or null.
+struct WireExport {
+    const uint4 *W;
+    uint64_t Bp;
+    uint32_t first, n;
+    ExportListSource src;
+    uint32_t n_witnesses;
+    const uint32_t *row_of, *producer;
+    const uint32_t *u_index, *u_plain;
+    const uint32_t *sel;
+    uint32_t n_positions;
+    const uint32_t *rank, *list_mask, *lane_prefix, *crc_pow;
+    uint32_t crc_x64;
+    uint32_t *crc;
+    uint32_t container;
+    uint8_t *out;
+    uint64_t pitch;
+    uint64_t *lengths;
+};
+// per lane of the exact path and 32-witness word: its assigned list positions in the words below, and behind the last word their total
+void launch_wire_lane_prefix(hipStream_t s, const uint32_t *assigned_bits, uint32_t n_slow, uint32_t n_words, const uint32_t *list_mask, uint32_t *lane_prefix);
+void launch_wire_export(hipStream_t s, const WireExport &x, uint32_t n_windows);
 // ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
 // {status, err, opcode index, index in the range} over them; any column may be null
 void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);

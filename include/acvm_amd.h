@@ -947,6 +947,52 @@ int acvm_debug_import_state(acvm_batch_t *b, uint32_t *rows, uint32_t *planes, u
 long long acvm_witness_map_decode(const uint8_t *bytes, size_t len, uint32_t *ids, uint8_t *values_be32, uint32_t cap);
 long long acvm_witness_map_encode(const uint32_t *ids, const uint8_t *values_be32, uint32_t n, uint8_t *out, size_t cap);
 long long acvm_batch_witness_map_bytes(acvm_batch_t *b, uint32_t instance, uint8_t *out, size_t cap);
+/*
+ * The same format for MANY instances, written on the device: output row i receives the serialised WitnessMap of its instance in the slot at
+ * d_bytes + i * pitch, in one synchronous call without a round trip per instance.
+ *   - Which entries: one per witness the instance has ASSIGNED, of the whole map or of the listed witnesses, ascending -- the entries of
+ *     acvm_batch_witness_map_bytes. A failed or waiting instance gives the map as it stands; a listed witness beyond the circuit is unassigned.
+ *   - Body (ACVM_WIRE_BINCODE, what acvm_witness_map_decode also accepts): u64le N, then per entry u32le witness, u64le 64 and the 64 lowercase
+ *     hex characters of the canonical big-endian value. The entry of rank r lies at 8 + 76 r, the body is 8 + 76 N bytes.
+ *   - ACVM_WIRE_GZIP_STORED: one gzip member around the body -- what WitnessMap::try_from(&[u8]) and every inflater read -- that does not
+ *     compress, with every byte pinned: the header 1f 8b 08 08 00 00 00 00 00 ff 00 (FNAME, an empty name, MTIME 0, OS 255); the body in stored
+ *     blocks of 65 532 bytes (the last one shorter), each behind its 5-byte header BFINAL, LEN, ~LEN; three empty non-final stored blocks
+ *     (00 00 00 ff ff) in front of every block header but the first; CRC-32 of the body and ISIZE = its length mod 2^32. The body starts at
+ *     byte 16 of the slot, and a map of N entries takes 16 + L + 20 (ceil(L / 65532) - 1) + 8 bytes, L = 8 + 76 N.
+ *   - acvm_batch_wire_bound: the length of the longest map the descriptor can give -- every listed witness assigned, or every witness of the
+ *     circuit -- rounded up to 16; negative for a null batch, a null descriptor, an unknown container.
+ *   - d_lengths[i] (DEVICE, may be NULL): the bytes of row i's map.
+ *   - What is never written: a byte of a slot at or behind its row's length, a byte between slots, a byte in front of d_bytes. No byte of
+ *     d_bytes is loaded.
+ *   - d_instances (DEVICE) or NULL: with a list, rows are read as by acvm_batch_export_device_list -- any order, repeats allowed, an entry at
+ *     or beyond the live count is an instance that assigned nothing: a map of 0 entries -- and first must be 0, n the list's length.
+ *   - States and host traffic: those of acvm_batch_export_device / _list for the same witness set. It answers after stepping, under the
+ *     forced slow path and with instances waiting at a foreign call; under ACVM_BATCH_REUSE_SLOTS it serves kept and initial witnesses only.
+ *     ACVM_E_STATE: not solved; a witness that was not kept (the whole map under slot reuse); after acvm_batch_solve_then_import. Host to
+ *     device go the witness list, the plan's tables and the exact lanes' map when it changed, never anything per instance
+ *     (acvm_debug_export_h2d_bytes counts it).
+ *   - Refused with ACVM_E_INVALID, the message naming the cause, nothing enqueued: a null descriptor; an unknown container; a list that is
+ *     not strictly ascending; a pitch below the bound or not a multiple of 16; a misaligned d_bytes; a range beyond the live instances;
+ *     first != 0 with a list; a null buffer while n > 0.
+ *   - acvm_batch_witness_maps_wire: the same into host memory, range form. The slots are made in the handle's staging buffer in chunks of
+ *     instances and copied down once per chunk; row i's bytes [0, lengths[i]) of out + i * pitch are written, lengths must not be NULL, out
+ *     needs no alignment.
+ * Not here: a node form, an asynchronous variant, compression (a caller who wants small files deflates the BINCODE bodies on its own threads).
+ * A body of 4 GiB or more wraps ISIZE as gzip defines it.
+ */
+enum { ACVM_WIRE_BINCODE = 0,       /* the bincode body alone */
+       ACVM_WIRE_GZIP_STORED = 1 }; /* one gzip member around it, stored blocks */
+typedef struct {
+    uint32_t container;
+    uint32_t first, n;           /* instances [first, first + n); with a list: first == 0, n = its length */
+    const uint32_t *witnesses;   /* HOST, strictly ascending, or NULL = the whole map */
+    uint32_t n_witnesses;
+    uint64_t pitch;              /* bytes from one instance's slot to the next; 0 = the bound; a multiple of 16 */
+} acvm_wire_desc_t;
+long long acvm_batch_wire_bound(const acvm_batch_t *b, const acvm_wire_desc_t *d);
+int acvm_batch_witness_maps_wire_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances /* DEVICE or NULL */,
+                                        void *d_bytes /* DEVICE, 16-byte aligned */, uint64_t *d_lengths /* DEVICE [n], may be NULL */);
+int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out /* host, n * pitch */, uint64_t *lengths /* host [n] */);
 
 
 /*
