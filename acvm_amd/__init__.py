@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "acvm_batch_wire_bound", "acvm_batch_witness_maps_wire_device", "acvm_batch_witness_maps_wire",
     "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
     "acvm_debug_lin_add", "acvm_debug_lin_plan",
+    "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
 ]
 
 
@@ -156,6 +157,11 @@ def wire_desc(container, first, n, witnesses=None, pitch=0):
         arr = (C.c_uint32 * max(len(ws), 1))(*ws)
         desc.witnesses, desc.n_witnesses = arr, len(ws)
     return desc, arr
+
+
+class WireInDesc(C.Structure):
+    """acvm_wire_in_desc_t"""
+    _fields_ = [("container", C.c_uint32), ("pitch", C.c_uint64)]
 
 
 class RecordMaskedField(C.Structure):
@@ -626,6 +632,9 @@ def lib():
         L.acvm_batch_wire_bound.argtypes = [C.c_void_p, C.POINTER(WireDesc)]
         L.acvm_batch_witness_maps_wire_device.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_void_p, C.c_void_p]
         L.acvm_batch_witness_maps_wire.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_wire"):
+        L.acvm_batch_import_device_wire.argtypes = [C.c_void_p, C.POINTER(WireInDesc), C.c_void_p, C.c_void_p]
+        L.acvm_batch_set_initial_witness_maps_wire.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -1419,6 +1428,31 @@ class Batch:
             raise ValueError("records has the wrong size")
         desc, _keep = record_masked_desc(pitch, fields)
         _check(lib().acvm_batch_set_initial_witness_records_masked(self._h, C.byref(desc), buf.ctypes.data if buf.size else None))
+
+    def import_device_wire(self, d_ptr: int, container, pitch: int, d_lengths=None):
+        """The initial witnesses read from serialised WitnessMaps in device memory (acvm_batch_import_device_wire): instance j's map -- the
+        bincode body (WIRE_BINCODE) or the stored-block gzip member around it (WIRE_GZIP_STORED), what witness_maps_wire_device writes -- is the
+        slot at d_ptr + j * pitch (d_ptr 16-byte aligned, pitch a multiple of 16). An initial witness a row does not name is absent, as under a
+        mask byte 0 of import_device_masked. d_lengths: device pointer of B uint64 lengths, or None = each row's count word gives its length.
+        Bytes that are no such map raise, and the batch is then without initial witnesses until another import."""
+        desc = WireInDesc(container=container, pitch=pitch)
+        _check(lib().acvm_batch_import_device_wire(self._h, C.byref(desc), d_ptr, d_lengths))
+
+    def set_initial_witness_maps_wire(self, maps):
+        """One serialised WitnessMap per instance from host memory (acvm_batch_set_initial_witness_maps_wire): maps is a list of B bytes objects,
+        each what compress_witness / compressWitness writes (any gzip stream) or the raw bincode body. Everything decompress_witness reads is
+        accepted with the same meaning; every key must be one of the ids the batch was created with. A row that does not parse raises naming its
+        instance, and the batch keeps the initial witnesses it had."""
+        import numpy as np
+        maps = [bytes(m) for m in maps]
+        if len(maps) != self.B:
+            raise ValueError("one serialised map per instance")
+        lengths = np.array([len(m) for m in maps], dtype=np.uint64)
+        pitch = max([len(m) for m in maps] + [1])
+        buf = np.zeros(self.B * pitch, dtype=np.uint8)
+        for j, m in enumerate(maps):
+            buf[j * pitch:j * pitch + len(m)] = np.frombuffer(m, dtype=np.uint8)
+        _check(lib().acvm_batch_set_initial_witness_maps_wire(self._h, buf.ctypes.data if buf.size else None, pitch, lengths.ctypes.data if self.B else None))
 
     def import_state(self) -> dict:
         """what the last import left on the device (acvm_debug_import_state), as uint32 arrays: rows [n_initial][2][B][4], planes [n_initial][B],

@@ -6,6 +6,8 @@
 #include "export_encode.hpp"
 #include "import_mask.hpp"
 #include "record_plan.hpp"
+#include "wire_decode.hpp"
+#include "wire_in_plan.hpp"
 
 static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
                   EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
@@ -279,6 +281,100 @@ int acvm_batch_import_device_records_masked(acvm_batch_t *b, const acvm_record_m
 } ABI_CATCH
 int acvm_batch_set_initial_witness_records_masked(acvm_batch_t *b, const acvm_record_masked_desc_t *d, const void *records) try {
     return import_records_masked(b, d, records, true);
+} ABI_CATCH
+
+// ---- the wire import (include/acvm_amd.h acvm_batch_import_device_wire): wire_in_plan.cpp checks the descriptor and makes the sorted id table
+// and the CRC power table, which go up into the staging arena (nothing per instance); kernels_wire_in.hip reads the slots. It ends as the masked
+// import ends (import_masked_and_wait): the same wait, the same few words read back, the same fail-closed refusal and bookkeeping. A wire import
+// never rides behind a solve.
+static const char *wire_in_class_text(uint32_t cls) {
+    static const char *const text[WIRE_IN_CLASSES] = {"", "the count word cannot be a map of this slot", "an entry's length word is not 64", "a character that is not a hex digit",
+                                                      "a key that is not an initial witness of this handle", "keys not strictly ascending",
+                                                      "a framing word of the gzip member is not the pinned one", "the trailer's CRC-32 is not the body's"};
+    return text[cls < WIRE_IN_CLASSES ? cls : 0];
+}
+// host_slots: the host form's staged BINCODE slots (B * plan.pitch bytes), which go up behind the tables; else d_bytes is the caller's
+static int import_wire_and_wait(acvm_batch *b, const WireInPlan &plan, const void *d_bytes, const uint64_t *d_lengths, const std::vector<uint8_t> *host_slots) {
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = missing_set_ready(b)) return rc;  // (in front of everything: a refusal so far leaves the handle as it was)
+    const bool gzip = plan.container == ACVM_WIRE_GZIP_STORED;
+    // the arena: [keys][positions][crc powers][crc words][host form: slots]
+    size_t at = 0;
+    auto carve = [&](size_t n_bytes) { const size_t begin = at; at += align256(n_bytes); return begin; };
+    const size_t at_keys = carve(plan.keys.size() * 4), at_positions = carve(plan.positions.size() * 4), at_pow = carve(plan.crc_pow.size() * 4);
+    const size_t at_crc = carve(gzip ? (size_t)b->B * 4 : 0), at_slots = carve(host_slots ? host_slots->size() : 0);
+    if (int rc = stage_reserve(b, at)) return rc;
+    hipStream_t s = b->stream;
+    auto put = [&](size_t where, const void *from, size_t n_bytes) -> hipError_t {
+        return n_bytes ? hipMemcpyAsync(b->d_stage + where, from, n_bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIPCHK(put(at_keys, plan.keys.data(), plan.keys.size() * 4));
+    HIPCHK(put(at_positions, plan.positions.data(), plan.positions.size() * 4));
+    HIPCHK(put(at_pow, plan.crc_pow.data(), plan.crc_pow.size() * 4));
+    if (host_slots) HIPCHK(put(at_slots, host_slots->data(), host_slots->size()));
+    // (d_mask_result is zero here: since its allocation, or since the memset the previous masked or wire import left behind on the stream)
+    const WireImport x{host_slots ? b->d_stage + at_slots : (const uint8_t *)d_bytes, plan.pitch, d_lengths, plan.container, b->B, plan.n_initial,
+                       (const uint32_t *)(b->d_stage + at_keys), (const uint32_t *)(b->d_stage + at_positions), b->reuse() ? b->d_init_rows : b->d_init_ids,
+                       b->d_byte_plane_of_input, b->d_byte_plane, b->d_W, b->Bp, b->d_event, b->d_missing, (uint32_t *)(b->d_stage + at_crc),
+                       gzip ? (const uint32_t *)(b->d_stage + at_pow) : nullptr, plan.crc_x64, plan.rank_bits, b->d_mask_result};
+    const bool reset_written = launch_wire_import(s, x, plan.n_windows);
+    import_epilogue(b, true, reset_written);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_mask_result, b->d_mask_result, IMPORT_MASK_RESULT_WORDS * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (also what keeps the plan's tables and the staged slots alive for their copies)
+    const uint64_t result[IMPORT_MASK_RESULT_WORDS] = {b->h_mask_result[0], b->h_mask_result[1], b->h_mask_result[2]};
+    HIPCHK(hipMemsetAsync(b->d_mask_result, 0, IMPORT_MASK_RESULT_WORDS * 8, s));
+    if (result[IMPORT_MASK_BAD]) {
+        // The host could not see the bytes beforehand and rows are written: the handle is left without initial witnesses.
+        b->inputs_set = false;
+        const uint64_t key = result[IMPORT_MASK_BAD_KEY];
+        const uint32_t cls = wire_in_key_class(key, plan.rank_bits);
+        return set_err(ACVM_E_INVALID, "wire import: " + std::to_string(result[IMPORT_MASK_BAD]) + " findings, the first of them instance " +
+                                           std::to_string(wire_in_key_instance(key, plan.rank_bits)) + ", class " + std::to_string(cls) + " (" + wire_in_class_text(cls) + "), entry " +
+                                           std::to_string(wire_in_key_rank(key, plan.rank_bits)) + "; the handle is left without initial witnesses");
+    }
+    b->n_missing = result[IMPORT_MASK_MISSING];
+    return 0;
+}
+static int wire_in_plan_of(const acvm_batch *b, const acvm_wire_in_desc_t *d, const void *bytes, bool device, WireInPlan *out) {
+    std::string err;
+    const int rc = wire_in_plan(b ? &b->B : nullptr, b ? b->plan().initial_ids.data() : nullptr, b ? (uint32_t)b->plan().initial_ids.size() : 0u, d, bytes, device, out, &err);
+    return rc ? set_err(rc, err) : 0;
+}
+int acvm_batch_import_device_wire(acvm_batch_t *b, const acvm_wire_in_desc_t *d, const void *d_bytes, const uint64_t *d_lengths) try {
+    WireInPlan plan;
+    if (int rc = wire_in_plan_of(b, d, d_bytes, true, &plan)) return rc;
+    return import_wire_and_wait(b, plan, d_bytes, d_lengths, nullptr);
+} ABI_CATCH
+// The host form: every row judged on the host (wire_in_plan.cpp) -- inflated where it is a gzip member, staged as it is where the device form
+// reads it, through the reader and the writer where not -- and nothing enqueued before every row has passed.
+int acvm_batch_set_initial_witness_maps_wire(acvm_batch_t *b, const uint8_t *bytes, uint64_t pitch, const uint64_t *lengths) try {
+    const acvm_wire_in_desc_t d{ACVM_WIRE_BINCODE, pitch};
+    WireInPlan plan;
+    if (int rc = wire_in_plan_of(b, &d, bytes, false, &plan)) return rc;
+    if (b->B && !lengths) return set_err(ACVM_E_INVALID, "null lengths");
+    plan.pitch = wire_in_stage_pitch(plan.n_initial);
+    std::vector<uint8_t> slots((size_t)b->B * plan.pitch), inflated, body, values;
+    std::vector<uint32_t> ids;
+    for (uint32_t j = 0; j < b->B; j++) {
+        const uint8_t *row = bytes + (size_t)j * pitch;
+        size_t len = (size_t)lengths[j];
+        auto refuse = [&](const std::string &text) { return set_err(ACVM_E_INVALID, "instance " + std::to_string(j) + ": " + text); };
+        if (len >= 2 && row[0] == 0x1f && row[1] == 0x8b) {
+            if (!witness_map_inflate(row, len, inflated)) return refuse("gzip stream is corrupt");
+            row = inflated.data();
+            len = inflated.size();
+        }
+        if (!wire_in_body_canonical(plan, row, len)) {
+            std::string err;
+            if (!witness_map_from_bytes(row, len, ids, values, err)) return refuse(err);
+            if (wire_in_body_of_map(plan, ids.data(), values.data(), ids.size(), &body, &err)) return refuse(err);
+            row = body.data();
+            len = body.size();
+        }
+        memcpy(&slots[(size_t)j * plan.pitch], row, len);
+    }
+    return import_wire_and_wait(b, plan, nullptr, nullptr, &slots);
 } ABI_CATCH
 
 // What the last import left (include/acvm_amd.h): rows, planes, event words and missing set of the live instances, for the tests that compare two

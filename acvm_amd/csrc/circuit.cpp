@@ -362,6 +362,8 @@ bool witness_map_from_bytes(const uint8_t *buf, size_t len, std::vector<uint32_t
     return true;
 }
 
+bool witness_map_inflate(const uint8_t *buf, size_t len, std::vector<uint8_t> &out) { return gunzip(buf, len, out); }
+
 bool witness_map_to_bytes(const uint32_t *ids, const uint8_t *values_be32, size_t n, std::vector<uint8_t> &out, std::string &err) {
     // BTreeMap order: ascending witness index; a repeated index keeps its last value (map insert)
     std::map<uint32_t, const uint8_t *> m;

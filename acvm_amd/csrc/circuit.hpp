@@ -108,5 +108,7 @@ std::unique_ptr<Circuit> circuit_from_bytes(const uint8_t *buf, size_t len, std:
 // a FieldElement being its 64-character hex string. Values are canonical 32-byte big-endian (reduced on read).
 bool witness_map_from_bytes(const uint8_t *buf, size_t len, std::vector<uint32_t> &ids, std::vector<uint8_t> &values_be32, std::string &err);
 bool witness_map_to_bytes(const uint32_t *ids, const uint8_t *values_be32, size_t n, std::vector<uint8_t> &out, std::string &err);
+// the gzip layer alone, as witness_map_from_bytes takes it off: any deflate stream; false: the stream is corrupt
+bool witness_map_inflate(const uint8_t *buf, size_t len, std::vector<uint8_t> &out);
 
 }  // namespace acvm

@@ -210,6 +210,28 @@ struct WireExport {
 // per lane of the exact path and 32-witness word: its assigned list positions in the words below, and behind the last word their total
 void launch_wire_lane_prefix(hipStream_t s, const uint32_t *assigned_bits, uint32_t n_slow, uint32_t n_words, const uint32_t *list_mask, uint32_t *lane_prefix);
 void launch_wire_export(hipStream_t s, const WireExport &x, uint32_t n_windows);
+// ---- kernels_wire_in.hip (acvm_batch_import_device_wire): instance j reads the serialised WitnessMap in the slot at in + j * pitch (16-aligned,
+// pitch a multiple of 16) as its initial witnesses; what the row does not name is absent (import_mask.hpp: the missing set). keys / positions /
+// crc_pow / crc_x64 / rank_bits: wire_in_plan.hpp's tables (crc_pow null for BINCODE); rows / plane_of_input: per position of initial_ids, as
+// launch_import_mask takes them; crc: B words of scratch (GZIP_STORED; else unused); lengths: B device words or null; result: three words,
+// zero before the call -- [IMPORT_MASK_BAD] the findings, [IMPORT_MASK_BAD_KEY] the smallest wire_in_key, [IMPORT_MASK_MISSING] the instances
+// with an absent input. Every row of the live instances, every plane word of an input that has one, every missing word and the event words
+// are written exactly once. Returns what launch_import returns: whether the event words were reset.
+struct WireImport {
+    const uint8_t *in;
+    uint64_t pitch;
+    const uint64_t *lengths;
+    uint32_t container, B, n_in;
+    const uint32_t *keys, *positions, *rows, *plane_of_input;
+    uint32_t *plane;
+    uint4 *W;
+    uint64_t Bp;
+    uint32_t *event_reset, *missing, *crc;
+    const uint32_t *crc_pow;
+    uint32_t crc_x64, rank_bits;
+    uint64_t *result;
+};
+bool launch_wire_import(hipStream_t s, const WireImport &x, uint32_t n_windows);
 // ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
 // {status, err, opcode index, index in the range} over them; any column may be null
 void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);

@@ -22,6 +22,15 @@ static uint32_t crc_xpow_bytes(uint64_t bytes) {  // x^(8 bytes) mod P
     return r;
 }
 
+std::vector<uint32_t> wire_plan_crc_powers(uint32_t n_positions, uint32_t *x64) {
+    std::vector<uint32_t> pow((size_t)n_positions + 1);
+    const uint32_t step = crc_xpow_bytes(WIRE_PLAN_ENTRY_BYTES);
+    pow[0] = 0x80000000u;
+    for (uint32_t k = 1; k <= n_positions; k++) pow[k] = crc_mul(pow[k - 1], step);
+    *x64 = crc_xpow_bytes(8);
+    return pow;
+}
+
 uint64_t wire_plan_body_offset(uint32_t container, uint64_t k) { return container == ACVM_WIRE_GZIP_STORED ? 16 + k + 20 * (k / WIRE_PLAN_BLOCK_BYTES) : k; }
 uint64_t wire_plan_length(uint32_t container, uint64_t n_entries) {
     const uint64_t L = 8 + (uint64_t)WIRE_PLAN_ENTRY_BYTES * n_entries;
@@ -72,13 +81,7 @@ int wire_plan(const uint32_t *live, const uint32_t *producer, uint32_t n_witness
         if (w < n_witnesses) p.list_mask[w >> 5] |= 1u << (w & 31);
     }
     p.rank[n_positions] = (uint32_t)p.entries.size();
-    if (d->container == ACVM_WIRE_GZIP_STORED) {
-        p.crc_pow.resize((size_t)n_positions + 1);
-        const uint32_t step = crc_xpow_bytes(WIRE_PLAN_ENTRY_BYTES);
-        p.crc_pow[0] = 0x80000000u;
-        for (uint32_t k = 1; k <= n_positions; k++) p.crc_pow[k] = crc_mul(p.crc_pow[k - 1], step);
-        p.crc_x64 = crc_xpow_bytes(8);
-    }
+    if (d->container == ACVM_WIRE_GZIP_STORED) p.crc_pow = wire_plan_crc_powers(n_positions, &p.crc_x64);
     *out = std::move(p);
     return 0;
 }

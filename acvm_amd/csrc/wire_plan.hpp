@@ -38,6 +38,8 @@ uint64_t wire_plan_length(uint32_t container, uint64_t n_entries);
 uint64_t wire_plan_body_offset(uint32_t container, uint64_t k);
 // the length of the longest map `n_positions` list positions can give, rounded up to 16
 uint64_t wire_plan_bound(uint32_t container, uint64_t n_positions);
+// the CRC power table: [n_positions + 1], entry k = x^(8 * 76 * k) mod P; *x64 = x^64 mod P (the reader's too: wire_in_plan.cpp)
+std::vector<uint32_t> wire_plan_crc_powers(uint32_t n_positions, uint32_t *x64);
 
 // 0 and *out, or ACVM_E_INVALID and the text in *err (*out is then untouched). live: null is the null batch, else the live instance count the
 // range is judged by. producer / n_witnesses: the plan's assigned set. list: the call has an instance list (first must be 0; the entries are the

@@ -993,6 +993,63 @@ long long acvm_batch_wire_bound(const acvm_batch_t *b, const acvm_wire_desc_t *d
 int acvm_batch_witness_maps_wire_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances /* DEVICE or NULL */,
                                         void *d_bytes /* DEVICE, 16-byte aligned */, uint64_t *d_lengths /* DEVICE [n], may be NULL */);
 int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out /* host, n * pitch */, uint64_t *lengths /* host [n] */);
+/*
+ * The way back in: the same bytes READ on the device as per-instance, possibly partial, initial witness maps. The reference starts an execution
+ * from them -- executeCircuit takes the initial WitnessMap, and decompressWitness / WitnessMap::try_from(&[u8]) (witness_map.rs:121-146) is how
+ * one arrives from a file or another process. Instance j's map is the slot at d_bytes + j * pitch.
+ *   - Container, alignment and pitch rule are the export's: the buffer acvm_batch_witness_maps_wire_device wrote is this call's input with no
+ *     pass in between. Body: u64le N, then per entry u32le witness, u64le 64 and 64 hex characters, the entry of rank r at body byte 8 + 76 r;
+ *     ACVM_WIRE_GZIP_STORED: the pinned stored-block member described above, the body from byte 16 on with 20 bytes of joint in front of
+ *     every block but the first.
+ *   - An entry's value is the 32 bytes its 64 characters spell, EITHER letter case (hex::decode takes both), reduced mod p like
+ *     FieldElement::from_hex -> from_be_bytes_reduce (generic_ark.rs:263-283): a string >= p is legal input.
+ *   - A witness the row names is held with that value. An initial witness of the handle the row does not name is ABSENT, as for a mask byte 0 of
+ *     acvm_batch_import_device_masked: the row is zero, the plane word 0x80000000, the bit set in the missing set. The handle is left exactly as
+ *     acvm_batch_import_device_masked leaves it for the same values and presence -- rows and planes, the event words reset once, every word of
+ *     the missing set of the live instances rewritten, acvm_debug_import_missing -- and everything behind it is as documented there: solve,
+ *     reset, stepping, slot reuse, a caller's solver. When every row names every initial witness the missing set is empty and none of the three
+ *     missing-set passes behind the schedule is launched.
+ *   - d_lengths[j] (DEVICE, may be NULL) must be the bytes of a map of N_j entries exactly: the reference refuses trailing bytes. With NULL
+ *     the row's own count word gives the length.
+ *   - The bytes are untrusted. No load touches a byte outside [d_bytes, d_bytes + B * pitch); within a slot nothing at or behind
+ *     min(derived length, pitch) influences anything. N is judged before any entry of the row is read: the map's bytes must fit the pitch, and
+ *     N <= n_initial (which follows from the key rule, so the grid is sized by n_initial and never by a value read from the device).
+ *   - Findings, which only the device can see, each with a class code:
+ *       1  the count word cannot be a map of this slot: too long for the pitch, more than n_initial entries, or not what d_lengths[j] says
+ *       2  an entry's length word is not 64
+ *       3  a character that is not a hex digit -- a string starting 0x is one: 64 characters with that prefix are 31 bytes in the reference,
+ *          a shape the device form does not read
+ *       4  a key that is not an initial witness of this handle
+ *       5  keys not strictly ascending: every BTreeMap serialiser writes them ascending, and a repeat ("last one wins" in serde) has no
+ *          parallel meaning
+ *       6  GZIP_STORED: a head, joint, ISIZE or block-header word that is not the pinned one for this body length
+ *       7  GZIP_STORED: the trailer's CRC-32 is not the body's
+ *     A row with a class-1 finding reads no entries and has exactly that one; an entry gives its lowest class; a row gives 6 or else 7. Any
+ *     finding is ACVM_E_INVALID: the message gives the number of findings and names the smallest (instance, class, entry rank), and the handle
+ *     is left WITHOUT initial witnesses -- acvm_batch_solve is ACVM_E_STATE until another import. Nothing per instance comes back: a few words.
+ *   - Refused on the host with ACVM_E_INVALID, nothing enqueued, the handle as it was: a null batch or descriptor; an unknown container; a
+ *     pitch that is 0 or not a multiple of 16; a misaligned d_bytes; a null buffer with B > 0.
+ *   - Synchronous, like every import.
+ * acvm_batch_set_initial_witness_maps_wire is the host form: row j is bytes[j * pitch, + lengths[j]), pitch and alignment of any kind. A row
+ * starting 1f 8b is inflated with zlib -- real deflate streams, what compressWitness writes, not only stored blocks; any other row is the raw
+ * bincode body. A row in canonical shape (every length word 64, no 0x prefix, keys strictly ascending) is staged as it is; any other row goes
+ * through the reader and the writer of acvm_witness_map_decode / _encode, so everything WitnessMap::try_from accepts is accepted with the same
+ * meaning: strings of another length, prefixes, unordered and repeated keys, last one wins. A row the reader rejects -- a corrupt gzip stream, bad hex,
+ * trailing bytes -- a key that is not an initial witness, or a map with more entries than fit is refused before anything is enqueued, the
+ * message naming the instance and the reader's text; the handle stays as it was. Then the bodies go through the staging buffer as
+ * ACVM_WIRE_BINCODE slots and the device path runs.
+ * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant, inflating compressed deflate on the device, keys
+ * outside the handle's initial id set (the reference's ACVM::new would take them; here the plan is keyed by the initial ids), a per-row offset
+ * column instead of a pitch.
+ */
+typedef struct {
+    uint32_t container;   /* ACVM_WIRE_BINCODE or ACVM_WIRE_GZIP_STORED: what every slot holds */
+    uint64_t pitch;       /* bytes from one instance's slot to the next; a multiple of 16 */
+} acvm_wire_in_desc_t;
+int acvm_batch_import_device_wire(acvm_batch_t *b, const acvm_wire_in_desc_t *d, const void *d_bytes /* DEVICE, 16-byte aligned */,
+                                  const uint64_t *d_lengths /* DEVICE [B] or NULL */);
+int acvm_batch_set_initial_witness_maps_wire(acvm_batch_t *b, const uint8_t *bytes /* host */, uint64_t pitch /* any */,
+                                             const uint64_t *lengths /* host [B], required */);
 
 
 /*
