@@ -139,7 +139,7 @@ def record_out_desc(pitch, fields, first, n):
     return RecordOutDesc(pitch=pitch, fields=arr, n_fields=len(fl), first=first, n=n), arr
 
 
-WIRE_BINCODE, WIRE_GZIP_STORED = 0, 1  # ACVM_WIRE_*
+WIRE_BINCODE, WIRE_GZIP_STORED, WIRE_GZIP_DEFLATE = 0, 1, 8  # ACVM_WIRE_* (DEFLATE: export only; the value is gzip's CM byte)
 
 
 class WireDesc(C.Structure):
@@ -1594,16 +1594,18 @@ class Batch:
 
     def wire_bound(self, container=WIRE_GZIP_STORED, witnesses=None) -> int:
         """The bytes of the longest map witness_maps_wire_device can write for this container and witness list (None: the whole map), rounded up
-        to 16 (acvm_batch_wire_bound): the smallest pitch it accepts."""
+        to 16 (acvm_batch_wire_bound): the smallest pitch it accepts. For WIRE_GZIP_DEFLATE it is what the map costs when nothing matches, about
+        0.72 of WIRE_GZIP_STORED's."""
         desc, _keep = wire_desc(container, 0, 0, witnesses)
         return _check(lib().acvm_batch_wire_bound(self._h, C.byref(desc)))
 
     def witness_maps_wire_device(self, d_ptr: int, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None, pitch=0, d_instances=None, d_lengths=None):
         """The WitnessMap of every output row in the reference's wire format, written on the device (acvm_batch_witness_maps_wire_device): row i's
         map goes to d_ptr + i * pitch (d_ptr 16-byte aligned; pitch a multiple of 16, 0 = wire_bound) -- WIRE_BINCODE: the bincode body,
-        WIRE_GZIP_STORED: one gzip member of stored blocks around it, what decompress_witness and every inflater read. One entry per witness the
-        instance assigned, of the whole map or of `witnesses` (strictly ascending). d_lengths: device pointer of uint64 [n] that receives each
-        row's length, or None; nothing at or behind a row's length is written. Row i is instance first + i, or instance d_instances[i] of a
+        WIRE_GZIP_STORED: one gzip member of stored blocks around it, what decompress_witness and every inflater read,
+        WIRE_GZIP_DEFLATE: one gzip member of one dynamic-Huffman block whose code and parse are fixed by the format, for the same readers at a
+        fraction of the size (it is only written: import_device_wire refuses it). One entry per witness the instance assigned, of the whole map
+        or of `witnesses` (strictly ascending). d_lengths: device pointer of uint64 [n] that receives each row's length, or None; nothing at or behind a row's length is written. Row i is instance first + i, or instance d_instances[i] of a
         device array of n absolute instance numbers as export_device_list reads it. Nothing is copied to the host."""
         if n is None:
             if d_instances is not None:
@@ -1613,7 +1615,8 @@ class Batch:
         _check(lib().acvm_batch_witness_maps_wire_device(self._h, C.byref(desc), d_instances, d_ptr, d_lengths))
 
     def witness_maps_wire(self, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None):
-        """witness_maps_wire_device into host memory (acvm_batch_witness_maps_wire): a list of n bytes objects, one serialised map per instance."""
+        """witness_maps_wire_device into host memory (acvm_batch_witness_maps_wire): a list of n bytes objects, one serialised map per instance;
+        WIRE_GZIP_DEFLATE rows are what set_initial_witness_maps_wire and decompress_witness read."""
         import numpy as np
         n = self.B - first if n is None else n
         pitch = self.wire_bound(container, witnesses)

@@ -549,11 +549,12 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
     // the rows of one pass: all of them into the caller's device buffer, or what fits the chunk of the staging arena (whole blocks of 64 rows)
     uint32_t chunk = plan.n;
     if (host) chunk = (uint32_t)std::min<uint64_t>(plan.n, std::max<uint64_t>(64, WIRE_HOST_CHUNK_BYTES / plan.pitch / 64 * 64));
-    // the arena: [witness list][rank][list mask][crc powers][slow ids][lane prefix][crc words][host: lengths, slots]
+    // the arena: [witness list][rank][list mask][crc powers][slow ids][lane prefix][deflate table][crc words][host: lengths, slots]
     size_t at = 0;
     auto carve = [&](size_t n_bytes) { const size_t begin = at; at += align256(n_bytes); return begin; };
     const size_t at_sel = carve(plan.whole ? 0 : (size_t)plan.n_positions * 4), at_rank = carve(plan.rank.size() * 4), at_mask = carve((size_t)n_words * 4);
     const size_t at_pow = carve(plan.crc_pow.size() * 4), at_ids = carve(map_stale ? (size_t)n_slow * 4 : 0), at_prefix = carve(((size_t)n_words + 1) * n_slow * 4);
+    const size_t at_deflate = carve(plan.deflate.size() * 4);
     const size_t at_crc = carve(gzip ? (size_t)chunk * 4 : 0), at_lengths = carve(host ? (size_t)chunk * 8 : 0), at_slots = carve(host ? (size_t)chunk * plan.pitch : 0);
     if (int rc = stage_reserve(b, at)) return rc;
     hipStream_t s = b->stream;
@@ -566,6 +567,7 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
     HIPCHK(put(at_rank, plan.rank));
     HIPCHK(put(at_mask, plan.list_mask));
     HIPCHK(put(at_pow, plan.crc_pow));
+    HIPCHK(put(at_deflate, plan.deflate));
     if (int rc = lane_map_ready(b, s, (uint32_t *)(b->d_stage + at_ids))) return rc;
     uint32_t *d_prefix = n_slow ? (uint32_t *)(b->d_stage + at_prefix) : nullptr;
     launch_wire_lane_prefix(s, b->d_assigned, n_slow, n_words, (const uint32_t *)(b->d_stage + at_mask), d_prefix);
@@ -580,7 +582,8 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
                            b->plan().n_witnesses, b->d_slot_of, b->d_producer, b->unscale.index, b->unscale.consts_plain,
                            plan.whole ? nullptr : (const uint32_t *)(b->d_stage + at_sel), plan.n_positions,
                            (const uint32_t *)(b->d_stage + at_rank), (const uint32_t *)(b->d_stage + at_mask), d_prefix, (const uint32_t *)(b->d_stage + at_pow), plan.crc_x64, d_crc,
-                           plan.container, host ? b->d_stage + at_slots : (uint8_t *)bytes, plan.pitch, host ? (uint64_t *)(b->d_stage + at_lengths) : lengths};
+                           plan.container, host ? b->d_stage + at_slots : (uint8_t *)bytes, plan.pitch, host ? (uint64_t *)(b->d_stage + at_lengths) : lengths,
+                           plan.deflate.empty() ? nullptr : (const uint32_t *)(b->d_stage + at_deflate), plan.deflate_prefix_bits};
         launch_wire_export(s, x, plan.n_windows);
         HIPCHK(hipGetLastError());
         if (host) {
@@ -596,7 +599,8 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
 long long acvm_batch_wire_bound(const acvm_batch_t *b, const acvm_wire_desc_t *d) try {
     if (!d) return set_err(ACVM_E_INVALID, "null argument");
     if (!b) return set_err(ACVM_E_INVALID, "null batch");
-    if (d->container != ACVM_WIRE_BINCODE && d->container != ACVM_WIRE_GZIP_STORED) return set_err(ACVM_E_INVALID, "unknown container " + std::to_string(d->container));
+    if (d->container != ACVM_WIRE_BINCODE && d->container != ACVM_WIRE_GZIP_STORED && d->container != ACVM_WIRE_GZIP_DEFLATE)
+        return set_err(ACVM_E_INVALID, "unknown container " + std::to_string(d->container));
     return (long long)wire_plan_bound(d->container, d->witnesses ? d->n_witnesses : b->plan().n_witnesses);
 } ABI_CATCH
 int acvm_batch_witness_maps_wire_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *d_bytes, uint64_t *d_lengths) try {

@@ -188,7 +188,8 @@ void launch_export_records(hipStream_t s, const RecordExport &x, uint32_t n_wind
 // out + i * pitch (16-aligned, pitch a multiple of 16); row i is instance src.list[i], or first + i where src.list is null. sel: the device
 // copy of the witness list (n_positions entries) or null = position k is witness k; rank / list_mask / crc_pow / crc_x64: wire_plan.hpp's
 // tables; lane_prefix: [(n_witnesses + 31) / 32 + 1][n_slow], made by launch_wire_lane_prefix (null while no instance left the generic path);
-// crc: n zeroed words (GZIP_STORED; else unused); lengths: n device words or null.
+// crc: n zeroed words (GZIP_STORED; else unused); lengths: n device words or null; deflate / deflate_prefix_bits: wire_plan.hpp's code table
+// and the bits of its prefix (GZIP_DEFLATE; else null).
 struct WireExport {
     const uint4 *W;
     uint64_t Bp;
@@ -206,10 +207,14 @@ struct WireExport {
     uint8_t *out;
     uint64_t pitch;
     uint64_t *lengths;
+    const uint32_t *deflate;
+    uint32_t deflate_prefix_bits;
 };
 // per lane of the exact path and 32-witness word: its assigned list positions in the words below, and behind the last word their total
 void launch_wire_lane_prefix(hipStream_t s, const uint32_t *assigned_bits, uint32_t n_slow, uint32_t n_words, const uint32_t *list_mask, uint32_t *lane_prefix);
 void launch_wire_export(hipStream_t s, const WireExport &x, uint32_t n_windows);
+// ---- kernels_wire_deflate.hip: the GZIP_DEFLATE container of the same call, what launch_wire_export dispatches to
+void launch_wire_deflate(hipStream_t s, const WireExport &x, uint32_t n_windows);
 // ---- kernels_wire_in.hip (acvm_batch_import_device_wire): instance j reads the serialised WitnessMap in the slot at in + j * pitch (16-aligned,
 // pitch a multiple of 16) as its initial witnesses; what the row does not name is absent (import_mask.hpp: the missing set). keys / positions /
 // crc_pow / crc_x64 / rank_bits: wire_in_plan.hpp's tables (crc_pow null for BINCODE); rows / plane_of_input: per position of initial_ids, as

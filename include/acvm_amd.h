@@ -960,7 +960,7 @@ long long acvm_batch_witness_map_bytes(acvm_batch_t *b, uint32_t instance, uint8
  *     (00 00 00 ff ff) in front of every block header but the first; CRC-32 of the body and ISIZE = its length mod 2^32. The body starts at
  *     byte 16 of the slot, and a map of N entries takes 16 + L + 20 (ceil(L / 65532) - 1) + 8 bytes, L = 8 + 76 N.
  *   - acvm_batch_wire_bound: the length of the longest map the descriptor can give -- every listed witness assigned, or every witness of the
- *     circuit -- rounded up to 16; negative for a null batch, a null descriptor, an unknown container.
+ *     circuit -- rounded up to 16 (ACVM_WIRE_GZIP_DEFLATE: see there); negative for a null batch, a null descriptor, an unknown container.
  *   - d_lengths[i] (DEVICE, may be NULL): the bytes of row i's map.
  *   - What is never written: a byte of a slot at or behind its row's length, a byte between slots, a byte in front of d_bytes. No byte of
  *     d_bytes is loaded.
@@ -977,11 +977,38 @@ long long acvm_batch_witness_map_bytes(acvm_batch_t *b, uint32_t instance, uint8
  *   - acvm_batch_witness_maps_wire: the same into host memory, range form. The slots are made in the handle's staging buffer in chunks of
  *     instances and copied down once per chunk; row i's bytes [0, lengths[i]) of out + i * pitch are written, lengths must not be NULL, out
  *     needs no alignment.
- * Not here: a node form, an asynchronous variant, compression (a caller who wants small files deflates the BINCODE bodies on its own threads).
- * A body of 4 GiB or more wraps ISIZE as gzip defines it.
+ *   - ACVM_WIRE_GZIP_DEFLATE (= 8, gzip's CM byte; these three calls only, the two import calls refuse it as an unknown container): one gzip
+ *     member around the body that COMPRESSES, every byte pinned, made of these pieces in order.
+ *       Head: the 11 bytes 1f 8b 08 08 00 00 00 00 00 ff 00.
+ *       One deflate block, BFINAL = 1, BTYPE = 10 (dynamic Huffman), LSB first as RFC 1951 packs it. Its code description is a constant of the
+ *       format, 265 bits, the same in every row of every call: HLIT = 21 (278 literal/length codes), HDIST = 12 (13 distance codes), HCLEN = 14;
+ *       the code-length code is STATED, not derived: symbol 16 has 1 bit, 9 has 2, 7 has 3, and 1, 5, 10, 18 have 5 each (the 18 three-bit
+ *       entries in the order 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1); the 278 + 13 lengths are one sequence cut into runs of equal
+ *       lengths -- a run of n zeros: while n >= 11 one symbol 18 over min(n, 138), then while n >= 3 one symbol 17 over min(n, 10), the rest
+ *       as 0s; a run of n lengths v > 0: v itself, then while 3 or more remain one symbol 16 over min(remaining, 6) (the longest repeat
+ *       first: 7 remaining are 6 + v), the rest as v.
+ *       Literal/length code, canonical over symbols 0..277: the 16 bytes '0'-'9' 'a'-'f' 5 bits; symbols 257..277 (match lengths 3..82) 7 bits;
+ *       the remaining 241 symbols (the other 240 literals and end-of-block) in ascending order: the first 103 get 9 bits, the rest 10. The
+ *       Kraft sum is exactly 1: 16/32 + 21/128 + 103/512 + 138/1024.
+ *       Distance code: symbol 0 (distance 1) and symbol 12 (distances 65..96, 5 extra bits, 76 is extra 11), one bit each.
+ *       Token stream, a function of the body alone: the 8 count bytes as 8 literals; then each entry (rank e, its 76 bytes cur, prev = the entry
+ *       of rank e - 1) parsed greedily from p = 0: L76 = the run of positions from p on with cur[q] == prev[q] (0 when e = 0), L1 = the run
+ *       with cur[q] == cur[q - 1] (0 when p = 0); if max(L76, L1) >= 3 a match of that length with distance 76 if L76 >= L1, else distance
+ *       1, and p advances by the length; otherwise the literal cur[p]. No token spans two entries. Then end-of-block; the last byte is
+ *       zero-padded.
+ *       Trailer: CRC-32 of the body and ISIZE = its length mod 2^32, little-endian, at the next BYTE: generally not dword-aligned.
+ *     Bound (acvm_batch_wire_bound): the block is at most 265 + 8 * 10 + n_positions * (12 * 10 + 64 * 5) + 10 bits -- no match costs more
+ *     than the literals it replaces: at most 7 + 4 + 1 + 5 = 17 bits against 5 per byte -- and the member 11 + ceil(bits / 8) + 8 bytes,
+ *     rounded up to 16: about 0.72 of the stored container's. d_lengths[i] is the member's length; a row that names no instance is a map of
+ *     0 entries, 63 bytes. Descriptor, pitch and alignment rule, states, refusals, what is never written or loaded and the host-to-device
+ *     traffic (the plan's tables, 1 384 bytes of code table among them) are the other containers'. The position inside a row is 64-bit.
+ * Not here: a node form, an asynchronous variant, inflating ACVM_WIRE_GZIP_DEFLATE on the device (the host import inflates any deflate
+ * stream), a packed output with an offsets column instead of a pitch, adaptive codes or longer match distances, any change to
+ * acvm_batch_witness_map_bytes. A body of 4 GiB or more wraps ISIZE as gzip defines it.
  */
-enum { ACVM_WIRE_BINCODE = 0,       /* the bincode body alone */
-       ACVM_WIRE_GZIP_STORED = 1 }; /* one gzip member around it, stored blocks */
+enum { ACVM_WIRE_BINCODE = 0,        /* the bincode body alone */
+       ACVM_WIRE_GZIP_STORED = 1,    /* one gzip member around it, stored blocks */
+       ACVM_WIRE_GZIP_DEFLATE = 8 }; /* one gzip member around it, one dynamic-Huffman block (export only; the value is gzip's CM byte) */
 typedef struct {
     uint32_t container;
     uint32_t first, n;           /* instances [first, first + n); with a list: first == 0, n = its length */
