@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
     "acvm_debug_lin_add", "acvm_debug_lin_plan",
     "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
+    "acvm_debug_gate_records",
 ]
 
 
@@ -531,6 +532,7 @@ def lib():
     L.acvm_circuit_plan_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
     L.acvm_circuit_plan_stats_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
     L.acvm_debug_plan_fingerprint.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32]
+    L.acvm_debug_gate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.acvm_circuit_plans_built.restype = C.c_uint64
     L.acvm_circuit_plans_built.argtypes = [C.c_void_p]
     L.acvm_circuit_check_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
@@ -1069,6 +1071,46 @@ class Circuit:
                                               karr, len(keep), out, 128)
         _check(n)
         return list(out[:n])
+
+    GATE_KINDS = ("ASSERT", "SOLVE", "SOLVE_DYN")
+    GATE_OUT_MODES = ("ASIS", "WEAK", "CANON")
+
+    def gate_records(self, initial_ids, fold_digest=False, reuse_slots=False, keep=()) -> list:
+        """Host-only: the gate records of the static plan in stream order (acvm_debug_gate_records), decoded after csrc/gate_record.hpp. One dict per
+        record: program (its wave program), position (0: the host of the wave program), kind ("ASSERT" / "SOLVE" / "SOLVE_DYN"), opcode, out,
+        np_mac, nl_mac, np_pos, np_neg, nl_pos, nl_neg (the lengths of its six term lists), tail (another record follows in its wave), set_local,
+        out_mode ("ASIS" / "WEAK" / "CANON"; None for an ASSERT), sub_k, presum_weak, has_qc, lin_terms (terms that take the table form: 0 where the
+        wave program has no tables or the record does not qualify), words."""
+        ids = list(initial_ids)
+        arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+        keep = list(keep)
+        karr = (C.c_uint32 * max(len(keep), 1))(*keep)
+        flags = (1 if fold_digest else 0) | (2 if reuse_slots else 0)
+        n = _check(lib().acvm_debug_gate_records(self._h, arr, len(ids), flags, karr, len(keep), None, 0))
+        out = (C.c_uint32 * n)()
+        assert _check(lib().acvm_debug_gate_records(self._h, arr, len(ids), flags, karr, len(keep), out, n)) == n
+        n_prog, n_words = out[0], out[1]
+        offsets, lin, stream = out[2:2 + n_prog], out[2 + n_prog:2 + 2 * n_prog], out[2 + 2 * n_prog:n]
+        assert len(stream) == n_words
+        records = []
+        for q in range(n_prog):
+            pos, k = offsets[q], 0
+            while True:
+                w0, w5 = stream[pos], stream[pos + 5]
+                kind, np_mac, nl_mac = w0 & 0xff, (w0 >> 8) & 0xff, (w0 >> 16) & 0xff
+                np_pos, np_neg, nl_pos, nl_neg = w5 & 0xff, (w5 >> 8) & 0xff, (w5 >> 16) & 0xff, w5 >> 24
+                words = 6 + 10 * np_mac + 9 * nl_mac + 2 * (np_pos + np_neg) + nl_pos + nl_neg
+                tabled = lin[q] != 0xFFFFFFFF and np_mac == 0 and np_pos == 0
+                records.append({"program": q, "position": k, "kind": self.GATE_KINDS[kind], "opcode": stream[pos + 1], "out": stream[pos + 2] if kind else None,
+                                "np_mac": np_mac, "nl_mac": nl_mac, "np_pos": np_pos, "np_neg": np_neg, "nl_pos": nl_pos, "nl_neg": nl_neg,
+                                "tail": bool(w0 & 1 << 24), "set_local": bool(w0 & 1 << 25), "out_mode": self.GATE_OUT_MODES[(w0 >> 26) & 3] if kind else None,
+                                "sub_k": (w0 >> 28) & 3, "presum_weak": bool(w0 & 1 << 30), "has_qc": stream[pos + 3] != 0xFFFFFFFD,
+                                "lin_terms": nl_mac if tabled else 0, "words": words})
+                if not w0 & 1 << 24:
+                    break
+                pos += words
+                k += 1
+        return records
 
 
 class NodeOpts(C.Structure):

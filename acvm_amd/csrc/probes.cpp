@@ -430,6 +430,34 @@ int acvm_debug_inverse_batch_shared(const uint32_t *den, uint32_t n_jobs, uint32
     return debug_inverse_batch(den, n_jobs, B, inv_chunk, inverse_share_clamp(inv_share), slot_of, inv_out, event_out, device_count, host_count);
 } ABI_CATCH
 
+// Host-only: the gate stream of the plan a handle of these options would use, copied word for word beside acvm_debug_plan_fingerprint's hashes of it
+// (tests/test_arith_cases.py reads the record shapes -- kinds, counts, flags -- that its case lists reach). out: [n_programs, n_stream_words,
+// gate_offset[n_programs], lin_offset[n_programs] (GATE_LIN_NONE where the plan has none), gate_stream[n_stream_words]]; returns the number of words
+// that is, of which the first min(that, cap) are written (out may be null with cap = 0: ask for the size first).
+int acvm_debug_gate_records(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                            uint32_t *out, uint32_t cap) try {
+    if (!c || (n_initial && !initial_ids) || (n_keep && !keep_ids) || (cap && !out)) return set_err(ACVM_E_INVALID, "null argument");
+    PlanOpts opts;
+    opts.fold_digest = (flags & (ACVM_BATCH_FOLD_DIGEST | ACVM_BATCH_REUSE_SLOTS)) != 0;
+    opts.reuse_slots = (flags & ACVM_BATCH_REUSE_SLOTS) != 0;
+    opts.host_blackbox = (flags & 0x100u) != 0;
+    opts.keep.assign(keep_ids, keep_ids + n_keep);
+    const std::shared_ptr<const Plan> sp = plan_for(c, initial_ids, n_initial, opts);
+    const Plan &p = *sp;
+    if (!p.unsupported.empty()) return set_err(ACVM_E_UNSUPPORTED, p.unsupported);
+    const uint64_t n_prog = p.gate_offset.size(), n_words = p.gate_stream.size(), total = 2 + 2 * n_prog + n_words;
+    if (total > 0x7FFFFFFFull) return set_err(ACVM_E_INVALID, "the gate stream is too large for this probe");
+    std::vector<uint32_t> all;
+    all.reserve((size_t)total);
+    all.push_back((uint32_t)n_prog);
+    all.push_back((uint32_t)n_words);
+    all.insert(all.end(), p.gate_offset.begin(), p.gate_offset.end());
+    for (size_t q = 0; q < n_prog; q++) all.push_back(q < p.lin_offset.size() ? p.lin_offset[q] : GATE_LIN_NONE);
+    all.insert(all.end(), p.gate_stream.begin(), p.gate_stream.end());
+    if (cap) memcpy(out, all.data(), (size_t)std::min<uint64_t>(total, cap) * 4);
+    return (int)total;
+} ABI_CATCH
+
 // The shipped selection kernels through their launcher on a status array of the caller's (kernels_select.hip launch_select). The device's list starts as the
 // caller's out_list, so that what the kernels leave alone comes back as it went in.
 int acvm_debug_select(const uint8_t *status, uint32_t n, uint32_t select_mask, uint32_t *out_list, uint32_t *n_selected) try {

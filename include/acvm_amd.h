@@ -345,6 +345,12 @@ int acvm_circuit_check_schedule(const acvm_circuit_t *c, const uint32_t *initial
  * For tests and tools that assert that a change of the planner moved nothing (tests/test_plan_host.py). */
 int acvm_debug_plan_fingerprint(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids,
                                 uint32_t n_keep, uint64_t *out, uint32_t cap);
+/* Host-only: the gate stream of the same plan word for word (acvm_amd/csrc/gate_record.hpp says what a record's words mean), for tests that assert which
+ * record shapes their inputs reach. out[0] = wave programs, out[1] = words of the stream, then the offset of every wave program in the stream, then the
+ * offset of every wave program's linear tables (0xFFFFFFFF: it has none), then the stream. Returns the number of words that is and writes the first
+ * min(that, cap) of them (out may be NULL with cap = 0). */
+int acvm_debug_gate_records(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids,
+                            uint32_t n_keep, uint32_t *out, uint32_t cap);
 /*
  * ACVM::new for n_instances instances that all assign the same initial witness ids.
  * The circuit is levelised once against that set. `solver` may be NULL (built-in HIP backend).

@@ -27,11 +27,13 @@ The rules and where they stand:
 A Variant is the same model wrong in ONE way; tests/test_mem_cases.py uses them to prove that each list of tests/mem_cases.py would notice."""
 import collections
 
+import arith_ref
 import brillig_ref
 from acvm_amd.acir import P, Arithmetic, BlackBoxFuncCall, Brillig, Expression, MemoryInit, MemoryOp
+from arith_ref import (ST_SOLVED, ST_IN_PROGRESS, ST_FAILURE, ST_REQUIRES_FOREIGN_CALL,  # ACVMStatus and the error kinds as oracle/binding.py numbers them
+                       E_NONE, E_MISSING_ASSIGNMENT, E_TOO_MANY_UNKNOWNS, E_UNSATISFIED, E_INDEX_OOB, E_BRILLIG_FAILED, E_PANIC,
+                       Fail as _Fail, evaluate, insert_value)  # ArithmeticSolver::evaluate and insert_value are restated in tests/arith_ref.py
 
-ST_SOLVED, ST_IN_PROGRESS, ST_FAILURE, ST_REQUIRES_FOREIGN_CALL = 0, 1, 2, 3  # ACVMStatus and the error kinds as oracle/binding.py numbers them
-E_NONE, E_MISSING_ASSIGNMENT, E_TOO_MANY_UNKNOWNS, E_UNSATISFIED, E_INDEX_OOB, E_BRILLIG_FAILED, E_PANIC = 0, 1, 2, 4, 5, 7, 8
 U32, U64 = 1 << 32, 1 << 64
 
 # the texts of the two panics. The first is core's wording of Option::unwrap on None; the result ABI (oracle/pwg.c and the device alike) appends which
@@ -62,40 +64,11 @@ LABELS = (
 VARIANTS = ("readable_is_len", "pred_counts_only_as_one", "index_not_wrapped", "pred_before_to_witness", "replay_style", "dynamic_read_writes_back")
 
 
-class _Fail(Exception):
-    def __init__(self, err, aux0=0, aux1=0, message=None):
-        self.head = (err, aux0, aux1, message)
-
-
 class Block:
     """MemoryOpSolver: block_value (keys are never removed), block_len"""
 
     def __init__(self):
         self.cells, self.len = {}, 0
-
-
-def evaluate(e, wm):
-    """ArithmeticSolver::evaluate: (mul_terms, linear_combinations, q_c) with every known witness folded into the constant"""
-    mul, lin, qc = [], [], 0
-    for c, l, r in e.mul_terms:
-        c %= P
-        if l in wm and r in wm:
-            qc += c * wm[l] * wm[r]
-        elif l not in wm and r not in wm:
-            if c:
-                mul.append((c, l, r))
-        else:
-            known, unknown = (l, r) if l in wm else (r, l)
-            v = c * wm[known] % P
-            if v:
-                lin.append((v, unknown))
-    for c, w in e.linear_combinations:
-        c %= P
-        if w in wm:
-            qc += c * wm[w]
-        elif c:
-            lin.append((c, w))
-    return mul, lin, (qc + e.q_c) % P
 
 
 def get_value(e, wm):
@@ -109,14 +82,6 @@ def get_value(e, wm):
 def to_witness(ev):
     mul, lin, qc = ev
     return lin[0][1] if not mul and len(lin) == 1 and lin[0][0] == 1 and qc == 0 else None
-
-
-def insert_value(wm, w, v):
-    """the map takes the new value FIRST, then the displaced one is compared"""
-    old = wm.get(w)
-    wm[w] = v
-    if old is not None and old != v:
-        raise _Fail(E_UNSATISFIED)
 
 
 def is_constant(e):
@@ -239,22 +204,14 @@ class Model:
 
     # ---- the opcodes around them
     def gate(self, e, wm, hit):
-        """ArithmeticSolver::solve"""
-        mul, lin, qc = evaluate(e, wm)
-        # solve_mul_term / solve_fan_in_term run on the EVALUATED expression: its witnesses are all unknown
-        if len(mul) > 1:
-            raise _Fail(E_PANIC, message=b"Mul term in the arithmetic opcode must contain either zero or one term")
-        if mul or len(lin) > 1:
-            raise _Fail(E_TOO_MANY_UNKNOWNS)
-        if not lin:
-            if qc:
-                hit("gate_unsatisfied")
-                raise _Fail(E_UNSATISFIED)
-            hit("gate_satisfied")
-            return
-        c, w = lin[0]
-        hit("gate_solves")
-        insert_value(wm, w, -qc * pow(c, -1, P) % P)
+        """ArithmeticSolver::solve (tests/arith_ref.py gate); the arms the memory lists reach, under this model's labels"""
+        seen = set()
+        try:
+            arith_ref.gate(e, wm, seen.add)
+        finally:
+            for arm, label in (("arm_solved_solvable_assigns", "gate_solves"), ("arm_solved_satisfied_ok", "gate_satisfied"), ("arm_solved_satisfied_unsatisfied", "gate_unsatisfied")):
+                if arm in seen:
+                    hit(label)
 
     def range(self, op, wm, hit):
         f = op.args["input"]

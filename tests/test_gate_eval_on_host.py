@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import arith_cases as ac
 from acvm_amd import synth
 from acvm_amd.acir import P, Circuit, Expression as E
 from oracle import binding as ob
@@ -103,3 +104,18 @@ def test_without_relaxed_rows(exe, tmp_path):
     out = run(exe, tmp_path, circ, ids, synth.witness_batch(3, seed=3, edge_cases=False), 3, tuning="relax=0")
     modes = [int(x) for x in out.split("asis/weak/canon ")[1].split(",")[0].split("/")]
     assert modes[0] == 0 and modes[1] == 0
+
+
+# list C of tests/arith_cases.py: forced outputs at the limb boundaries, sums that are k p, 0..20 and 254..300 unit terms of each kind, 255 general terms, 31..65
+# multiplied terms (16, 17, 32 and 33 reductions), the grid of record shapes, the large bounds under subtraction and in front of the inverse. The tool runs
+# plans of gates alone that cover their circuit, so the RANGE readers are left out (they assign nothing: the rows and the maps stay what they are; an output
+# they pinned may now be stored relaxed, which is one more plan to bound) and the two circuits whose plan ends at a gate of 256 general terms do not run here.
+LIST_C = [c for c in ac.lists()["C"] if ac.expected_truncation(c) == ac.NOT_TRUNCATED]
+
+
+@pytest.mark.parametrize("tuning", [None, "scale=0"], ids=["default", "scale=0"])
+@pytest.mark.parametrize("case", LIST_C, ids=lambda c: c.name)
+def test_list_c_of_the_arithmetic_edge_cases(exe, tmp_path, case, tuning):
+    gates = [op for op in case.circuit.opcodes if isinstance(op, E)]
+    circ = Circuit(current_witness_index=case.circuit.current_witness_index, opcodes=gates)
+    run(exe, tmp_path, circ, case.ids, synth.values_from_rows(case.rows), len(case.rows), tuning=tuning)

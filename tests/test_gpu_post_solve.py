@@ -7,6 +7,7 @@ import pytest
 import acvm_amd
 from acvm_amd.acir import P, BlackBoxFuncCall as BB, Circuit, Expression as E, FunctionInput as FI, MemoryInit, MemoryOp
 from acvm_amd.synth import be32
+from arith_ref import expr_display, field_display
 
 pytestmark = pytest.mark.gpu
 
@@ -170,32 +171,7 @@ def test_witness_map_blake2s_tree_digest(oracle, shape, force_slow):
 
 
 # ---- OpcodeNotSolvable::ExpressionHasTooManyUnknowns(Expression): the Display text carries the expression (pwg/mod.rs:72-78)
-_SUP = "⁰¹²³⁴⁵⁶⁷⁸⁹"
-
-
-def field_display(v):
-    """impl Display for FieldElement, acir_field/src/generic_ark.rs:13-74, restated with Python integers"""
-    v %= P
-    if v == 0:
-        return "0"
-    minus = (P - v) % P
-    neg = len(str(minus)) < len(str(v))
-    s = minus if neg else v
-    out = "-" if neg else ""
-    if bin(s).count("1") == 1:
-        bit = s.bit_length() - 1
-        return out + (str(1 << bit) if bit < 4 else "2" + "".join(_SUP[int(d)] for d in str(bit)))
-    for power in (64, 32, 16, 8, 4):
-        if s % (1 << power) == 0:
-            return out + "2" + "".join(_SUP[int(d)] for d in str(power)) + "×" + str(s >> power)
-    return out + str(s)
-
-
-def expr_display(mul, lin, qc):
-    """impl Display for Expression (expression/mod.rs:40-48) over Opcode::Arithmetic's Debug text (circuit/opcodes.rs:88-102)"""
-    if not mul and len(lin) == 1 and lin[0][0] % P == 1 and qc % P == 0:
-        return f"x{lin[0][1]}"
-    return "%EXPR [ " + "".join(f"({field_display(c)}, _{a}, _{b}) " for c, a, b in mul) + "".join(f"({field_display(c)}, _{w}) " for c, w in lin) + field_display(qc) + " ]%"
+# (FieldElement's and Expression's Display are restated in the model of the Arithmetic opcode: tests/arith_ref.py field_display, expr_display)
 
 
 def test_field_display_shapes():

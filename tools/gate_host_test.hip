@@ -171,7 +171,10 @@ int main(int argc, char **argv) {
                         n_store++;
                         bool limbs_ok = true;
                         for (int i = 0; i < 8; i++) limbs_ok &= acc.v[i] < (1u << 29);
-                        if (!limbs_ok || !big_lt(big_mul_small(v, 256), big_mul_small(P, kb)) || v.v[8] || v.v[9]) {
+                        // (the bound is inclusive: a subtracted term enters the side sum as 2^k p - x, which IS 2^k p where a zero operand makes x zero -- every
+                        // consumer of a bound takes "at most": gate_h_sub's x <= 2^k p, gate_k_product's ceiling, GATE_K_ROW_MAX p / 256 < 2^256; a canonical row
+                        // alone is strictly below p)
+                        if (!limbs_ok || big_lt(big_mul_small(P, kb), big_mul_small(v, 256)) || (kb == GATE_K_CANON && !big_lt(v, P)) || v.v[8] || v.v[9]) {
                             if (flagged[j] == 0xFFFFFFFFu) { fails++; printf("FAIL opcode %u w%u instance %u: value exceeds the planner's bound %u / 256 p (mode %u)\n", opcode, out, j, kb, (w0 >> GATE_OUT_SHIFT) & 3u); }
                         } else {
                             // slack of the bound: how many p / 256 below it the value is (statistics)
