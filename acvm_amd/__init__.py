@@ -58,7 +58,7 @@ ABI_SYMBOLS = [
     "acvm_batch_export_device_records", "acvm_batch_witness_records",
     "acvm_batch_wire_bound", "acvm_batch_witness_maps_wire_device", "acvm_batch_witness_maps_wire",
     "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
-    "acvm_debug_lin_add", "acvm_debug_lin_plan",
+    "acvm_debug_lin_add", "acvm_debug_lin_plan", "acvm_debug_bundle_plan",
     "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
     "acvm_debug_gate_records",
 ]
@@ -536,6 +536,8 @@ def lib():
     L.acvm_circuit_plans_built.restype = C.c_uint64
     L.acvm_circuit_plans_built.argtypes = [C.c_void_p]
     L.acvm_circuit_check_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    if hasattr(L, "acvm_debug_bundle_plan"):  # (likewise)
+        L.acvm_debug_bundle_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
     if hasattr(L, "acvm_debug_lin_plan"):  # (an older build loaded through ACVM_AMD_LIB for an A/B run has neither)
         L.acvm_debug_lin_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         L.acvm_debug_lin_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1060,6 +1062,31 @@ class Circuit:
         return {"ok": rc == 0, "n_wave_programs": counts[0], "n_programs_with_tables": counts[1], "n_gate_records": counts[2], "n_lin_records": counts[3],
                 "n_lin_terms": counts[4], "n_findings": counts[5], "report": text.value.decode()}
 
+    SHARED_NONE = 0xFFFFFFFE
+
+    def bundle_plan(self, initial_ids, n_instances=4096, fold_digest=False, reuse_slots=False, keep=(), mutation=0) -> dict:
+        """Host-only: the bundles of the static plan (acvm_debug_bundle_plan; csrc/gate_record.hpp "bundles"): per gate launch -- one level -- the wave
+        programs one wave runs one after the other and the operand row they share. Returns {launches: per level a list of (programs, row) with the
+        programs as `gate_records` numbers them and row None where nothing is shared, n_bundles, n_shared_bundles, n_shared_loads_saved (row loads per
+        instance), n_findings (of the hazard checker, after mutation 1 -- a wave program named twice in a copy of the plan -- if asked)}."""
+        ids = list(initial_ids)
+        arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+        keep = list(keep)
+        karr = (C.c_uint32 * max(len(keep), 1))(*keep)
+        flags = (1 if fold_digest else 0) | (2 if reuse_slots else 0)
+        n = _check(lib().acvm_debug_bundle_plan(self._h, arr, len(ids), flags, karr, len(keep), n_instances, mutation, None, 0))
+        out = (C.c_uint32 * n)()
+        assert _check(lib().acvm_debug_bundle_plan(self._h, arr, len(ids), flags, karr, len(keep), n_instances, mutation, out, n)) == n
+        n_levels, n_bundles, n_prog = out[0], out[1], out[2]
+        at = 6
+        level_start = out[at:at + n_levels + 1]; at += n_levels + 1
+        start = out[at:at + n_bundles + 1]; at += n_bundles + 1
+        row = out[at:at + n_bundles]; at += n_bundles
+        prog = out[at:at + n_prog]
+        launches = [[(list(prog[start[b]:start[b + 1]]), None if row[b] == self.SHARED_NONE else row[b]) for b in range(level_start[L], level_start[L + 1])]
+                    for L in range(n_levels)]
+        return {"launches": launches, "n_bundles": n_bundles, "n_shared_bundles": out[3], "n_shared_loads_saved": out[4], "n_findings": out[5]}
+
     def plan_fingerprint(self, initial_ids, fold_digest=False, reuse_slots=False, keep=(), host_solver=False) -> list:
         """Host-only: 64-bit fingerprints of the static plan, one per component (acvm_debug_plan_fingerprint)."""
         ids = list(initial_ids)
@@ -1080,7 +1107,8 @@ class Circuit:
         record: program (its wave program), position (0: the host of the wave program), kind ("ASSERT" / "SOLVE" / "SOLVE_DYN"), opcode, out,
         np_mac, nl_mac, np_pos, np_neg, nl_pos, nl_neg (the lengths of its six term lists), tail (another record follows in its wave), set_local,
         out_mode ("ASIS" / "WEAK" / "CANON"; None for an ASSERT), sub_k, presum_weak, has_qc, lin_terms (terms that take the table form: 0 where the
-        wave program has no tables or the record does not qualify), words."""
+        wave program has no tables or the record does not qualify), words, operands (the operand rows in the order of the term lists; 0xFFFFFFFF =
+        the wave's forwarded value)."""
         ids = list(initial_ids)
         arr = (C.c_uint32 * max(len(ids), 1))(*ids)
         keep = list(keep)
@@ -1101,11 +1129,14 @@ class Circuit:
                 np_pos, np_neg, nl_pos, nl_neg = w5 & 0xff, (w5 >> 8) & 0xff, (w5 >> 16) & 0xff, w5 >> 24
                 words = 6 + 10 * np_mac + 9 * nl_mac + 2 * (np_pos + np_neg) + nl_pos + nl_neg
                 tabled = lin[q] != 0xFFFFFFFF and np_mac == 0 and np_pos == 0
+                t = pos + 6
+                operands = [stream[t + 10 * i + k] for i in range(np_mac) for k in (8, 9)] + [stream[t + 10 * np_mac + 9 * i + 8] for i in range(nl_mac)]
+                operands += stream[t + 10 * np_mac + 9 * nl_mac:pos + words]
                 records.append({"program": q, "position": k, "kind": self.GATE_KINDS[kind], "opcode": stream[pos + 1], "out": stream[pos + 2] if kind else None,
                                 "np_mac": np_mac, "nl_mac": nl_mac, "np_pos": np_pos, "np_neg": np_neg, "nl_pos": nl_pos, "nl_neg": nl_neg,
                                 "tail": bool(w0 & 1 << 24), "set_local": bool(w0 & 1 << 25), "out_mode": self.GATE_OUT_MODES[(w0 >> 26) & 3] if kind else None,
                                 "sub_k": (w0 >> 28) & 3, "presum_weak": bool(w0 & 1 << 30), "has_qc": stream[pos + 3] != 0xFFFFFFFD,
-                                "lin_terms": nl_mac if tabled else 0, "words": words})
+                                "lin_terms": nl_mac if tabled else 0, "words": words, "operands": operands})
                 if not w0 & 1 << 24:
                     break
                 pos += words

@@ -231,7 +231,7 @@ int acvm_circuit_plan_stats_ex(const acvm_circuit_t *c, const uint32_t *initial_
 // same plan meanwhile plans too -- the node driver asks once, before its lanes start).
 static size_t plan_bytes(const Plan &p) {
     size_t words = p.gate_stream.size() + p.gate_offset.size() + p.prog.size() + p.prog_offset.size() + p.prog_scratch.size() + p.bytecode.size() + p.slot_of.size() + p.kbound.size() +
-                   p.unscale_index.size() + p.scaled_ids.size() + p.producer.size() + p.byte_plane_of.size() + p.dyn_offset.size() + p.lin_tables.size() + p.lin_offset.size();
+                   p.unscale_index.size() + p.scaled_ids.size() + p.producer.size() + p.byte_plane_of.size() + p.dyn_offset.size() + p.lin_tables.size() + p.lin_offset.size() + p.bundle_prog.size() + p.bundle_start.size() + p.bundle_row.size() + p.bundle_level_start.size();
     for (int k = 0; k < (int)N_CLS; k++) words += 2 * p.cls_offset[k].size();
     return words * 4 + (p.constants.size() + p.unscale.size()) * sizeof(FrH);
 }
@@ -345,6 +345,38 @@ int acvm_debug_lin_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, ui
     return rep.ok ? 0 : 1;
 } ABI_CATCH
 
+// Host-only: the bundles of the plan a handle of these options would get (plan.hpp Plan::bundle_*), word for word, with the hazard checker's verdict on
+// them, optionally after a mutation of a COPY of the plan: 1 = the second entry of the grouped list names the first one's wave program again.
+// out: [n_levels, n_bundles, n_programs, n_shared_bundles, n_shared_loads_saved, findings of the checker, bundle_level_start[n_levels + 1],
+// bundle_start[n_bundles + 1], bundle_row[n_bundles] (0xFFFFFFFE: no shared row), bundle_prog[n_programs]]; returns the number of words that is, of
+// which the first min(that, cap) are written (out may be null with cap = 0: ask for the size first).
+int acvm_debug_bundle_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                           uint32_t n_instances, uint32_t mutation, uint32_t *out, uint32_t cap) try {
+    if (!c || (n_initial && !initial_ids) || (n_keep && !keep_ids) || (cap && !out)) return set_err(ACVM_E_INVALID, "null argument");
+    PlanOpts opts;
+    opts.fold_digest = (flags & (ACVM_BATCH_FOLD_DIGEST | ACVM_BATCH_REUSE_SLOTS)) != 0;
+    opts.reuse_slots = (flags & ACVM_BATCH_REUSE_SLOTS) != 0;
+    opts.host_blackbox = (flags & 0x100u) != 0;
+    opts.keep.assign(keep_ids, keep_ids + n_keep);
+    const std::shared_ptr<const Plan> sp = plan_for(c, initial_ids, n_initial, opts);
+    if (!sp->unsupported.empty()) return set_err(ACVM_E_UNSUPPORTED, sp->unsupported);
+    Plan p = *sp;
+    if (mutation == 1) {
+        if (p.bundle_prog.size() < 2) return set_err(ACVM_E_INVALID, "the plan has fewer than two wave programs");
+        p.bundle_prog[1] = p.bundle_prog[0];
+    } else if (mutation) return set_err(ACVM_E_INVALID, "no such mutation");
+    const LaunchLayout lay = layout_launches(p, ((uint64_t)n_instances + 63) / 64 * 64);
+    const LevelSchedule sched = level_schedule(p, lay);
+    const ScheduleReport rep = check_level_schedule(p, lay, sched, 0xFFFFFFFFu);
+    const uint64_t total = 6 + p.bundle_level_start.size() + p.bundle_start.size() + p.bundle_row.size() + p.bundle_prog.size();
+    if (total > 0x7FFFFFFFull) return set_err(ACVM_E_INVALID, "the bundle table is too large for this probe");
+    std::vector<uint32_t> all = {p.n_levels, (uint32_t)p.bundle_row.size(), (uint32_t)p.bundle_prog.size(), p.n_shared_bundles, p.n_shared_loads_saved, rep.n_findings};
+    all.reserve((size_t)total);
+    for (const std::vector<uint32_t> *v : {&p.bundle_level_start, &p.bundle_start, &p.bundle_row, &p.bundle_prog}) all.insert(all.end(), v->begin(), v->end());
+    if (cap) memcpy(out, all.data(), (size_t)std::min<uint64_t>(total, cap) * 4);
+    return (int)total;
+} ABI_CATCH
+
 // Host-only: 64-bit FNV-1a fingerprints of everything the planner hands to the device and to the scheduler, component by component
 // (tests/test_plan_host.py, tools/plan_fingerprint.py: a refactoring of the planner must not move a word). out[0..N): see the order below;
 // the per-class record lists are hashed level by level in sorted order (the order inside a level is a launch-placement choice).
@@ -391,6 +423,23 @@ int acvm_debug_plan_fingerprint(const acvm_circuit_t *c, const uint32_t *initial
 // The two fixed field elements of the witness-map digest (include/acvm_amd.h acvm_batch_digest): Blake2s-256 of the ASCII strings
 // "acvm_amd witness map digest: g" / "... h", read as big-endian integers and reduced modulo p.
 
+// The plan's bundle tables as the gate kernels read them (kernels.hpp GateBundles): per entry of the grouped list the wave program's stream offset and its first
+// linear table, the last entry of each bundle marked; per bundle its first entry and shared row.
+static int upload_bundles(acvm_batch *b, const Plan &p) {
+    std::vector<uint2> progs(p.bundle_prog.size()), tab(p.bundle_row.size());
+    for (size_t q = 0; q < progs.size(); q++) {
+        const uint32_t lin = p.lin_offset[p.bundle_prog[q]];
+        if (lin != GATE_LIN_NONE && lin >= GATE_BUNDLE_LIN_NONE) return set_err(ACVM_E_UNSUPPORTED, "more linear tables than a bundle entry can name");
+        progs[q] = make_uint2(p.gate_offset[p.bundle_prog[q]], lin == GATE_LIN_NONE ? GATE_BUNDLE_LIN_NONE : lin);
+    }
+    for (size_t i = 0; i < tab.size(); i++) {
+        tab[i] = make_uint2(p.bundle_start[i], p.bundle_row[i]);
+        progs[p.bundle_start[i + 1] - 1].y |= GATE_BUNDLE_LAST;
+    }
+    if (int rc = upload(&b->d_bundle_progs, progs)) return rc;
+    return upload(&b->d_bundle_tab, tab);
+}
+
 static int batch_init(acvm_batch *b) {
     HIPCHK(hipGetDevice(&b->device));
     hipDeviceProp_t prop;
@@ -409,9 +458,8 @@ static int batch_init(acvm_batch *b) {
     size_t w_bytes = (size_t)(b->reuse() ? p.n_slots : p.n_witnesses) * 2 * b->Bp * sizeof(uint4);
     HIPCHK(hipMalloc((void **)&b->d_W, w_bytes ? w_bytes : 16));
     if (int rc = upload(&b->d_gate_stream, p.gate_stream)) return rc;
-    if (int rc = upload(&b->d_gate_offset, p.gate_offset)) return rc;
     if (int rc = upload(&b->d_lin_tables, p.lin_tables)) return rc;
-    if (int rc = upload(&b->d_lin_offset, p.lin_offset)) return rc;
+    if (int rc = upload_bundles(b, p)) return rc;
     std::vector<uint32_t> consts(p.constants.size() * 8);
     for (size_t i = 0; i < p.constants.size(); i++) {
         const FrH d = frh::to_device_form(p.constants[i]);

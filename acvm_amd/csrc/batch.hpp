@@ -93,8 +93,9 @@ struct acvm_batch {
     int device = 0;
     hipStream_t stream = nullptr;
     uint4 *d_W = nullptr, *d_Mem = nullptr;
-    uint32_t *d_gate_stream = nullptr, *d_gate_offset = nullptr, *d_consts = nullptr;
-    uint32_t *d_lin_tables = nullptr, *d_lin_offset = nullptr;  // Plan::lin_tables, Plan::lin_offset (parallel to d_gate_offset)
+    uint32_t *d_gate_stream = nullptr, *d_consts = nullptr;
+    uint32_t *d_lin_tables = nullptr;  // Plan::lin_tables (the programs' offsets into the stream and the tables: d_bundle_progs)
+    uint2 *d_bundle_progs = nullptr, *d_bundle_tab = nullptr;  // Plan::bundle_* composed for the gate kernels (batch.cpp upload_bundles; kernels.hpp GateBundles)
     uint32_t *d_prog = nullptr, *d_prog_offset = nullptr, *d_bytecode = nullptr, *d_init_ids = nullptr, *d_producer = nullptr;
     uint32_t *d_dyn_offset = nullptr, *d_slow_start = nullptr;
     uint8_t *d_prog_class = nullptr;  // OpClass per opcode, for the one-launch exact path
@@ -277,9 +278,9 @@ struct acvm_batch {
 
     ~acvm_batch() {
         hipSetDevice(device);
-        for (void *p : {(void *)d_W, (void *)d_Mem, (void *)d_gate_stream, (void *)d_gate_offset, (void *)d_consts, (void *)d_prog,
+        for (void *p : {(void *)d_W, (void *)d_Mem, (void *)d_gate_stream, (void *)d_consts, (void *)d_prog,
                         (void *)d_prog_offset, (void *)d_bytecode, (void *)d_init_ids, (void *)d_producer, (void *)d_dyn_offset,
-                        (void *)d_slow_start, (void *)d_lin_tables, (void *)d_lin_offset, (void *)d_event_base, (void *)d_slow_ids, (void *)d_assigned, (void *)d_slow_res})
+                        (void *)d_slow_start, (void *)d_lin_tables, (void *)d_bundle_progs, (void *)d_bundle_tab, (void *)d_event_base, (void *)d_slow_ids, (void *)d_assigned, (void *)d_slow_res})
             if (p) hipFree(p);
         if (h_flag_count) hipHostFree(h_flag_count);
         for (int k = 0; k < (int)N_CLS; k++)

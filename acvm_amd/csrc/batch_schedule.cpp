@@ -50,14 +50,16 @@ static int enqueue_level_schedule(acvm_batch *b, LaunchTimers *tm) {
             if (!b->events_fresh) launch_event_reset(s, b->d_event, b->B);
             b->events_fresh = false;
             break;
-        case SO_GATES:
-            launch_arith_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_gate_offset + st.first, st.count, b->d_consts, b->d_event, b->d_inv, b->d_lin_tables,
-                               b->d_lin_offset + st.first);
+        case SO_GATES: case SO_GATES_LIGHT: {
+            // a gate launch is the whole level's range of wave programs (schedule.cpp), dispatched as the level's bundles (plan.cpp bundle_shared_rows)
+            const uint32_t b0 = p.bundle_level_start[st.level], b1 = p.bundle_level_start[st.level + 1];
+            const GateBundles bundles{b->d_bundle_progs, b->d_bundle_tab + b0, b1 - b0};
+            if (st.op == SO_GATES) launch_arith_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_consts, b->d_event, b->d_inv, b->d_lin_tables, bundles);
+            else
+                launch_arith_light_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_inv, b->dp, b->d_cls_offset[CLS_LIGHT] + st.first2, st.count2, b->d_event, b->d_lin_tables,
+                                         bundles);
             break;
-        case SO_GATES_LIGHT:
-            launch_arith_light_level(s, b->d_W, b->Bp, b->B, b->d_gate_stream, b->d_gate_offset + st.first, st.count, b->d_inv, b->dp,
-                                     b->d_cls_offset[CLS_LIGHT] + st.first2, st.count2, b->d_event, b->d_lin_tables, b->d_lin_offset + st.first);
-            break;
+        }
         case SO_LIGHT: launch_light_level(s, b->d_W, b->Bp, b->B, b->dp, off, st.count, b->d_event); break;
         case SO_LIGHT_SL: launch_light_sl_level(s, b->d_W, b->Bp, b->B, b->dp, off, st.count, b->d_event); break;
         case SO_HASH_COOP: launch_hash_coop_level(s, b->d_W, b->Bp, b->B, b->dp, off, st.count, b->d_event, st.lds_words); break;

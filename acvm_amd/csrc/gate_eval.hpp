@@ -61,6 +61,9 @@ FR_HD __forceinline__ Fr29 gate_operand(const L &ld, uint32_t slot, const Fr29 &
 #endif
         return r;
     }
+    // the bundle's shared row (gate_record.hpp "bundles"): fetched once per bundle by the caller, kept by the loader; GATE_SHARED_NONE is no row
+    // (wave-uniform compare; L::SHARES = false compiles it out)
+    if (L::SHARES && slot == ld.shared_row) return ld.load_shared();
     return ld.load(slot);
 }
 // the witness side of the k-th multiplied term of the record: the products come first (coef[8], a, b), then the linear terms (coef[8], w);
@@ -77,6 +80,8 @@ FR_HD __forceinline__ Fr29 gate_mac_operand(const L &ld, GateWords c, bool produ
 // Value of a record: normalised limbs, below the planner's bound for the record (plan.cpp mirrors this walk term by term).
 //   L: loader with  Fr29 load(uint32_t slot) const  (GATE_LOCAL never reaches it),  Fr29 load_inverse(uint32_t slot) const,
 //      GateWords constant(uint32_t idx) const  (8 words of the constant pool),  bool any(bool) const  (wave-wide OR: the ballot),
+//      static constexpr bool SHARES,  uint32_t shared_row  and  Fr29 load_shared() const: the row the bundle's wave programs share (GATE_SHARED_NONE:
+//      none) and its value in working form, fetched once per bundle,
 //      bool has_lin() const  and  GateWords lin: whether the wave program has linear tables (gate_record.hpp), and the cursor into them. The
 //      cursor is the one thing a record leaves behind for the next one of its wave program: a qualifying record moves it past its
 //      nl_mac tables, every other record leaves it alone (the tables of a wave program lie in record order, plan.cpp build_lin_tables).

@@ -70,6 +70,15 @@ GATE_HD inline uint32_t gate_lin_terms(uint32_t w0, uint32_t w5) {
     return ((w0 >> 8) & 0xff) == 0 && (w5 & 0xff) == 0 ? (w0 >> 16) & 0xff : 0u;
 }
 
+// BUNDLES (plan.hpp Plan::bundle_*, plan.cpp bundle_shared_rows). The wave programs of one launch that one wave runs one after the other share one
+// operand row: the wave fetches it once, keeps its working form (ops_common.hpp: in LDS), and every operand word of every record of the bundle that
+// names that row takes the copy instead of memory (gate_eval.hpp gate_operand). The records say nothing about it -- operand words keep naming
+// the row --: the bundle's entry in Plan::bundle_row decides, GATE_SHARED_NONE = the bundle shares nothing (no operand word ever holds that
+// value: rows are below 2^27, GATE_LOCAL is tested first).
+static constexpr uint32_t GATE_SHARED_NONE = 0xFFFFFFFEu;
+// second word of an entry of the device's grouped program list (kernels.hpp GateBundles): the wave program's first linear table, or none; bit 31: its bundle ends here
+static constexpr uint32_t GATE_BUNDLE_LAST = 1u << 31, GATE_BUNDLE_LIN_NONE = 0x7FFFFFFFu;
+
 // words of a gate record
 GATE_HD inline uint32_t gate_record_words(GateWords g) {
     const uint32_t w0 = g[0], w5 = g[5];

@@ -341,14 +341,15 @@ __global__ void __launch_bounds__(256) unscale_slow_kernel(uint4 *__restrict__ W
 #ifndef ARITH_BLOCK
 #define ARITH_BLOCK 256
 #endif
+static_assert(ARITH_BLOCK == GATE_BLOCK_THREADS, "arith_level_body keeps the bundle's shared row in LDS, nine words per thread of the block");
 #ifndef ARITH_WAVES_MIN  // (tools/build_variant.sh: 7 waves per SIMD = 72 VGPRs + 20 B of scratch measured 5.72-5.76 against 5.79-5.81 M witnesses/s, 8 = 64 VGPRs + 60 B: 5.10-5.14)
 #define ARITH_WAVES_MIN 6
 #endif
 __global__ void __launch_bounds__(ARITH_BLOCK) __attribute__((amdgpu_waves_per_eu(ARITH_WAVES_MIN, 8)))
-arith_level_kernel(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_t *__restrict__ gate_stream, const uint32_t *__restrict__ gate_offset,
-                   const uint32_t *__restrict__ consts, uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, const uint32_t *__restrict__ lin_tables,
-                   const uint32_t *__restrict__ lin_offset) {
-    arith_level_body(W, Bp, B, gate_stream, gate_offset, consts, event, Inv, lin_tables, lin_offset, blockIdx.y);
+arith_level_kernel(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_t *__restrict__ gate_stream, const uint32_t *__restrict__ consts,
+                   uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, const uint32_t *__restrict__ lin_tables, const uint2 *__restrict__ bundle_progs,
+                   const uint2 *__restrict__ bundle_tab) {
+    arith_level_body<true>(W, Bp, B, gate_stream, consts, event, Inv, lin_tables, bundle_progs, bundle_tab, blockIdx.y);
 }
 
 // Denominators of the gates whose unknown is multiplied by a known witness (arithmetic.rs:68-91): 1 / partner for a batch of
@@ -725,13 +726,13 @@ void launch_unscale_slow(hipStream_t s, uint4 *W, uint64_t Bp, const uint32_t *s
     hipLaunchKernelGGL(unscale_slow_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, W, Bp, slow_ids, n_slow, u.scaled_ids, u.n_scaled,
                        u.consts, producer, start_opcode);
 }
-void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset,
-                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv, const uint32_t *lin_tables, const uint32_t *lin_offset) {
+void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *consts, uint32_t *event, const uint4 *inv,
+                        const uint32_t *lin_tables, const GateBundles &bundles) {
     // gridDim.y is limited to 65535
-    for (uint32_t done = 0; done < n_gates;) {
-        uint32_t n = n_gates - done > 65535u ? 65535u : n_gates - done;
-        hipLaunchKernelGGL(arith_level_kernel, dim3((B + ARITH_BLOCK - 1) / ARITH_BLOCK, n), dim3(ARITH_BLOCK), 0, s, W, Bp, B, gate_stream, gate_offset + done, consts, event, inv, lin_tables,
-                           lin_offset + done);
+    for (uint32_t done = 0; done < bundles.count;) {
+        uint32_t n = bundles.count - done > 65535u ? 65535u : bundles.count - done;
+        hipLaunchKernelGGL(arith_level_kernel, dim3((B + ARITH_BLOCK - 1) / ARITH_BLOCK, n), dim3(ARITH_BLOCK), 0, s, W, Bp, B, gate_stream, consts, event, inv, lin_tables, bundles.progs,
+                           bundles.tab + done);
         done += n;
     }
 }

@@ -256,16 +256,22 @@ void launch_gather_columns(hipStream_t s, uint4 *Wx, uint64_t Bpx, const uint4 *
                            const uint32_t *unscale_index, const uint32_t *unscale_consts, const uint32_t *producer, const uint32_t *start_opcode);
 void launch_unscale_slow(hipStream_t s, uint4 *W, uint64_t Bp, const uint32_t *slow_ids, uint32_t n_slow, const Unscale &u, const uint32_t *producer,
                          const uint32_t *start_opcode);
-void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset,
-                        uint32_t n_gates, const uint32_t *consts, uint32_t *event, const uint4 *inv, const uint32_t *lin_tables, const uint32_t *lin_offset);  // lin_offset: parallel to gate_offset
+// The bundles of one gate launch (plan.hpp Plan::bundle_*) as the driver composes them for the device (batch.cpp upload_bundles; ops_common.hpp
+// arith_level_body): tab = the launch's first (first program entry, shared row) pair of `count`; progs = the plan's whole list of (offset in gate_stream,
+// first linear table | GATE_BUNDLE_LAST) pairs, grouped by bundle. grid.y counts the launch's bundles.
+struct GateBundles {
+    const uint2 *progs, *tab;
+    uint32_t count;
+};
+void launch_arith_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *consts, uint32_t *event, const uint4 *inv,
+                        const uint32_t *lin_tables, const GateBundles &bundles);
 void launch_inverse_batch(hipStream_t s, const uint4 *W, uint4 *inv, uint64_t Bp, uint32_t B, const uint32_t *gate_stream,
                           const uint32_t *job_offset, uint32_t n_jobs, uint32_t *event, uint32_t inv_chunk, uint32_t inv_share);
 // waves that share one field inversion (tuning.hpp inv_share): 1, 2, 4 or 8; anything else is the next lower of those
 inline uint32_t inverse_share_clamp(int64_t v) { return v >= 8 ? 8u : v >= 4 ? 4u : v >= 2 ? 2u : 1u; }
-// gates [0, n_gates) of a level and n_light light records of the same level in one launch (n_gates + n_light <= 65535)
-void launch_arith_light_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint32_t *gate_offset, uint32_t n_gates,
-                              const uint4 *inv, const DeviceProgram &dp, const uint32_t *light_offsets, uint32_t n_light, uint32_t *event, const uint32_t *lin_tables,
-                              const uint32_t *lin_offset);
+// the bundles of a level's gates and n_light light records of the same level in one launch (bundles + n_light <= 65535)
+void launch_arith_light_level(hipStream_t s, uint4 *W, uint64_t Bp, uint32_t B, const uint32_t *gate_stream, const uint4 *inv, const DeviceProgram &dp,
+                              const uint32_t *light_offsets, uint32_t n_light, uint32_t *event, const uint32_t *lin_tables, const GateBundles &bundles);
 void launch_modmul_rate(hipStream_t s, uint32_t *out, uint32_t blocks, uint32_t iters);
 void launch_secp_rate(hipStream_t s, uint32_t curve, uint32_t *out, uint32_t blocks, uint32_t iters);  // kernels_ecdsa.hip
 void launch_stream_rate(hipStream_t s, const uint4 *a, const uint4 *b, uint4 *out, uint64_t n);  // n: multiple of 256

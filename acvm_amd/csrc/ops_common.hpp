@@ -74,8 +74,10 @@ static constexpr int EVENT_HDR_WORDS = 4;
 __device__ __forceinline__ void flag_instance(uint32_t *__restrict__ event, uint64_t j, uint32_t opcode) {
     const bool first = atomicMin(&event[j], opcode) == 0xFFFFFFFFu;
     const uint64_t firsts = __builtin_amdgcn_ballot_w64(first);  // over the lanes that are here (the callers sit inside `if (error)`)
-    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-    if (first && (uint32_t)__builtin_ctzll(firsts) == lane) {
+    // the lowest of those lanes counts for all: the one with no flagging lane below it. (Counted from `firsts`, not from the lane's number: that one is
+    // loop-invariant, and the gate kernel, which has no register to spare, kept it alive -- in scratch -- across its whole body for this rare path.)
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(firsts >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)firsts, 0u));
+    if (first && below == 0) {
         const uint32_t n = (uint32_t)__builtin_popcountll(firsts);
         atomicAdd(event - 4, n);
         uint32_t *host = *(uint32_t *const *)(event - 2);
@@ -83,14 +85,32 @@ __device__ __forceinline__ void flag_instance(uint32_t *__restrict__ event, uint
     }
 }
 // ---- the gate kernel's body (kernels.hip arith_level_kernel; kernels_ops.hip runs it beside the light records of the same level):
-// gate_eval.hpp's record evaluation over the witness table. grid = (ceil(B/256), gates in level). Lane = instance. The gate record
-// (number gate_index of the level) is wave-uniform.
+// gate_eval.hpp's record evaluation over the witness table. grid = (ceil(B/256), bundles of the level's wave programs). Lane = instance. The
+// bundle, its wave programs and their gate records are wave-uniform.
+// The bundle's shared row (gate_record.hpp "bundles") waits in LDS, not in registers: nine words per lane, [limb][thread] so that a wave's access is one
+// bank row, written once per bundle and read by the lane that wrote them (no barrier: a lane's own LDS accesses stay in order). Nine registers held
+// across the whole body took the kernel past its 80 (scratch, or five waves); 9 KiB per block of 256 is far below what LDS allows at seven waves.
+static constexpr uint32_t GATE_BLOCK_THREADS = 256;  // threads of a block that runs arith_level_body (kernels.hip ARITH_BLOCK, kernels_ops.hip)
+template <bool SHARE>
 struct GateDeviceLoader {
+    static constexpr bool SHARES = SHARE;
     const uint4 *__restrict__ W;
     const uint4 *__restrict__ Inv;
     const uint32_t *__restrict__ consts;
     uint64_t Bp, j;
     GateWords lin;  // cursor into the wave program's linear tables (gate_eval.hpp), null = it has none: wave-uniform, read by scalar loads like the record
+    uint32_t shared_row;  // the operand row the bundle's wave programs share (wave-uniform), GATE_SHARED_NONE = none
+    uint32_t *shared;     // ... and this lane's first word of it in LDS (the next limb: GATE_BLOCK_THREADS words on)
+    __device__ __forceinline__ void store_shared(const Fr29 &x) const {
+#pragma unroll
+        for (int i = 0; i < 9; i++) shared[i * GATE_BLOCK_THREADS] = x.v[i];
+    }
+    __device__ __forceinline__ Fr29 load_shared() const {
+        Fr29 r;
+#pragma unroll
+        for (int i = 0; i < 9; i++) r.v[i] = shared[i * GATE_BLOCK_THREADS];
+        return r;
+    }
     __device__ __forceinline__ bool has_lin() const { return lin != GATE_WORDS(nullptr); }
     __device__ __forceinline__ Fr29 load(uint32_t slot) const {
         // nontemporal (streaming) loads: an operand row is read by this launch and then not again for levels (5.53 -> 5.55 M witnesses/s)
@@ -108,37 +128,63 @@ struct GateDeviceLoader {
     __device__ __forceinline__ GateWords constant(uint32_t idx) const { return GATE_WORDS(consts) + (uint64_t)idx * 8; }
     __device__ __forceinline__ bool any(bool x) const { return __builtin_amdgcn_ballot_w64(x) != 0; }
 };
+// One wave = one BUNDLE of the launch (plan.cpp bundle_shared_rows): wave programs that run one after the other and share one operand row, which is
+// loaded once here. The two tables are the plan's, composed for the device by the driver (batch.cpp upload_bundles):
+//   bundle_tab[i] = (first entry of bundle i in bundle_progs, its shared row or GATE_SHARED_NONE); the launcher passes the launch's first bundle,
+//     bundle_index counts from there;
+//   bundle_progs[q] = (offset of the wave program in gate_stream, its first linear table or GATE_BUNDLE_LIN_NONE, bit 31 = GATE_BUNDLE_LAST: the bundle ends
+//     here), the programs grouped by bundle. The list ends itself: a cursor is all the loop keeps.
+// (Two pointers where the kernel had gate_offset and lin_offset: the kernel is at its scalar-register limit.) SHARE = false compiles the shared
+// row out: every operand is loaded as its record names it (the bundles' programs still run in their wave, one after the other).
+template <bool SHARE>
 __device__ __forceinline__ void arith_level_body(uint4 *__restrict__ W, uint64_t Bp, uint32_t B, const uint32_t *__restrict__ gate_stream,
-                                                 const uint32_t *__restrict__ gate_offset, const uint32_t *__restrict__ consts,
-                                                 uint32_t *__restrict__ event, const uint4 *__restrict__ Inv, const uint32_t *__restrict__ lin_tables,
-                                                 const uint32_t *__restrict__ lin_offset, uint32_t gate_index) {
+                                                 const uint32_t *__restrict__ consts, uint32_t *__restrict__ event, const uint4 *__restrict__ Inv,
+                                                 const uint32_t *__restrict__ lin_tables, const uint2 *__restrict__ bundle_progs,
+                                                 const uint2 *__restrict__ bundle_tab, uint32_t bundle_index) {
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= B) return;
-    GateWords g = GATE_WORDS(gate_stream) + gate_offset[gate_index];
-    // the wave program's first linear table (in tables; GATE_LIN_NONE: it has none): gate_eval moves the cursor from record to record
-    const uint32_t lin_at = lin_offset[gate_index];
-    GateDeviceLoader ld{W, Inv, consts, Bp, j, lin_at != GATE_LIN_NONE ? GATE_WORDS(lin_tables) + (uint64_t)lin_at * GATE_LIN_TABLE_WORDS : GATE_WORDS(nullptr)};
-    Fr29 local = fr29_from(fr_zero());
-    bool host = true;
-    for (;;) {  // the record, then the records fused behind it (they read this one's output as GATE_LOCAL)
-        const uint32_t w0 = g[0], kind = w0 & 0xff, opcode = g[1], out = g[2];
-        const Fr29 acc = gate_eval(ld, g, local);
-        if (kind == 0) {  // constraint only (arithmetic.rs:92-102): the value is canonical
-            uint32_t z = 0;
+    // (The kernel is at its scalar-register limit. hipcc fetches the pointer arguments as ONE eight-register tuple and, short of registers, parks and
+    // restores that tuple whole -- eight lane moves in front of every use, the constant pool's in every record included. An empty asm makes each pointer
+    // a value of its own: what has to be parked is then the pointers of the rare paths, the event words and the inverse table.)
+    asm volatile("" : "+s"(gate_stream), "+s"(consts), "+s"(event), "+s"(Inv), "+s"(lin_tables));
+    __shared__ uint32_t shared_lds[SHARE ? 9 * GATE_BLOCK_THREADS : 1];
+    GateDeviceLoader<SHARE> ld{W, Inv, consts, Bp, j, GATE_WORDS(nullptr), GATE_SHARED_NONE, shared_lds + (SHARE ? threadIdx.x : 0)};
+    const uint2 bundle = bundle_tab[bundle_index];
+    if (SHARE) {
+        ld.shared_row = bundle.y;
+        if (ld.shared_row != GATE_SHARED_NONE) ld.store_shared(ld.load(ld.shared_row));
+    }
+    const uint2 *__restrict__ next = bundle_progs + bundle.x;
+#pragma unroll 1
+    for (bool last = false; !last;) {
+        const uint2 prog = *next++;
+        last = (prog.y & GATE_BUNDLE_LAST) != 0;
+        const uint32_t lin_at = prog.y & ~GATE_BUNDLE_LAST;
+        GateWords g = GATE_WORDS(gate_stream) + prog.x;
+        // the wave program's first linear table (in tables; none: it has none): gate_eval moves the cursor from record to record
+        ld.lin = lin_at != GATE_BUNDLE_LIN_NONE ? GATE_WORDS(lin_tables) + (uint64_t)lin_at * GATE_LIN_TABLE_WORDS : GATE_WORDS(nullptr);
+        Fr29 local = fr29_from(fr_zero());
+        bool host = true;
+        for (;;) {  // the record, then the records fused behind it (they read this one's output as GATE_LOCAL)
+            const uint32_t w0 = g[0], kind = w0 & 0xff, opcode = g[1], out = g[2];
+            const Fr29 acc = gate_eval(ld, g, local);
+            if (kind == 0) {  // constraint only (arithmetic.rs:92-102): the value is canonical
+                uint32_t z = 0;
 #pragma unroll
-            for (int i = 0; i < 9; i++) z |= acc.v[i];
-            if (z) flag_instance(event, j, opcode);
-        } else {  // coefficients were pre-multiplied by -1/coeff on the host (arithmetic.rs:120)
+                for (int i = 0; i < 9; i++) z |= acc.v[i];
+                if (z) flag_instance(event, j, opcode);
+            } else {  // coefficients were pre-multiplied by -1/coeff on the host (arithmetic.rs:120)
 #ifdef GATE_EXP_NO_STORES  // measurement only: the result leaves through one word (kept alive, never true)
-            if (fr29_pack(acc).v[3] == 0x12345678u && acc.v[5] == 77u) event[j] = 0;
+                if (fr29_pack(acc).v[3] == 0x12345678u && acc.v[5] == 77u) event[j] = 0;
 #else
-            fr_store_nt(W, out, Bp, j, fr29_pack(acc));  // read again levels later, long after it left the caches: 5.38 -> 5.50 M witnesses/s
+                fr_store_nt(W, out, Bp, j, fr29_pack(acc));  // read again levels later, long after it left the caches: 5.38 -> 5.50 M witnesses/s
 #endif
+            }
+            if (!(w0 & GATE_TAIL_FLAG)) break;
+            if (host || (w0 & GATE_SETLOCAL_FLAG)) local = acc;  // the tails read the host's output until a record takes `local` over
+            host = false;
+            g += gate_record_words(g);
         }
-        if (!(w0 & GATE_TAIL_FLAG)) break;
-        if (host || (w0 & GATE_SETLOCAL_FLAG)) local = acc;  // the tails read the host's output until a record takes `local` over
-        host = false;
-        g += gate_record_words(g);
     }
 }
 __device__ __forceinline__ Fr coef_value(uint32_t coef, const uint32_t *__restrict__ consts) {

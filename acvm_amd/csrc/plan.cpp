@@ -374,6 +374,138 @@ void build_lin_tables(Plan &p) {
     }
 }
 
+// =========================================================================== bundles (gate_record.hpp; tuning share, max_bundle)
+// Many wave programs of one launch read the same operand row (the synthetic circuits draw operands from all earlier witnesses: early ones are read
+// by many gates of every level) and nothing made those reads meet in a cache: a row is 32 B x the tile, a level moves gigabytes. A BUNDLE is a list
+// of wave programs of one launch -- one level's range of gate_offset (schedule.cpp) -- that one wave runs one after the other, with one row they share
+// loaded once into registers. Greedy, per level: the row with the most readers among the programs not yet bundled takes up to max_bundle of them
+// (ties: the lowest row; readers in list order, so programs of similar length meet), until no row has two; every other program is a bundle of its
+// own. A row that a record of the level writes is never shared (none exists in a hazard-free plan -- the launch's programs run side by side --: the
+// pass does not rely on it). Bundles are dispatched longest first, by their record words, as the programs were. Runs after lay_out and
+// build_lin_tables: the stream, the order of gate_offset and the level cuts are final, and none of them is touched.
+namespace {
+// operand rows (GATE_LOCAL left out) and output rows of the wave program at pos; returns its words
+template <class R, class Wr>
+size_t walk_program_rows(const std::vector<uint32_t> &gs, size_t pos, R &&read, Wr &&write) {
+    const size_t first = pos;
+    for (;;) {
+        const uint32_t w0 = gs[pos], w5 = gs[pos + 5];
+        const uint32_t np_mac = (w0 >> 8) & 0xff, nl_mac = (w0 >> 16) & 0xff;
+        const uint32_t n_unit = 2 * ((w5 & 0xff) + ((w5 >> 8) & 0xff)) + ((w5 >> 16) & 0xff) + (w5 >> 24);
+        if ((w0 & 0xff) != GATE_ASSERT) write(gs[pos + 2]);
+        size_t t = pos + 6;
+        auto operand = [&](uint32_t row) { if (row != GATE_LOCAL) read(row); };
+        for (uint32_t i = 0; i < np_mac; i++, t += 10) { operand(gs[t + 8]); operand(gs[t + 9]); }
+        for (uint32_t i = 0; i < nl_mac; i++, t += 9) operand(gs[t + 8]);
+        for (uint32_t i = 0; i < n_unit; i++, t++) operand(gs[t]);
+        pos = t;
+        if (!(w0 & GATE_TAIL_FLAG)) break;
+    }
+    return pos - first;
+}
+}  // namespace
+
+void bundle_shared_rows(Plan &p) {
+    p.bundle_prog.clear(); p.bundle_row.clear();
+    p.bundle_start.assign(1, 0);
+    p.bundle_level_start.assign(p.n_levels + 1, 0);
+    p.n_shared_bundles = p.n_shared_loads_saved = 0;
+    const std::vector<uint32_t> &gs = p.gate_stream;
+    const uint32_t cap = p.tune.share && p.tune.max_bundle >= 2 ? (uint32_t)std::min<int64_t>(p.tune.max_bundle, 64) : 1u;
+    struct Bundle { std::vector<uint32_t> progs; uint32_t row; uint64_t words; };
+    for (size_t L = 0; L < p.n_levels; L++) {
+        const uint32_t lo = p.level_start[L], hi = p.level_start[L + 1], m = hi - lo;
+        p.bundle_level_start[L] = (uint32_t)p.bundle_row.size();
+        if (!m) continue;
+        std::vector<uint64_t> words(m);
+        std::vector<std::pair<uint32_t, uint32_t>> reads;  // (row, program of the level): distinct pairs, sorted
+        std::vector<uint32_t> written;
+        for (uint32_t i = 0; i < m; i++)
+            words[i] = walk_program_rows(gs, p.gate_offset[lo + i], [&](uint32_t row) { if (cap > 1) reads.push_back({row, i}); }, [&](uint32_t row) { written.push_back(row); });
+        std::sort(reads.begin(), reads.end());
+        reads.erase(std::unique(reads.begin(), reads.end()), reads.end());
+        std::sort(written.begin(), written.end());
+        std::vector<uint8_t> grouped(m, 0);
+        std::vector<Bundle> bundles;
+        // candidates: (readers not yet bundled, ~row so that the lowest row wins a tie, first entry of the row in `reads`); counts only fall, so an
+        // entry whose count is stale goes back with its true count
+        std::priority_queue<std::tuple<uint32_t, uint32_t, size_t>> heap;
+        for (size_t a = 0; a < reads.size();) {
+            size_t b = a;
+            while (b < reads.size() && reads[b].first == reads[a].first) b++;
+            if (b - a >= 2 && !std::binary_search(written.begin(), written.end(), reads[a].first)) heap.push({(uint32_t)(b - a), ~reads[a].first, a});
+            a = b;
+        }
+        while (!heap.empty()) {
+            const auto [count, nrow, a] = heap.top();
+            heap.pop();
+            const uint32_t row = ~nrow;
+            uint32_t left = 0;
+            for (size_t k = a; k < reads.size() && reads[k].first == row; k++) left += !grouped[reads[k].second];
+            if (left < 2) continue;
+            if (left != count) { heap.push({left, nrow, a}); continue; }
+            Bundle bd{{}, row, 0};
+            for (size_t k = a; k < reads.size() && reads[k].first == row && bd.progs.size() < cap; k++)
+                if (!grouped[reads[k].second]) { grouped[reads[k].second] = 1; bd.progs.push_back(lo + reads[k].second); bd.words += words[reads[k].second]; }
+            if (left - (uint32_t)bd.progs.size() >= 2) heap.push({left - (uint32_t)bd.progs.size(), nrow, a});
+            bundles.push_back(std::move(bd));
+        }
+        for (uint32_t i = 0; i < m; i++)
+            if (!grouped[i]) bundles.push_back({{lo + i}, GATE_SHARED_NONE, words[i]});
+        // longest first (blocks are dispatched in grid order, and a level ends when its last wave ends); with share = 0 this is the programs' own order
+        std::stable_sort(bundles.begin(), bundles.end(), [](const Bundle &x, const Bundle &y) { return x.words != y.words ? x.words > y.words : x.progs[0] < y.progs[0]; });
+        for (const Bundle &bd : bundles) {
+            p.bundle_prog.insert(p.bundle_prog.end(), bd.progs.begin(), bd.progs.end());
+            p.bundle_start.push_back((uint32_t)p.bundle_prog.size());
+            p.bundle_row.push_back(bd.row);
+            if (bd.row == GATE_SHARED_NONE) continue;
+            uint32_t loads = 0;
+            for (uint32_t q : bd.progs) walk_program_rows(gs, p.gate_offset[q], [&](uint32_t row) { loads += row == bd.row; }, [](uint32_t) {});
+            p.n_shared_bundles++;
+            p.n_shared_loads_saved += loads - 1;
+        }
+    }
+    p.bundle_level_start[p.n_levels] = (uint32_t)p.bundle_row.size();
+}
+
+// What bundle_shared_rows promises (tuning plan_validate, like the Planner's check_*; break_it: the injected violation -- a wave program named twice):
+// the bundles of a launch name each of its wave programs exactly once; a bundle with a shared row has at least two programs that read that row as
+// an operand of their records (not GATE_LOCAL); no record of the bundle writes that row (rows, so slot reuse is covered); no bundle is larger than asked.
+void check_bundles(Plan &p, bool break_it) {
+    auto violated = [](const std::string &what) { throw std::logic_error("plan invariant violated after pass bundle_shared_rows: " + what); };
+    if (break_it && p.bundle_prog.size() > 1) p.bundle_prog[1] = p.bundle_prog[0];
+    const size_t n_bundles = p.bundle_row.size();
+    if (p.bundle_start.size() != n_bundles + 1 || p.bundle_start[0] != 0 || p.bundle_start.back() != p.bundle_prog.size() || p.bundle_prog.size() != p.gate_offset.size())
+        violated("the bundle table does not close the list of wave programs");
+    if (p.bundle_level_start.size() != (size_t)p.n_levels + 1 || p.bundle_level_start.back() != n_bundles) violated("the level table does not close the bundles");
+    const uint32_t cap = p.tune.share && p.tune.max_bundle >= 2 ? (uint32_t)std::min<int64_t>(p.tune.max_bundle, 64) : 1u;
+    std::vector<uint8_t> seen(p.gate_offset.size(), 0);
+    for (size_t L = 0; L < p.n_levels; L++) {
+        const uint32_t b0 = p.bundle_level_start[L], b1 = p.bundle_level_start[L + 1];
+        if (b1 < b0 || b1 > n_bundles) violated("the level table goes backwards");
+        if (p.bundle_start[b0] != p.level_start[L] || p.bundle_start[b1] != p.level_start[L + 1]) violated("the bundles of level " + std::to_string(L) + " do not cover the launch's wave programs");
+        for (uint32_t b = b0; b < b1; b++) {
+            const uint32_t q0 = p.bundle_start[b], q1 = p.bundle_start[b + 1], row = p.bundle_row[b];
+            if (q1 <= q0) violated("an empty bundle");
+            if (q1 - q0 > cap) violated("a bundle of " + std::to_string(q1 - q0) + " wave programs, " + std::to_string(cap) + " asked for");
+            if (row == GATE_SHARED_NONE && q1 - q0 != 1) violated("a bundle of several wave programs shares no row");
+            uint32_t readers = 0;
+            for (uint32_t q = q0; q < q1; q++) {
+                const uint32_t prog = p.bundle_prog[q];
+                if (prog < p.level_start[L] || prog >= p.level_start[L + 1]) violated("wave program " + std::to_string(prog) + " is bundled outside its launch");
+                if (seen[prog]++) violated("wave program " + std::to_string(prog) + " is named twice");
+                bool reads = false;
+                walk_program_rows(p.gate_stream, p.gate_offset[prog], [&](uint32_t r) { reads |= r == row; },
+                                  [&](uint32_t r) { if (r == row) violated("a record of the bundle writes the shared row " + std::to_string(row)); });
+                readers += reads;
+            }
+            if (row != GATE_SHARED_NONE && readers < 2) violated("shared row " + std::to_string(row) + " has " + std::to_string(readers) + " reader(s) in its bundle");
+        }
+    }
+    for (size_t q = 0; q < seen.size(); q++)
+        if (!seen[q]) violated("wave program " + std::to_string(q) + " is in no bundle");
+}
+
 // memory blocks: cell ranges of the per-instance memory table + the program-order chain level
 // level = level of the last write (MemoryInit included), rlevel = latest level of a read since that write: reads of a block
 // between two writes have no order among themselves and may share a level; a write comes after every earlier access
@@ -2006,6 +2138,8 @@ Plan build_plan(const Circuit &c, const uint32_t *initial_ids, uint32_t n_initia
     if (v) b.check_layout();
     order_level_records(b.p);                           // placement inside a level
     build_lin_tables(b.p);                              // precomputed reductions of the coefficient terms, beside the stream
+    bundle_shared_rows(b.p);                            // wave programs of a launch that share an operand row, beside the stream
+    if (v) check_bundles(b.p, b.inject(4));
     return b.finish();
 }
 

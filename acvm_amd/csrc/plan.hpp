@@ -76,6 +76,14 @@ struct Plan {
     std::vector<uint32_t> lin_tables;
     std::vector<uint32_t> lin_offset;           // per wave program, parallel to gate_offset: its first table (index in tables), GATE_LIN_NONE = it has none
     uint32_t n_lin_records = 0, n_lin_terms = 0; // statistics: records that take the table form, their terms (= tables)
+    // Bundles (gate_record.hpp "bundles"; tuning share, max_bundle; plan.cpp bundle_shared_rows): the wave programs of one launch -- one level's
+    // range of gate_offset -- that one wave runs one after the other, with one operand row they share loaded once. Beside the record stream like the
+    // linear tables: no record word knows of them, acvm_debug_plan_fingerprint hashes none of this.
+    std::vector<uint32_t> bundle_prog;          // the wave programs (indices into gate_offset) grouped by bundle: per level a permutation of the level's range
+    std::vector<uint32_t> bundle_start;         // size bundles + 1: bundle b runs bundle_prog[bundle_start[b] .. bundle_start[b + 1])
+    std::vector<uint32_t> bundle_row;           // per bundle: the shared operand row, GATE_SHARED_NONE = none
+    std::vector<uint32_t> bundle_level_start;   // size n_levels + 1, indexes the bundles: a bundle never crosses a launch
+    uint32_t n_shared_bundles = 0, n_shared_loads_saved = 0;  // statistics: bundles with a shared row; row loads per instance they save
     std::vector<uint32_t> level_start;          // size n_levels + 1, indexes gate_offset
     std::vector<uint32_t> dyn_offset;           // per inversion job (denominator of a SOLVE_DYN gate), level-major
     std::vector<uint32_t> dyn_level_start;      // size n_levels + 1, indexes dyn_offset

@@ -397,6 +397,25 @@ struct Checker {
         void leaf(uint32_t row) override { c.write(RK_LEAF, row, NONE, who); }
     };
 
+    // ---- BUNDLES: the driver dispatches a gate launch as the bundles of its level (batch_schedule.cpp; plan.hpp Plan::bundle_*). The same wave programs
+    // sit in the same launch, so the access sets below stand as they are: what is left to show is that the bundle table is a partition of the launch's
+    // range [first, first + count) -- every wave program runs, and runs once.
+    void check_launch_bundles(const SchedStep &st) {
+        if (p.bundle_level_start.size() != (size_t)p.n_levels + 1 || st.level >= p.n_levels || p.bundle_start.size() != p.bundle_row.size() + 1) { finding("BUNDLES: " + launch_name(cur) + ": the plan has no bundle table for the launch's level"); return; }
+        const uint32_t b0 = p.bundle_level_start[st.level], b1 = p.bundle_level_start[st.level + 1];
+        if (b0 > b1 || b1 > p.bundle_row.size() || p.bundle_start[b1] > p.bundle_prog.size() || p.bundle_start[b0] > p.bundle_start[b1]) { finding("BUNDLES: " + launch_name(cur) + ": its bundles run past the table"); return; }
+        std::vector<uint8_t> times(st.count, 0);
+        for (uint32_t q = p.bundle_start[b0]; q < p.bundle_start[b1]; q++) {
+            const uint32_t prog = p.bundle_prog[q];
+            if (prog < st.first || prog - st.first >= st.count) { finding("BUNDLES: " + launch_name(cur) + " runs wave program " + std::to_string(prog) + " of another launch"); continue; }
+            if (times[prog - st.first]++) finding("BUNDLES: " + launch_name(cur) + " runs wave program " + std::to_string(prog) + " twice");
+        }
+        for (uint32_t i = 0; i < st.count; i++)
+            if (!times[i]) { finding("BUNDLES: " + launch_name(cur) + " never runs wave program " + std::to_string(st.first + i)); break; }
+        for (uint32_t b = b0; b < b1; b++)
+            if (p.bundle_start[b + 1] <= p.bundle_start[b]) { finding("BUNDLES: " + launch_name(cur) + " has an empty bundle"); break; }
+    }
+
     // ---- (4) a gate wave program: accesses + gate_eval's bounds walk (gate_eval.hpp), operand bounds from the rows' actual writers
     void walk_wave_program(uint32_t gate_index) {
         const std::vector<uint32_t> &gs = p.gate_stream;
@@ -650,6 +669,7 @@ struct Checker {
             switch (st.op) {
             case SO_GATES: case SO_GATES_LIGHT:
                 if ((uint64_t)st.first + st.count > p.gate_offset.size()) { finding("gate launch runs past the gate list"); break; }
+                check_launch_bundles(st);
                 for (uint32_t g = st.first; g < st.first + st.count; g++) { cur_prog = g; walk_wave_program(g); }
                 if (st.op == SO_GATES_LIGHT) walk_class_records(st, CLS_LIGHT, st.first2, st.count2);
                 break;

@@ -23,6 +23,11 @@ struct Tuning {
     int64_t lin_table = 1;         // coefficient x witness terms that share a reduction with no witness product carry a precomputed table (gate_record.hpp "linear tables"): 81 + 16 multiply-adds
                                    // instead of 81 + 72. 0: no tables, the gate kernel evaluates every record as before. The rows' residues are the same either way.
                                    // Headline, one box, three rounds in turn: parent 6.044-6.056 M witnesses/s, 1: 6.156-6.171 (+1.7 %), 0: 6.007-6.034 (NOTEBOOK.md, "Linear tables")
+    int64_t share = 1;             // bundles (gate_record.hpp): wave programs of a launch that read the same operand row run one after the other in one wave, which loads that row once.
+                                   // 0: every wave program is a bundle of its own, the gate kernel loads every operand as before. The rows are the same bit for bit either way.
+    int64_t max_bundle = 8;        // wave programs per bundle at most (2 .. 64; below 2: as share = 0)
+                                   // Headline, one box, two rounds in turn: parent 6.328-6.354 M witnesses/s, 2: 6.490-6.508, 3: 6.566-6.571, 4: 6.585-6.591, 6: 6.609-6.610, 8: 6.608-6.612 (+4.2 %),
+                                   // 12: 6.605-6.609; share = 0 (every program alone, the same kernel): 1.6 % below the parent (NOTEBOOK.md, "Bundles")
     int64_t inv_latency = 1;     // levels of slack between an inversion batch and the first gate that reads it
     int64_t heavy_epoch = 1;       // heavy records launched every K-th level only
     int64_t heavy_latency = 0;     // levels the main stream waits before it reads a heavy output

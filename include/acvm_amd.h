@@ -273,6 +273,14 @@ int acvm_debug_lin_add(const uint32_t *n_terms, const uint32_t *coef, const uint
  * tables starts one table later. counts[6]: wave programs, wave programs with tables, gate records, records that take the table form, tables, findings. */
 int acvm_debug_lin_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
                         uint32_t n_instances, uint32_t mutation, uint64_t *counts, char *report, size_t report_len);
+/* Host-only: the bundles of the plan a handle of these options would get -- the wave programs of each gate launch that one wave runs one after the other
+ * with one shared operand row loaded once (tuning share, max_bundle) -- and the hazard checker's verdict on them, optionally after a mutation of a copy of
+ * the plan: 0 none, 1 the grouped list names a wave program twice. out: [n_levels, n_bundles, n_programs, n_shared_bundles, n_shared_loads_saved (row loads
+ * per instance), findings, bundle_level_start[n_levels + 1], bundle_start[n_bundles + 1], bundle_row[n_bundles] (0xFFFFFFFE: none), bundle_prog[n_programs]
+ * (indices of wave programs in level-major order, as acvm_debug_gate_records lists them)]. Returns the number of words that is; the first min(that, cap)
+ * are written (out may be NULL with cap = 0). */
+int acvm_debug_bundle_plan(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                           uint32_t n_instances, uint32_t mutation, uint32_t *out, uint32_t cap);
 /* The inversion batch of the level schedule (inverse_batch_kernel through its launcher, exactly as a solve starts it) on a table made for the call.
  * den: [n_jobs][B] canonical denominators in the storage form (8 x u32; zero = the instance leaves the generic path at that job). Job k reads row k,
  * carries opcode index k and owns row slot_of[k] of the inverse table (null: row k; otherwise a permutation of [0, n_jobs)); the rows have the batch's

@@ -2,7 +2,9 @@
 // arith_level_kernel runs (gate_eval.hpp is __host__ __device__) over a witness table in host memory, with the planner's bounds for the
 // relaxed rows CHECKED at every store and every stored row replaced by an ADVERSARIAL representative of its residue: the largest
 // value + t p below the bound the planner claims for it (and below 2^256), so that every later gate meets the worst operand its record was
-// sized for. Run by tests/test_gate_eval_on_host.py, which compares the canonical values with the CPU oracle's witness map.
+// sized for. A level is walked bundle by bundle as arith_level_body walks it (plan.cpp bundle_shared_rows): the bundle's shared row is fetched once and every
+// operand word that names it is served from that copy. Run by tests/test_gate_eval_on_host.py, which compares the canonical values with the CPU oracle's
+// witness map, and by tests/test_bundles_on_host.py, which compares them with Python integers.
 //   gate_host_test <in> <out> [seed]
 //   in:  u32 n_circuit_bytes, circuit bytes, u32 n_ids, ids, u32 B, B x n_ids x 32 big-endian values
 //   out: u32 n_witnesses, u32 B, then per instance: u32 flagged (first opcode that left the generic path or 0xFFFFFFFF), n_witnesses x (u8 produced, 32 bytes BE)
@@ -92,6 +94,11 @@ struct HostLoader {
     uint32_t B, j;
     bool force_any;
     GateWords lin;  // the cursor into the wave program's linear tables, as arith_level_body sets it up (ops_common.hpp)
+    static constexpr bool SHARES = true;
+    uint32_t shared_row;  // the row the bundle's wave programs share, loaded once per bundle as arith_level_body does (GATE_SHARED_NONE: none)
+    Fr29 shared;
+    mutable uint64_t n_shared_operands = 0;
+    Fr29 load_shared() const { n_shared_operands++; return shared; }
     bool has_lin() const { return lin != nullptr; }
     Fr29 load(uint32_t slot) const { return fr29_from((*W)[(size_t)slot * B + j]); }
     Fr29 load_inverse(uint32_t slot) const { return fr29_from((*Inv)[(size_t)slot * B + j]); }
@@ -132,7 +139,7 @@ int main(int argc, char **argv) {
     for (uint32_t j = 0; j < B; j++)
         for (uint32_t k = 0; k < n_ids; k++) W[(size_t)ids[k] * B + j] = dev_of(frh::from_be_bytes32_reduce(vals + ((size_t)j * n_ids + k) * 32, 32));
     const Big P = big_p();
-    uint64_t n_store = 0, n_bumped = 0, fails = 0;
+    uint64_t n_store = 0, n_bumped = 0, fails = 0, n_shared_bundle_runs = 0, n_shared_operands = 0;
     uint32_t worst_slack = 0xFFFFFFFFu;
     for (uint32_t L = 0; L < p.n_levels; L++) {
         // the inversion batch of this level (inverse_batch_kernel): 1 / stored denominator, zero denominators leave the generic path
@@ -149,52 +156,60 @@ int main(int argc, char **argv) {
                 Inv[(size_t)g[2] * B + j] = inv;
             }
         }
-        for (uint32_t q = p.level_start[L]; q < p.level_start[L + 1]; q++) {
+        // the level's launch as the kernel dispatches it: bundle by bundle, the shared row loaded once in front of the bundle's wave programs
+        for (uint32_t bi = p.bundle_level_start[L]; bi < p.bundle_level_start[L + 1]; bi++) {
             for (uint32_t j = 0; j < B; j++) {
-                const uint32_t *g = &p.gate_stream[p.gate_offset[q]];
-                const uint32_t lin_at = p.lin_offset[q];
-                HostLoader ld{&W, &Inv, &consts, B, j, (sm() & 3) == 0, lin_at != GATE_LIN_NONE ? p.lin_tables.data() + (size_t)lin_at * GATE_LIN_TABLE_WORDS : nullptr};
-                Fr29 local = fr29_from(fr_zero());
-                bool host = true;
-                for (;;) {
-                    const uint32_t w0 = g[0], kind = w0 & 0xff, opcode = g[1], out = g[2];
-                    Fr29 acc = gate_eval(ld, g, local);
-                    const Big v = big_of29(acc);
-                    if (kind == 0) {
-                        uint32_t z = 0;
-                        for (int i = 0; i < 9; i++) z |= acc.v[i];
-                        if (!big_lt(v, P)) { fails++; printf("FAIL assert value of opcode %u is not canonical\n", opcode); }
-                        if (z) flagged[j] = std::min(flagged[j], opcode);
-                    } else {
-                        // the planner's bound for this row, and the 256 bits of the row
-                        const uint32_t kb = p.kbound[out];
-                        n_store++;
-                        bool limbs_ok = true;
-                        for (int i = 0; i < 8; i++) limbs_ok &= acc.v[i] < (1u << 29);
-                        // (the bound is inclusive: a subtracted term enters the side sum as 2^k p - x, which IS 2^k p where a zero operand makes x zero -- every
-                        // consumer of a bound takes "at most": gate_h_sub's x <= 2^k p, gate_k_product's ceiling, GATE_K_ROW_MAX p / 256 < 2^256; a canonical row
-                        // alone is strictly below p)
-                        if (!limbs_ok || big_lt(big_mul_small(P, kb), big_mul_small(v, 256)) || (kb == GATE_K_CANON && !big_lt(v, P)) || v.v[8] || v.v[9]) {
-                            if (flagged[j] == 0xFFFFFFFFu) { fails++; printf("FAIL opcode %u w%u instance %u: value exceeds the planner's bound %u / 256 p (mode %u)\n", opcode, out, j, kb, (w0 >> GATE_OUT_SHIFT) & 3u); }
+                HostLoader ld{&W, &Inv, &consts, B, j, false, nullptr, p.bundle_row[bi], fr29_from(fr_zero())};
+                if (ld.shared_row != GATE_SHARED_NONE) { ld.shared = ld.load(ld.shared_row); n_shared_bundle_runs++; }
+                for (uint32_t bq = p.bundle_start[bi]; bq < p.bundle_start[bi + 1]; bq++) {
+                    const uint32_t q = p.bundle_prog[bq];
+                    const uint32_t *g = &p.gate_stream[p.gate_offset[q]];
+                    const uint32_t lin_at = p.lin_offset[q];
+                    ld.force_any = (sm() & 3) == 0;
+                    ld.lin = lin_at != GATE_LIN_NONE ? p.lin_tables.data() + (size_t)lin_at * GATE_LIN_TABLE_WORDS : nullptr;
+                    Fr29 local = fr29_from(fr_zero());
+                    bool host = true;
+                    for (;;) {
+                        const uint32_t w0 = g[0], kind = w0 & 0xff, opcode = g[1], out = g[2];
+                        Fr29 acc = gate_eval(ld, g, local);
+                        const Big v = big_of29(acc);
+                        if (kind == 0) {
+                            uint32_t z = 0;
+                            for (int i = 0; i < 9; i++) z |= acc.v[i];
+                            if (!big_lt(v, P)) { fails++; printf("FAIL assert value of opcode %u is not canonical\n", opcode); }
+                            if (z) flagged[j] = std::min(flagged[j], opcode);
                         } else {
-                            // slack of the bound: how many p / 256 below it the value is (statistics)
-                            Big b = v;
-                            // adversarial representative: add p while it stays below the bound and below 2^256
-                            for (;;) {
-                                const Big nb = big_add(b, P);
-                                if (nb.v[8] || nb.v[9] || !big_lt(big_mul_small(nb, 256), big_mul_small(P, kb))) break;
-                                b = nb;
-                                n_bumped++;
+                            // the planner's bound for this row, and the 256 bits of the row
+                            const uint32_t kb = p.kbound[out];
+                            n_store++;
+                            bool limbs_ok = true;
+                            for (int i = 0; i < 8; i++) limbs_ok &= acc.v[i] < (1u << 29);
+                            // (the bound is inclusive: a subtracted term enters the side sum as 2^k p - x, which IS 2^k p where a zero operand makes x zero -- every
+                            // consumer of a bound takes "at most": gate_h_sub's x <= 2^k p, gate_k_product's ceiling, GATE_K_ROW_MAX p / 256 < 2^256; a canonical row
+                            // alone is strictly below p)
+                            if (!limbs_ok || big_lt(big_mul_small(P, kb), big_mul_small(v, 256)) || (kb == GATE_K_CANON && !big_lt(v, P)) || v.v[8] || v.v[9]) {
+                                if (flagged[j] == 0xFFFFFFFFu) { fails++; printf("FAIL opcode %u w%u instance %u: value exceeds the planner's bound %u / 256 p (mode %u)\n", opcode, out, j, kb, (w0 >> GATE_OUT_SHIFT) & 3u); }
+                            } else {
+                                // slack of the bound: how many p / 256 below it the value is (statistics)
+                                Big b = v;
+                                // adversarial representative: add p while it stays below the bound and below 2^256
+                                for (;;) {
+                                    const Big nb = big_add(b, P);
+                                    if (nb.v[8] || nb.v[9] || !big_lt(big_mul_small(nb, 256), big_mul_small(P, kb))) break;
+                                    b = nb;
+                                    n_bumped++;
+                                }
+                                acc = fr29_of_big(b);
                             }
-                            acc = fr29_of_big(b);
+                            W[(size_t)out * B + j] = fr29_pack(acc);
                         }
-                        W[(size_t)out * B + j] = fr29_pack(acc);
+                        if (!(w0 & GATE_TAIL_FLAG)) break;
+                        if (host || (w0 & GATE_SETLOCAL_FLAG)) local = acc;
+                        host = false;
+                        g += gate_record_words(g);
                     }
-                    if (!(w0 & GATE_TAIL_FLAG)) break;
-                    if (host || (w0 & GATE_SETLOCAL_FLAG)) local = acc;
-                    host = false;
-                    g += gate_record_words(g);
                 }
+                n_shared_operands += ld.n_shared_operands;
             }
         }
     }
@@ -226,6 +241,8 @@ int main(int argc, char **argv) {
     fclose(o);
     printf("stores %llu, representatives raised by p %llu times, out modes asis/weak/canon %u/%u/%u, largest record bound %u/256 p\n", (unsigned long long)n_store,
            (unsigned long long)n_bumped, p.n_gate_out_mode[0], p.n_gate_out_mode[1], p.n_gate_out_mode[2], p.max_gate_bound);
+    printf("bundles %zu, with a shared row %u, row loads saved per instance %u, shared rows loaded %llu times, operands served from them %llu\n", p.bundle_row.size(), p.n_shared_bundles,
+           p.n_shared_loads_saved, (unsigned long long)n_shared_bundle_runs, (unsigned long long)n_shared_operands);
     printf(fails ? "FAILED %llu\n" : "OK\n", (unsigned long long)fails);
     return fails ? 1 : 0;
 }
