@@ -17,7 +17,10 @@
 #               (tests/test_record_mask_plan_on_host.py), and the checks, ranks, bound and CRC power table of the batch-wide wire format:
 #               tools/asan/wire_plan_host_test (tests/test_wire_plan_on_host.py), and the checks, key table and row judgement of the batch-wide
 #               wire import: tools/asan/wire_in_plan_host_test (tests/test_wire_in_plan_on_host.py), and the code tables, constant header and
-#               bound of its deflating container: tools/asan/wire_deflate_plan_host_test (tests/test_wire_deflate_plan_on_host.py)
+#               bound of its deflating container: tools/asan/wire_deflate_plan_host_test (tests/test_wire_deflate_plan_on_host.py), and the
+#               gzip import: its checks, arena layout and fixed-code tables: tools/asan/wire_inflate_plan_host_test
+#               (tests/test_wire_inflate_plan_on_host.py), and the per-row inflater the kernel runs, on the host over untrusted rows in heap blocks
+#               of exactly their bounds: tools/asan/wire_inflate_host_test (hipcc, host side sanitized; tests/test_wire_inflate_on_host.py)
 CXX ?= g++
 ASAN_FLAGS = -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wno-sign-compare
 ASAN_SRCS = tools/asan/fuzz_driver.cpp acvm_amd/csrc/circuit.cpp acvm_amd/csrc/plan.cpp acvm_amd/csrc/tuning.cpp acvm_amd/csrc/schedule.cpp acvm_amd/csrc/schedule_check.cpp
@@ -32,11 +35,13 @@ RECORD_OUT_SRCS = tools/record_out_plan_host_test.cpp acvm_amd/csrc/record_out_p
 WIRE_SRCS = tools/wire_plan_host_test.cpp acvm_amd/csrc/wire_plan.cpp
 WIRE_DEFLATE_SRCS = tools/wire_deflate_plan_host_test.cpp acvm_amd/csrc/wire_plan.cpp
 WIRE_IN_SRCS = tools/wire_in_plan_host_test.cpp acvm_amd/csrc/wire_in_plan.cpp acvm_amd/csrc/wire_plan.cpp
+WIRE_INFLATE_PLAN_SRCS = acvm_amd/csrc/wire_inflate_plan.cpp acvm_amd/csrc/wire_in_plan.cpp acvm_amd/csrc/wire_plan.cpp
+WIRE_INFLATE_HDRS = acvm_amd/csrc/wire_inflate_plan.hpp acvm_amd/csrc/wire_in_plan.hpp acvm_amd/csrc/wire_plan.hpp include/acvm_amd.h
 HIPCC ?= /opt/rocm/bin/hipcc
 asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigned_view_host_test tools/asan/node_io_plan_host_test tools/asan/foreign_plan_host_test \
       tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test tools/asan/import_mask_host_test \
       tools/asan/record_plan_host_test tools/asan/record_out_plan_host_test tools/asan/record_mask_plan_host_test tools/asan/wire_plan_host_test \
-      tools/asan/wire_in_plan_host_test tools/asan/wire_deflate_plan_host_test
+      tools/asan/wire_in_plan_host_test tools/asan/wire_deflate_plan_host_test tools/asan/wire_inflate_plan_host_test tools/asan/wire_inflate_host_test
 tools/asan/fuzz_driver: $(ASAN_SRCS) $(wildcard acvm_amd/csrc/*.hpp)
 	$(CXX) $(ASAN_FLAGS) -o $@ $(ASAN_SRCS) -lz
 tools/asan/import_plan_host_test: $(PLAN_SRCS) acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
@@ -65,6 +70,10 @@ tools/asan/wire_deflate_plan_host_test: $(WIRE_DEFLATE_SRCS) acvm_amd/csrc/wire_
 	$(CXX) $(ASAN_FLAGS) -o $@ $(WIRE_DEFLATE_SRCS)
 tools/asan/wire_in_plan_host_test: $(WIRE_IN_SRCS) acvm_amd/csrc/wire_in_plan.hpp acvm_amd/csrc/wire_plan.hpp acvm_amd/csrc/assigned_view.hpp include/acvm_amd.h
 	$(CXX) $(ASAN_FLAGS) -o $@ $(WIRE_IN_SRCS)
+tools/asan/wire_inflate_plan_host_test: tools/wire_inflate_plan_host_test.cpp $(WIRE_INFLATE_PLAN_SRCS) $(WIRE_INFLATE_HDRS)
+	$(CXX) $(ASAN_FLAGS) -o $@ tools/wire_inflate_plan_host_test.cpp $(WIRE_INFLATE_PLAN_SRCS)
+tools/asan/wire_inflate_host_test: tools/wire_inflate_host_test.hip acvm_amd/csrc/wire_inflate.hpp acvm_amd/csrc/wire_encode.hpp $(WIRE_INFLATE_PLAN_SRCS) $(WIRE_INFLATE_HDRS)
+	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/wire_inflate_host_test.hip $(WIRE_INFLATE_PLAN_SRCS)
 tools/asan/assigned_view_host_test: tools/assigned_view_host_test.cpp acvm_amd/csrc/assigned_view.hpp
 	$(CXX) $(ASAN_FLAGS) -o $@ tools/assigned_view_host_test.cpp
 .PHONY: asan

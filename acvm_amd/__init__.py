@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "acvm_batch_import_device_records_masked", "acvm_batch_set_initial_witness_records_masked", "acvm_debug_import_state",
     "acvm_debug_lin_add", "acvm_debug_lin_plan", "acvm_debug_bundle_plan",
     "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
+    "acvm_batch_import_device_wire_gzip", "acvm_batch_set_initial_witness_maps_gzip", "acvm_debug_inflate_rows",
     "acvm_debug_gate_records",
 ]
 
@@ -639,6 +640,10 @@ def lib():
     if hasattr(L, "acvm_batch_import_device_wire"):
         L.acvm_batch_import_device_wire.argtypes = [C.c_void_p, C.POINTER(WireInDesc), C.c_void_p, C.c_void_p]
         L.acvm_batch_set_initial_witness_maps_wire.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    if hasattr(L, "acvm_batch_import_device_wire_gzip"):
+        L.acvm_batch_import_device_wire_gzip.argtypes = [C.c_void_p, C.POINTER(WireInDesc), C.c_void_p, C.c_void_p]
+        L.acvm_batch_set_initial_witness_maps_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.acvm_debug_inflate_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -941,6 +946,33 @@ def debug_inverse_batch(den, inv_chunk, slot_of=None, inv_share=None):
         _check(lib().acvm_debug_inverse_batch_shared(d.ctypes.data, n_jobs, B, inv_chunk, inv_share, None if s is None else s.ctypes.data, inv.ctypes.data,
                                                      ev.ctypes.data, C.byref(dc), C.byref(hc)))
     return inv, ev, dc.value, hc.value
+
+
+def debug_inflate_rows(rows, out_cap, fill=0, pitch=None, lengths=None):
+    """The shipped inflater on gzip members of the caller's, no handle (acvm_debug_inflate_rows): rows is a list of bytes objects, row i placed
+    at i * pitch (default: the longest row, at least 1) with lengths[i] (default: len(rows[i])) readable bytes -- or, with pitch given, one bytes
+    object of len * pitch bytes and lengths a sequence or None (= pitch). out_cap: a multiple of 4. Returns (out uint8 [n][out_cap], which started
+    as `fill` everywhere; lengths uint64 [n]; findings uint32 [n][2] = class, block; crcs uint32 [n])."""
+    import numpy as np
+    if isinstance(rows, (bytes, bytearray)):
+        buf = np.frombuffer(bytes(rows), dtype=np.uint8).copy()
+        n = buf.size // pitch
+        assert buf.size == n * pitch
+        lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint64)
+    else:
+        rows = [bytes(r) for r in rows]
+        n = len(rows)
+        pitch = pitch or max([len(r) for r in rows] + [1])
+        buf = np.zeros(n * pitch, dtype=np.uint8)
+        for i, r in enumerate(rows):
+            buf[i * pitch:i * pitch + min(len(r), pitch)] = np.frombuffer(r[:pitch], dtype=np.uint8)
+        lens = np.array([len(r) for r in rows] if lengths is None else lengths, dtype=np.uint64)
+    assert lens is None or lens.shape == (n,)
+    out = np.full((n, out_cap), fill, dtype=np.uint8)
+    out_lengths, findings, crcs = np.zeros(n, dtype=np.uint64), np.zeros((n, 2), dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+    _check(lib().acvm_debug_inflate_rows(buf.ctypes.data if buf.size else None, pitch, None if lens is None else lens.ctypes.data, n, out_cap,
+                                         out.ctypes.data if out.size else None, out_lengths.ctypes.data, findings.ctypes.data, crcs.ctypes.data))
+    return out, out_lengths, findings, crcs
 
 
 def debug_select(status, select_mask, out=None, want_list=True):
@@ -1527,6 +1559,30 @@ class Batch:
             buf[j * pitch:j * pitch + len(m)] = np.frombuffer(m, dtype=np.uint8)
         _check(lib().acvm_batch_set_initial_witness_maps_wire(self._h, buf.ctypes.data if buf.size else None, pitch, lengths.ctypes.data if self.B else None))
 
+    def import_device_wire_gzip(self, d_ptr: int, pitch: int, d_lengths=None):
+        """The initial witnesses read from gzip members in device memory, inflated on the device (acvm_batch_import_device_wire_gzip): instance
+        j's member -- any deflate stream around its bincode body: what witness_maps_wire_device(WIRE_GZIP_DEFLATE or WIRE_GZIP_STORED) or
+        compressWitness writes -- is the slot at d_ptr + j * pitch (d_ptr 16-byte aligned, pitch a multiple of 16), of which row j reads
+        min(d_lengths[j], pitch) bytes (d_lengths: device pointer of B uint64, or None = pitch). A member that does not inflate raises
+        ("wire inflate: ...") and the batch keeps the initial witnesses it had; a body that is no canonical map raises as import_device_wire does."""
+        desc = WireInDesc(container=WIRE_GZIP_DEFLATE, pitch=pitch)
+        _check(lib().acvm_batch_import_device_wire_gzip(self._h, C.byref(desc), d_ptr, d_lengths))
+
+    def set_initial_witness_maps_gzip(self, maps):
+        """One gzip member per instance from host memory, uploaded compressed and inflated on the device
+        (acvm_batch_set_initial_witness_maps_gzip): maps is a list of B bytes objects, each starting 1f 8b. The inflated body must be in canonical
+        shape (what every BTreeMap serialiser writes); set_initial_witness_maps_wire takes the others."""
+        import numpy as np
+        maps = [bytes(m) for m in maps]
+        if len(maps) != self.B:
+            raise ValueError("one serialised map per instance")
+        lengths = np.array([len(m) for m in maps], dtype=np.uint64)
+        pitch = max([len(m) for m in maps] + [1])
+        buf = np.zeros(self.B * pitch, dtype=np.uint8)
+        for j, m in enumerate(maps):
+            buf[j * pitch:j * pitch + len(m)] = np.frombuffer(m, dtype=np.uint8)
+        _check(lib().acvm_batch_set_initial_witness_maps_gzip(self._h, buf.ctypes.data if buf.size else None, pitch, lengths.ctypes.data if self.B else None))
+
     def import_state(self) -> dict:
         """what the last import left on the device (acvm_debug_import_state), as uint32 arrays: rows [n_initial][2][B][4], planes [n_initial][B],
         events [2 + B], missing [ceil(n_initial / 32)][B]"""
@@ -1677,7 +1733,7 @@ class Batch:
         map goes to d_ptr + i * pitch (d_ptr 16-byte aligned; pitch a multiple of 16, 0 = wire_bound) -- WIRE_BINCODE: the bincode body,
         WIRE_GZIP_STORED: one gzip member of stored blocks around it, what decompress_witness and every inflater read,
         WIRE_GZIP_DEFLATE: one gzip member of one dynamic-Huffman block whose code and parse are fixed by the format, for the same readers at a
-        fraction of the size (it is only written: import_device_wire refuses it). One entry per witness the instance assigned, of the whole map
+        fraction of the size (import_device_wire refuses it; import_device_wire_gzip reads it). One entry per witness the instance assigned, of the whole map
         or of `witnesses` (strictly ascending). d_lengths: device pointer of uint64 [n] that receives each row's length, or None; nothing at or behind a row's length is written. Row i is instance first + i, or instance d_instances[i] of a
         device array of n absolute instance numbers as export_device_list reads it. Nothing is copied to the host."""
         if n is None:

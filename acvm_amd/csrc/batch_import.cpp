@@ -8,6 +8,8 @@
 #include "record_plan.hpp"
 #include "wire_decode.hpp"
 #include "wire_in_plan.hpp"
+#include "wire_inflate.hpp"
+#include "wire_inflate_plan.hpp"
 
 static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
                   EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
@@ -293,13 +295,20 @@ static const char *wire_in_class_text(uint32_t cls) {
                                                       "a framing word of the gzip member is not the pinned one", "the trailer's CRC-32 is not the body's"};
     return text[cls < WIRE_IN_CLASSES ? cls : 0];
 }
-// host_slots: the host form's staged BINCODE slots (B * plan.pitch bytes), which go up behind the tables; else d_bytes is the caller's
-static int import_wire_and_wait(acvm_batch *b, const WireInPlan &plan, const void *d_bytes, const uint64_t *d_lengths, const std::vector<uint8_t> *host_slots) {
+// host_slots: the host form's staged BINCODE slots (B * plan.pitch bytes), which go up behind the tables; else d_bytes is the caller's.
+// front: the bytes at the arena's start that are the caller's (the gzip import's scratch, which d_bytes and d_lengths then lie in: that caller
+// has reserved front + wire_in_arena_bytes already, so the reservation here moves nothing).
+static size_t wire_in_arena_bytes(const WireInPlan &plan, uint32_t B, size_t host_slot_bytes) {
+    return align256(plan.keys.size() * 4) + align256(plan.positions.size() * 4) + align256(plan.crc_pow.size() * 4) +
+           align256(plan.container == ACVM_WIRE_GZIP_STORED ? (size_t)B * 4 : 0) + align256(host_slot_bytes);
+}
+static int import_wire_and_wait(acvm_batch *b, const WireInPlan &plan, const void *d_bytes, const uint64_t *d_lengths, const std::vector<uint8_t> *host_slots,
+                                size_t front = 0) {
     HIPCHK(hipSetDevice(b->device));
     if (int rc = missing_set_ready(b)) return rc;  // (in front of everything: a refusal so far leaves the handle as it was)
     const bool gzip = plan.container == ACVM_WIRE_GZIP_STORED;
-    // the arena: [keys][positions][crc powers][crc words][host form: slots]
-    size_t at = 0;
+    // the arena: [the caller's front][keys][positions][crc powers][crc words][host form: slots]
+    size_t at = front;
     auto carve = [&](size_t n_bytes) { const size_t begin = at; at += align256(n_bytes); return begin; };
     const size_t at_keys = carve(plan.keys.size() * 4), at_positions = carve(plan.positions.size() * 4), at_pow = carve(plan.crc_pow.size() * 4);
     const size_t at_crc = carve(gzip ? (size_t)b->B * 4 : 0), at_slots = carve(host_slots ? host_slots->size() : 0);
@@ -375,6 +384,115 @@ int acvm_batch_set_initial_witness_maps_wire(acvm_batch_t *b, const uint8_t *byt
         memcpy(&slots[(size_t)j * plan.pitch], row, len);
     }
     return import_wire_and_wait(b, plan, nullptr, nullptr, &slots);
+} ABI_CATCH
+
+// ---- the gzip import (include/acvm_amd.h acvm_batch_import_device_wire_gzip). Stage 1: kernels_wire_inflate.hip inflates every row into the
+// arena's scratch and writes nothing of the handle; its two result words come back behind the one wait between the stages, and any finding
+// ends the call with the handle as it was. Stage 2 is the body import above over the scratch, the inflater's lengths its d_lengths. The arena
+// is reserved ONCE for both (wire_inflate_plan.hpp): a second reservation that grew it would free the scratch under stage 2.
+static const char *inflate_class_text(uint32_t cls) {
+    static const char *const text[INFLATE_CLASSES] = {"", "the head is not a gzip head", "block type 3", "a stored block's LEN is not ~NLEN", "a dynamic block's code description is invalid",
+                                                      "bits that are no symbol of the block's code", "a distance beyond the bytes written", "the readable bytes end inside the member",
+                                                      "more output than the handle's longest body", "the trailer's CRC-32 is not the output's", "the trailer's ISIZE is not the output's length"};
+    return text[cls < INFLATE_CLASSES ? cls : 0];
+}
+// device: bytes / lengths are the caller's device memory; else host rows at `pitch`, staged compressed
+static int import_wire_gzip(acvm_batch *b, const acvm_wire_in_desc_t *d, const void *bytes, const uint64_t *lengths, bool device) {
+    uint64_t longest = 0;
+    // (the host form's rows are looked at before the plan is made: it wants the longest of them. A pitch the plan will refuse is not walked.)
+    if (!device && b && d && bytes && (unsigned __int128)b->B * d->pitch <= ((unsigned __int128)1 << 57)) {
+        if (b->B && !lengths) return set_err(ACVM_E_INVALID, "null lengths");
+        for (uint32_t j = 0; j < b->B; j++) {
+            const uint8_t *row = (const uint8_t *)bytes + (size_t)j * d->pitch;
+            const uint64_t n = std::min<uint64_t>(lengths[j], d->pitch);
+            if (n < 2 || row[0] != 0x1f || row[1] != 0x8b) return set_err(ACVM_E_INVALID, "instance " + std::to_string(j) + ": the row does not start 1f 8b");
+            longest = std::max(longest, n);
+        }
+    }
+    WireInflatePlan plan;
+    {
+        std::string err;
+        const int rc = wire_inflate_plan(b ? &b->B : nullptr, b ? b->plan().initial_ids.data() : nullptr, b ? (uint32_t)b->plan().initial_ids.size() : 0u, d, bytes, device,
+                                         longest, &plan, &err);
+        if (rc) return set_err(rc, err);
+    }
+    if (!b->B) return import_wire_and_wait(b, plan.body, nullptr, nullptr, nullptr);
+    HIPCHK(hipSetDevice(b->device));
+    if (int rc = missing_set_ready(b)) return rc;
+    if (int rc = stage_reserve(b, plan.front + wire_in_arena_bytes(plan.body, b->B, 0))) return rc;
+    hipStream_t s = b->stream;
+    uint8_t *arena = b->d_stage;
+    std::vector<uint8_t> staged;
+    std::vector<uint64_t> staged_lengths;
+    HIPCHK(hipMemsetAsync(arena + plan.at_result, 0, 16, s));
+    HIPCHK(hipMemcpyAsync(arena + plan.at_fixed, plan.fixed.data(), plan.fixed.size() * 2, hipMemcpyHostToDevice, s));
+    if (!device) {  // the rows as they are, compressed, at the staged pitch; their readable lengths beside them
+        staged.assign((size_t)b->B * plan.pitch, 0);
+        staged_lengths.resize(b->B);
+        for (uint32_t j = 0; j < b->B; j++) {
+            staged_lengths[j] = std::min<uint64_t>(lengths[j], d->pitch);
+            memcpy(&staged[(size_t)j * plan.pitch], (const uint8_t *)bytes + (size_t)j * d->pitch, (size_t)staged_lengths[j]);
+        }
+        HIPCHK(hipMemcpyAsync(arena + plan.at_rows, staged.data(), staged.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(arena + plan.at_row_lengths, staged_lengths.data(), staged_lengths.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    uint64_t *d_body_lengths = (uint64_t *)(arena + plan.at_lengths);
+    const WireInflate x{device ? (const uint8_t *)bytes : arena + plan.at_rows, plan.pitch, device ? lengths : (const uint64_t *)(arena + plan.at_row_lengths), b->B,
+                        arena + plan.at_scratch, plan.out_pitch, plan.out_cap, (uint32_t *)(arena + plan.at_tables), d_body_lengths, (uint32_t *)(arena + plan.at_findings), nullptr,
+                        (const uint16_t *)(arena + plan.at_fixed), (uint64_t *)(arena + plan.at_result)};
+    launch_wire_inflate(s, x);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b->h_mask_result, arena + plan.at_result, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (the one wait between the stages; also what keeps the staged rows alive for their copy)
+    const uint64_t n_findings = b->h_mask_result[0], key = b->h_mask_result[1];
+    if (n_findings) {
+        const uint32_t cls = inflate_key_class(key);
+        return set_err(ACVM_E_INVALID, "wire inflate: " + std::to_string(n_findings) + " findings, the first of them instance " + std::to_string(inflate_key_instance(key)) + ", class " +
+                                           std::to_string(cls) + " (" + inflate_class_text(cls) + "), block " + std::to_string(inflate_key_block(key)) + "; the handle stays as it was");
+    }
+    return import_wire_and_wait(b, plan.body, arena + plan.at_scratch, d_body_lengths, nullptr, plan.front);
+}
+int acvm_batch_import_device_wire_gzip(acvm_batch_t *b, const acvm_wire_in_desc_t *d, const void *d_bytes, const uint64_t *d_lengths) try {
+    return import_wire_gzip(b, d, d_bytes, d_lengths, true);
+} ABI_CATCH
+int acvm_batch_set_initial_witness_maps_gzip(acvm_batch_t *b, const uint8_t *bytes, uint64_t pitch, const uint64_t *lengths) try {
+    const acvm_wire_in_desc_t d{ACVM_WIRE_GZIP_DEFLATE, pitch};
+    return import_wire_gzip(b, &d, bytes, lengths, false);
+} ABI_CATCH
+// The shipped inflater through its launcher on rows of the caller's, no handle (include/acvm_amd.h). The device's output starts as the caller's
+// `out`, so that what the kernel leaves alone comes back as it went in.
+int acvm_debug_inflate_rows(const uint8_t *rows, uint64_t pitch, const uint64_t *lengths, uint32_t n, uint64_t out_cap, uint8_t *out, uint64_t *out_lengths,
+                            uint32_t *findings, uint32_t *crcs) try {
+    if (n && (!rows || (!out && out_cap) || !out_lengths || !findings)) return set_err(ACVM_E_INVALID, "null argument");
+    if (n && !pitch) return set_err(ACVM_E_INVALID, "pitch 0");
+    if (out_cap % 4) return set_err(ACVM_E_INVALID, "out_cap " + std::to_string(out_cap) + " is not a multiple of 4");
+    if ((unsigned __int128)n * pitch > ((unsigned __int128)1 << 40) || (unsigned __int128)n * out_cap > ((unsigned __int128)1 << 40)) return set_err(ACVM_E_INVALID, "too large for this probe");
+    if (!n) return 0;
+    struct Mem {
+        void *p[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Mem() {
+            for (void *q : p)
+                if (q) hipFree(q);
+        }
+    } m;
+    const std::vector<uint16_t> fixed = wire_inflate_fixed_tables();
+    const size_t in_bytes = (size_t)n * pitch, out_bytes = (size_t)n * out_cap;
+    const size_t sizes[8] = {in_bytes, (size_t)n * 8, out_bytes ? out_bytes : 4, (size_t)n * 8, (size_t)n * 8, (size_t)n * 4, fixed.size() * 2, (size_t)n * INFLATE_PLAN_ROW_WORDS * 4};
+    for (int k = 0; k < 8; k++) HIPCHK(hipMalloc(&m.p[k], sizes[k]));
+    HIPCHK(hipMemcpy(m.p[0], rows, in_bytes, hipMemcpyHostToDevice));
+    if (lengths) HIPCHK(hipMemcpy(m.p[1], lengths, (size_t)n * 8, hipMemcpyHostToDevice));
+    if (out_bytes) HIPCHK(hipMemcpy(m.p[2], out, out_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m.p[6], fixed.data(), fixed.size() * 2, hipMemcpyHostToDevice));
+    const WireInflate x{(const uint8_t *)m.p[0], pitch, lengths ? (const uint64_t *)m.p[1] : nullptr, n, (uint8_t *)m.p[2], out_cap, out_cap, (uint32_t *)m.p[7], (uint64_t *)m.p[3], (uint32_t *)m.p[4],
+                        (uint32_t *)m.p[5], (const uint16_t *)m.p[6], nullptr};
+    launch_wire_inflate(nullptr, x);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (out_bytes) HIPCHK(hipMemcpy(out, m.p[2], out_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_lengths, m.p[3], (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(findings, m.p[4], (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (crcs) HIPCHK(hipMemcpy(crcs, m.p[5], (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
 } ABI_CATCH
 
 // What the last import left (include/acvm_amd.h): rows, planes, event words and missing set of the live instances, for the tests that compare two

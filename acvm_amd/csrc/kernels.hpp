@@ -237,6 +237,24 @@ struct WireImport {
     uint64_t *result;
 };
 bool launch_wire_import(hipStream_t s, const WireImport &x, uint32_t n_windows);
+// ---- kernels_wire_inflate.hip (acvm_batch_import_device_wire_gzip, stage 1): row j's gzip member in [in + j * pitch, + min(lengths[j], pitch))
+// (lengths null: pitch) inflated into out + j * out_pitch (a multiple of 4; at most out_cap bytes, nothing at or behind the row's length is
+// written). tables: n x INFLATE_PLAN_ROW_WORDS dwords of scratch for the rows' code tables. out_lengths: n words; findings: n x {class, block} (wire_inflate.hpp); crcs: n words or null; fixed: wire_inflate_plan.hpp's
+// table; result: null, or two words, zero before the call -- the findings' count and the smallest inflate_key.
+struct WireInflate {
+    const uint8_t *in;
+    uint64_t pitch;
+    const uint64_t *lengths;
+    uint32_t n;
+    uint8_t *out;
+    uint64_t out_pitch, out_cap;
+    uint32_t *tables;
+    uint64_t *out_lengths;
+    uint32_t *findings, *crcs;
+    const uint16_t *fixed;
+    uint64_t *result;
+};
+void launch_wire_inflate(hipStream_t s, const WireInflate &x);
 // ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
 // {status, err, opcode index, index in the range} over them; any column may be null
 void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);

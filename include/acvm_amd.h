@@ -1016,8 +1016,7 @@ long long acvm_batch_witness_map_bytes(acvm_batch_t *b, uint32_t instance, uint8
  *     rounded up to 16: about 0.72 of the stored container's. d_lengths[i] is the member's length; a row that names no instance is a map of
  *     0 entries, 63 bytes. Descriptor, pitch and alignment rule, states, refusals, what is never written or loaded and the host-to-device
  *     traffic (the plan's tables, 1 384 bytes of code table among them) are the other containers'. The position inside a row is 64-bit.
- * Not here: a node form, an asynchronous variant, inflating ACVM_WIRE_GZIP_DEFLATE on the device (the host import inflates any deflate
- * stream), a packed output with an offsets column instead of a pitch, adaptive codes or longer match distances, any change to
+ * Not here: a node form, an asynchronous variant (the way back in is acvm_batch_import_device_wire_gzip, below), a packed output with an offsets column instead of a pitch, adaptive codes or longer match distances, any change to
  * acvm_batch_witness_map_bytes. A body of 4 GiB or more wraps ISIZE as gzip defines it.
  */
 enum { ACVM_WIRE_BINCODE = 0,        /* the bincode body alone */
@@ -1079,7 +1078,8 @@ int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uin
  * trailing bytes -- a key that is not an initial witness, or a map with more entries than fit is refused before anything is enqueued, the
  * message naming the instance and the reader's text; the handle stays as it was. Then the bodies go through the staging buffer as
  * ACVM_WIRE_BINCODE slots and the device path runs.
- * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant, inflating compressed deflate on the device, keys
+ * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant (compressed deflate is inflated on the device by
+ * acvm_batch_import_device_wire_gzip, below; these two calls are as they were), keys
  * outside the handle's initial id set (the reference's ACVM::new would take them; here the plan is keyed by the initial ids), a per-row offset
  * column instead of a pitch.
  */
@@ -1091,6 +1091,58 @@ int acvm_batch_import_device_wire(acvm_batch_t *b, const acvm_wire_in_desc_t *d,
                                   const uint64_t *d_lengths /* DEVICE [B] or NULL */);
 int acvm_batch_set_initial_witness_maps_wire(acvm_batch_t *b, const uint8_t *bytes /* host */, uint64_t pitch /* any */,
                                              const uint64_t *lengths /* host [B], required */);
+/*
+ * The gzip import: every instance's map as one gzip member (RFC 1952) around its bincode body, INFLATED ON THE DEVICE -- one row per lane, every
+ * row of the batch in flight together. What acvm_batch_witness_maps_wire_device(ACVM_WIRE_GZIP_DEFLATE) or (ACVM_WIRE_GZIP_STORED) left in device
+ * memory is this call's input with no pass in between, and so is what compressWitness writes (GzEncoder, Compression::best(): dynamic-Huffman
+ * blocks, witness_map.rs:109-146) or any other deflater: the inflater reads every RFC 1951 stream.
+ *   - The slot at d_bytes + j * pitch holds instance j's member; row j reads only bytes [0, min(d_lengths[j], pitch)) of its slot (NULL
+ *     lengths: pitch). Any mix and number of stored, fixed and dynamic blocks, distances up to 32 768. FLG may carry FEXTRA, FNAME, FCOMMENT
+ *     and FHCRC (checked as zlib checks it); MTIME, XFL and OS are not looked at; bytes behind the trailer are ignored, as GzDecoder ignores
+ *     them. The acceptance rules are zlib's.
+ *   - The inflated body must be a canonical body of the handle: it is read as an ACVM_WIRE_BINCODE slot by acvm_batch_import_device_wire's
+ *     kernels, the inflater's own output length serving as that row's d_lengths -- so trailing body bytes are a class-1 finding there. When every
+ *     row passes the handle is left bit for bit as acvm_batch_import_device_wire(ACVM_WIRE_BINCODE) leaves it for the same bodies.
+ *   - Two stages with one host synchronisation between them. Stage 1 inflates into scratch and writes nothing of the handle. Its findings are a
+ *     class space of their own; a row's reader is sequential and stops at its first, so a row has at most one, and with it goes the number of
+ *     block headers read so far (0 inside the head):
+ *       1  HEAD      bytes 0..2 are not 1f 8b 08; a reserved FLG bit is set; FHCRC is not the header's CRC-32 mod 2^16
+ *       2  BLOCK     BTYPE 3
+ *       3  STORED    LEN is not ~NLEN
+ *       4  CODES     a dynamic block's description that zlib refuses: HLIT > 29 or HDIST > 29; a code-length code that is over-subscribed or
+ *                    incomplete; repeat 16 with no length before it; a repeat past HLIT + HDIST + 258; symbol 256 without a code; a
+ *                    literal/length or distance set that is over-subscribed, or incomplete unless its longest code has 1 bit (an all-zero
+ *                    distance set is legal)
+ *       5  SYMBOL    bits that are no code of an incomplete set; literal/length symbols 286 / 287; distance symbols 30 / 31
+ *       6  DISTANCE  a distance beyond the bytes written so far
+ *       7  INPUT     the row's readable bytes end before the head, the final block or the 8 trailer bytes do
+ *       8  OUTPUT    more output than the handle's longest body, 8 + 76 * n_initial
+ *       9  CRC       the trailer's CRC-32 is not the output's
+ *       10 ISIZE     the trailer's ISIZE is not the output's length mod 2^32 (checked after the CRC, as zlib does)
+ *     Any of them is ACVM_E_INVALID: the message ("wire inflate: ...") gives the number of findings and the smallest (instance, class, block),
+ *     and the handle stays AS IT WAS -- a previous import still solves. Stage 2 is the body import over the scratch; its findings, its message
+ *     ("wire import: ...") and its "left without initial witnesses" rule are acvm_batch_import_device_wire's.
+ *   - Refused on the host with ACVM_E_INVALID, nothing enqueued, the handle as it was: a null batch or descriptor; a container other than
+ *     ACVM_WIRE_GZIP_DEFLATE; a pitch that is 0 or not a multiple of 16; a misaligned d_bytes; a null buffer with B > 0; more than 2^27 instances.
+ *   - Host-to-device traffic: the body import's tables and 736 bytes of fixed code table; nothing per instance either way. The staging arena
+ *     holds the scratch slots (the handle's longest body each, rounded up to 16) and 900 bytes of code tables per instance. Synchronous.
+ * acvm_batch_set_initial_witness_maps_gzip is the host form: row j is bytes[j * pitch, + lengths[j]), pitch and alignment of any kind. The rows go up
+ * as they are, COMPRESSED, at a 16-aligned pitch, then the device form runs: no host thread inflates anything. Also refused on the host: null
+ * lengths, a row that does not start 1f 8b. A body that is not in canonical shape is a finding here;
+ * acvm_batch_set_initial_witness_maps_wire, which inflates on the host and rewrites such bodies, remains the route for those.
+ * acvm_debug_inflate_rows runs the shipped inflater through its launcher on n rows of the caller's, no handle: bytes that need not be witness
+ * maps. out ([n][out_cap], out_cap a multiple of 4) goes up as it is and comes back with row i's bytes in front, so what the kernel leaves
+ * alone is seen to be left alone; out_lengths[i] the bytes stored, findings[2 i], [2 i + 1] the class (0: none) and the block count, crcs
+ * (may be NULL) the CRC-32 of the bytes stored. lengths may be NULL (pitch).
+ * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant, raw-deflate or zlib wrappers, multi-member files,
+ * bodies outside canonical shape on the device, parallel decoding within one row.
+ */
+int acvm_batch_import_device_wire_gzip(acvm_batch_t *b, const acvm_wire_in_desc_t *d /* container must be ACVM_WIRE_GZIP_DEFLATE */,
+                                       const void *d_bytes /* DEVICE, 16-byte aligned */, const uint64_t *d_lengths /* DEVICE [B] or NULL */);
+int acvm_batch_set_initial_witness_maps_gzip(acvm_batch_t *b, const uint8_t *bytes /* host */, uint64_t pitch /* any */,
+                                             const uint64_t *lengths /* host [B], required */);
+int acvm_debug_inflate_rows(const uint8_t *rows /* host */, uint64_t pitch, const uint64_t *lengths, uint32_t n, uint64_t out_cap,
+                            uint8_t *out /* host [n][out_cap] */, uint64_t *out_lengths, uint32_t *findings /* [n][2]: class, block */, uint32_t *crcs);
 
 
 /*
