@@ -61,7 +61,7 @@ ABI_SYMBOLS = [
     "acvm_debug_lin_add", "acvm_debug_lin_plan", "acvm_debug_bundle_plan",
     "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
     "acvm_batch_import_device_wire_gzip", "acvm_batch_set_initial_witness_maps_gzip", "acvm_debug_inflate_rows",
-    "acvm_debug_gate_records",
+    "acvm_debug_gate_records", "acvm_debug_record_scratch",
 ]
 
 
@@ -534,6 +534,7 @@ def lib():
     L.acvm_circuit_plan_stats_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(Stats)]
     L.acvm_debug_plan_fingerprint.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32]
     L.acvm_debug_gate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.acvm_debug_record_scratch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.acvm_circuit_plans_built.restype = C.c_uint64
     L.acvm_circuit_plans_built.argtypes = [C.c_void_p]
     L.acvm_circuit_check_schedule.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
@@ -1133,6 +1134,18 @@ class Circuit:
 
     GATE_KINDS = ("ASSERT", "SOLVE", "SOLVE_DYN")
     GATE_OUT_MODES = ("ASIS", "WEAK", "CANON")
+
+    def record_scratch(self, initial_ids, fold_digest=False, reuse_slots=False, keep=()) -> list:
+        """Host-only: the per-lane scratch words the static plan reserves for each opcode's record, in program order (acvm_debug_record_scratch)"""
+        ids = list(initial_ids)
+        arr = (C.c_uint32 * max(len(ids), 1))(*ids)
+        keep = list(keep)
+        karr = (C.c_uint32 * max(len(keep), 1))(*keep)
+        flags = (1 if fold_digest else 0) | (2 if reuse_slots else 0)
+        n = _check(lib().acvm_debug_record_scratch(self._h, arr, len(ids), flags, karr, len(keep), None, 0))
+        out = (C.c_uint32 * max(n, 1))()
+        assert _check(lib().acvm_debug_record_scratch(self._h, arr, len(ids), flags, karr, len(keep), out, n)) == n
+        return list(out[:n])
 
     def gate_records(self, initial_ids, fold_digest=False, reuse_slots=False, keep=()) -> list:
         """Host-only: the gate records of the static plan in stream order (acvm_debug_gate_records), decoded after csrc/gate_record.hpp. One dict per

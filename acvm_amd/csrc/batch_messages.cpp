@@ -23,12 +23,13 @@ void format_message(acvm_batch *b, uint32_t j, const SlowResult &sr, acvm_result
     switch (sr.msg) {
     case 1: snprintf(r.message, sizeof r.message, "Mul term in the arithmetic opcode must contain either zero or one term"); break;
     case 2: snprintf(r.message, sizeof r.message, "number of bits specified for each input must be the same"); break;
-    case 3: snprintf(r.message, sizeof r.message, "fetch_nearest_bytes: range end index out of range"); break;
+    // the slice panic of fetch_nearest_bytes (generic_ark.rs:316) on the first input wider than 256 bits: x0 is its num_bits, the end index its byte count as a usize
+    case 3: snprintf(r.message, sizeof r.message, "range end index %llu out of range for slice of length 32", ((unsigned long long)sr.x0 + 7) / 8); break;
     case 4: snprintf(r.message, sizeof r.message, "Expected 32 outputs but encountered %u", sr.x0); break;
     case 5: {
         unsigned long long len = 0;
         if (rec && rec[0] == PK_HASH)
-            for (uint32_t i = 0; i < rec[3]; i++) len += (rec[6 + 2 * i + 1] + 7) / 8;
+            for (uint32_t i = 0; i < rec[3]; i++) len += ((unsigned long long)rec[6 + 2 * i + 1] + 7) / 8;
         snprintf(r.message, sizeof r.message,
                  "the number of bytes to take from the message is more than the number of bytes in the message. %llu > %llu",
                  (unsigned long long)sr.x1 << 32 | sr.x0, len);

@@ -71,6 +71,9 @@ __device__ __forceinline__ Fr digest_to_field(const Digest &d) {
 // (3 SHA256, 4 Blake2s, 7 HashToField128Security, 11 Keccak256, 12 Keccak256VariableLength), | HASH_COOP_FLAG when every input is one
 // byte wide, the function is 3, 4 or 11, n_out == 32 and 1 <= n_in <= 1024 (plan.cpp)
 static constexpr uint32_t HASH_COOP_FLAG = 0x100u;
+// bytes an input of num_bits contributes: ceil(num_bits / 8), which the reference forms in a usize -- a width near 2^32 must not wrap to a
+// few bytes; every width above 256 answers 33 (the slice panic of fetch_nearest_bytes)
+__device__ __forceinline__ uint32_t hash_input_bytes(uint32_t num_bits) { return num_bits > 256u ? 33u : (num_bits + 7u) / 8u; }
 static constexpr uint32_t HASH_CHAIN_FLAG = 0x400u;  // level-schedule copy of the record: one more word behind it, the offset of the link to the record that hashes this digest (kernels_hash.hip)
 static constexpr uint32_t HASH_RANGE_FLAG = 0x200u;  // level-schedule copy of the record: (RANGE opcode or NONE, bits) x n_in behind the outputs
 template <class P>
@@ -86,11 +89,11 @@ __device__ __forceinline__ OpResult op_hash(const P &p, const uint32_t *__restri
     MsgBuf m{scratch, p.scratch_stride(), p.scratch_lane(), 0u, 0u};
     m.begin();
     for (uint32_t i = 0; i < n_in;) {
-        const uint32_t nb = (ins[2 * i + 1] + 7u) / 8u;
-        if (nb > 32u) return op_fail_msg(DE_PANIC, 0, DM_FETCH_BYTES);  // slice end out of range (generic_ark.rs:316)
+        const uint32_t nb = hash_input_bytes(ins[2 * i + 1]);
+        if (nb > 32u) return op_fail_msg(DE_PANIC, 0, DM_FETCH_BYTES, ins[2 * i + 1]);  // slice end out of range (generic_ark.rs:316); the host prints the width's byte count
         // byte arrays, four witnesses at a time: four rows in flight and four independent reductions for the one wave a SIMD
         // holds at these batch sizes; only the low limb of each canonical value is formed (fr29_redc_low)
-        if (nb == 1u && i + 4u <= n_in && (ins[2 * i + 3] + 7u) / 8u == 1u && (ins[2 * i + 5] + 7u) / 8u == 1u && (ins[2 * i + 7] + 7u) / 8u == 1u) {
+        if (nb == 1u && i + 4u <= n_in && hash_input_bytes(ins[2 * i + 3]) == 1u && hash_input_bytes(ins[2 * i + 5]) == 1u && hash_input_bytes(ins[2 * i + 7]) == 1u) {
             const Fr a0 = p.load(ins[2 * i]), a1 = p.load(ins[2 * i + 2]), a2 = p.load(ins[2 * i + 4]), a3 = p.load(ins[2 * i + 6]);
             bool b0, b1, b2, b3;
             const uint32_t l0 = fr_low_limb(a0, b0), l1 = fr_low_limb(a1, b1), l2 = fr_low_limb(a2, b2), l3 = fr_low_limb(a3, b3);

@@ -655,7 +655,7 @@ struct Planner {
                     // [PK_HASH, oi, func (| PLAN_HASH_COOP_FLAG), n_in, n_out, var_w (or NONE), (w, num_bits) x n_in, (out, flag) x n_out]
                     p.prog_class[oi] = CLS_HASH;
                     uint64_t bytes = 0;
-                    for (auto &in : b.in[0]) bytes += std::min<uint32_t>((in.num_bits + 7) / 8, 32);
+                    for (auto &in : b.in[0]) bytes += in.num_bits > 256 ? 32u : (in.num_bits + 7) / 8;  // (no 32-bit wrap for widths near 2^32)
                     if (bytes > (1u << 24)) { unsupported(oi, "hash input above 16 MiB"); }
                     p.prog_scratch[oi] = (uint32_t)((bytes + 3) / 4 + 1);
                     // byte messages (every input one byte wide) of the three plain hashes: the level kernel unpacks them with four
@@ -663,6 +663,10 @@ struct Planner {
                     bool coop = (b.func == BB_SHA256 || b.func == BB_BLAKE2S || b.func == BB_KECCAK256) && b.out.size() == 32 &&
                                 !b.in[0].empty() && b.in[0].size() <= PLAN_HASH_COOP_MAX_BYTES;
                     for (auto &in : b.in[0]) coop = coop && in.num_bits >= 1 && in.num_bits <= 8;
+                    // one witness twice among the outputs: the second occurrence COMPARES with what the first stored (write_digest_to_outputs goes
+                    // in order), and the cooperative kernel's waves store and compare side by side -- such a record takes the lane kernel
+                    for (size_t i = 0; coop && i < b.out.size(); i++)
+                        for (size_t k = 0; k < i; k++) coop = coop && b.out[i] != b.out[k];
                     s.insert(s.end(), {PK_HASH, oi, b.func | (coop ? PLAN_HASH_COOP_FLAG : 0u), (uint32_t)b.in[0].size(), (uint32_t)b.out.size(),
                                        b.func == BB_KECCAK256_VAR ? b.in[1][0].witness : 0xFFFFFFFFu});
                     for (auto &in : b.in[0]) { s.push_back(in.witness); s.push_back(in.num_bits); }
@@ -762,9 +766,17 @@ struct Planner {
                     uint32_t lg = 0;
                     while ((1u << lg) < n) lg++;
                     p.prog_scratch[oi] = 8 * n * d.tuple + 4 * n + n * (lg + 1) + 1 + 3 * 72 + (4 * n + 8) * (lg + 2) + 64;
-                    s.insert(s.end(), {PK_PERM_SORT, oi, n, d.tuple, (uint32_t)d.sort_by.size(), (uint32_t)d.bw.size()});
+                    // bits.iter().zip(control) (directives/mod.rs:115): a bit witness past the network's switches is never touched, so it is no
+                    // output of the record -- listed as one, the level schedule would hand it out as assigned
+                    uint64_t n_switches = 0;  // sum of ceil(log2 i) for i = 1 .. n (sorting.rs route)
+                    for (uint32_t i = 1, l = 0; i <= n; i++) {
+                        while ((1u << l) < i) l++;
+                        n_switches += l;
+                    }
+                    const uint32_t n_bits = (uint32_t)std::min<uint64_t>(d.bw.size(), n_switches);
+                    s.insert(s.end(), {PK_PERM_SORT, oi, n, d.tuple, (uint32_t)d.sort_by.size(), n_bits});
                     s.insert(s.end(), d.sort_by.begin(), d.sort_by.end());
-                    for (uint32_t w : d.bw) out(w);
+                    for (uint32_t k = 0; k < n_bits; k++) out(d.bw[k]);
                     for (auto &el : d.sort_inputs)
                         for (auto &ex : el) emit_expr(s, pool, ex);
                 }

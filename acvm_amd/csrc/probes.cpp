@@ -458,6 +458,26 @@ int acvm_debug_gate_records(const acvm_circuit_t *c, const uint32_t *initial_ids
     return (int)total;
 } ABI_CATCH
 
+// Host-only: the per-lane scratch words the plan reserves for each opcode's record (Plan::prog_scratch: hash messages, the working memory of
+// Directive::PermutationSort, Schnorr's preimage and window table, the Brillig VM), one word per opcode in program order, 0 where the record takes
+// none. tests/test_sort_cases.py holds the reservation of a sort against the allocation walk of ops_sort.hpp. Returns the number of opcodes and writes
+// the first min(that, cap) words (out may be null with cap = 0).
+int acvm_debug_record_scratch(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids, uint32_t n_keep,
+                              uint32_t *out, uint32_t cap) try {
+    if (!c || (n_initial && !initial_ids) || (n_keep && !keep_ids) || (cap && !out)) return set_err(ACVM_E_INVALID, "null argument");
+    PlanOpts opts;
+    opts.fold_digest = (flags & (ACVM_BATCH_FOLD_DIGEST | ACVM_BATCH_REUSE_SLOTS)) != 0;
+    opts.reuse_slots = (flags & ACVM_BATCH_REUSE_SLOTS) != 0;
+    opts.host_blackbox = (flags & 0x100u) != 0;
+    opts.keep.assign(keep_ids, keep_ids + n_keep);
+    const std::shared_ptr<const Plan> sp = plan_for(c, initial_ids, n_initial, opts);
+    const Plan &p = *sp;
+    if (!p.unsupported.empty()) return set_err(ACVM_E_UNSUPPORTED, p.unsupported);
+    if (p.prog_scratch.size() > 0x7FFFFFFFull) return set_err(ACVM_E_INVALID, "too many opcodes for this probe");
+    if (cap) memcpy(out, p.prog_scratch.data(), std::min<size_t>(p.prog_scratch.size(), cap) * 4);
+    return (int)p.prog_scratch.size();
+} ABI_CATCH
+
 // The shipped selection kernels through their launcher on a status array of the caller's (kernels_select.hip launch_select). The device's list starts as the
 // caller's out_list, so that what the kernels leave alone comes back as it went in.
 int acvm_debug_select(const uint8_t *status, uint32_t n, uint32_t select_mask, uint32_t *out_list, uint32_t *n_selected) try {

@@ -359,6 +359,11 @@ int acvm_debug_plan_fingerprint(const acvm_circuit_t *c, const uint32_t *initial
  * min(that, cap) of them (out may be NULL with cap = 0). */
 int acvm_debug_gate_records(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids,
                             uint32_t n_keep, uint32_t *out, uint32_t cap);
+/* Host-only: the per-lane scratch words the same plan reserves for the record of each opcode (hash messages, the working memory of
+ * Directive::PermutationSort, Schnorr's preimage, the Brillig VM), one word per opcode in program order, 0 where a record takes none. Returns the
+ * number of opcodes and writes the first min(that, cap) words (out may be NULL with cap = 0). */
+int acvm_debug_record_scratch(const acvm_circuit_t *c, const uint32_t *initial_ids, uint32_t n_initial, uint32_t flags, const uint32_t *keep_ids,
+                              uint32_t n_keep, uint32_t *out, uint32_t cap);
 /*
  * ACVM::new for n_instances instances that all assign the same initial witness ids.
  * The circuit is levelised once against that set. `solver` may be NULL (built-in HIP backend).

@@ -254,6 +254,7 @@ int fr_try_to_u64(const fr_t *a, uint64_t *v) {
     return 1;
 }
 int fr_fetch_nearest_bytes(const fr_t *a, uint32_t num_bits, uint8_t out[32]) {
+    if (num_bits > 256) return -1; /* before the byte count is formed: (num_bits + 7) / 8 must not wrap in 32 bits */
     uint32_t n = (num_bits + 7) / 8;
     if (n > 32) return -1; /* reference: slice index out of range panic */
     uint64_t c[4];

@@ -245,7 +245,13 @@ static int get_hash_input(oracle_acvm_t *a, const bb_call_t *b, int var_len, uin
         fr_t v;
         if (witness_to_value(a, b->in[0][i].witness, &v)) { free(m); return 1; }
         int n = fr_fetch_nearest_bytes(&v, b->in[0][i].num_bits, m + len);
-        if (n < 0) { free(m); pwg_fail(a, E_PANIC, 0, 0, "fetch_nearest_bytes: range end index out of range"); return 1; }
+        if (n < 0) { /* bytes[0..num_elements] on a Vec of 32 (generic_ark.rs:316), num_elements formed in a usize */
+            char msg[96];
+            snprintf(msg, sizeof msg, "range end index %llu out of range for slice of length 32", ((unsigned long long)b->in[0][i].num_bits + 7) / 8);
+            free(m);
+            pwg_fail(a, E_PANIC, 0, 0, msg);
+            return 1;
+        }
         len += (size_t)n;
     }
     if (var_len) {

@@ -88,4 +88,6 @@ def test_fetch_nearest_bytes(oracle):
         got = oracle.lib().oracle_fr_fetch_nearest_bytes(be(x), bits, out)
         assert got == n
         assert out.raw[:n] == x.to_bytes(32, "little")[:n]
-    assert oracle.lib().oracle_fr_fetch_nearest_bytes(be(x), 257, out) == -1  # reference: slice panic
+    # reference: slice panic for every width above 256 -- the byte count is formed in a usize, so the widths whose (bits + 7) wraps in 32 bits panic too
+    for bits in (257, 300, 1 << 31, 0xFFFFFFF8, 0xFFFFFFF9, 0xFFFFFFFF):
+        assert oracle.lib().oracle_fr_fetch_nearest_bytes(be(x), bits, out) == -1, hex(bits)
