@@ -20,7 +20,11 @@
 #               bound of its deflating container: tools/asan/wire_deflate_plan_host_test (tests/test_wire_deflate_plan_on_host.py), and the
 #               gzip import: its checks, arena layout and fixed-code tables: tools/asan/wire_inflate_plan_host_test
 #               (tests/test_wire_inflate_plan_on_host.py), and the per-row inflater the kernel runs, on the host over untrusted rows in heap blocks
-#               of exactly their bounds: tools/asan/wire_inflate_host_test (hipcc, host side sanitized; tests/test_wire_inflate_on_host.py)
+#               of exactly their bounds: tools/asan/wire_inflate_host_test (hipcc, host side sanitized; tests/test_wire_inflate_on_host.py), and the
+#               decisions of the Brillig retry loop -- continue, restart or final, the next pass's limits, columns and bytes:
+#               tools/asan/brillig_retry_plan_host_test (tests/test_brillig_retry_plan_on_host.py), and the checkpoint record, the scratch's index
+#               functions and the relocation run on host arrays of exactly their sizes: tools/asan/brillig_resume_host_test (hipcc, host side
+#               sanitized; tests/test_brillig_resume_on_host.py)
 CXX ?= g++
 ASAN_FLAGS = -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wno-sign-compare
 ASAN_SRCS = tools/asan/fuzz_driver.cpp acvm_amd/csrc/circuit.cpp acvm_amd/csrc/plan.cpp acvm_amd/csrc/tuning.cpp acvm_amd/csrc/schedule.cpp acvm_amd/csrc/schedule_check.cpp
@@ -41,7 +45,8 @@ HIPCC ?= /opt/rocm/bin/hipcc
 asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigned_view_host_test tools/asan/node_io_plan_host_test tools/asan/foreign_plan_host_test \
       tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test tools/asan/import_mask_host_test \
       tools/asan/record_plan_host_test tools/asan/record_out_plan_host_test tools/asan/record_mask_plan_host_test tools/asan/wire_plan_host_test \
-      tools/asan/wire_in_plan_host_test tools/asan/wire_deflate_plan_host_test tools/asan/wire_inflate_plan_host_test tools/asan/wire_inflate_host_test
+      tools/asan/wire_in_plan_host_test tools/asan/wire_deflate_plan_host_test tools/asan/wire_inflate_plan_host_test tools/asan/wire_inflate_host_test \
+      tools/asan/brillig_retry_plan_host_test tools/asan/brillig_resume_host_test
 tools/asan/fuzz_driver: $(ASAN_SRCS) $(wildcard acvm_amd/csrc/*.hpp)
 	$(CXX) $(ASAN_FLAGS) -o $@ $(ASAN_SRCS) -lz
 tools/asan/import_plan_host_test: $(PLAN_SRCS) acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
@@ -76,4 +81,9 @@ tools/asan/wire_inflate_host_test: tools/wire_inflate_host_test.hip acvm_amd/csr
 	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/wire_inflate_host_test.hip $(WIRE_INFLATE_PLAN_SRCS)
 tools/asan/assigned_view_host_test: tools/assigned_view_host_test.cpp acvm_amd/csrc/assigned_view.hpp
 	$(CXX) $(ASAN_FLAGS) -o $@ tools/assigned_view_host_test.cpp
+BRILLIG_RETRY_SRCS = tools/brillig_retry_plan_host_test.cpp acvm_amd/csrc/brillig_retry_plan.cpp
+tools/asan/brillig_retry_plan_host_test: $(BRILLIG_RETRY_SRCS) acvm_amd/csrc/brillig_retry_plan.hpp acvm_amd/csrc/brillig_resume.hpp
+	$(CXX) $(ASAN_FLAGS) -o $@ $(BRILLIG_RETRY_SRCS)
+tools/asan/brillig_resume_host_test: tools/brillig_resume_host_test.hip acvm_amd/csrc/brillig_resume.hpp
+	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/brillig_resume_host_test.hip
 .PHONY: asan

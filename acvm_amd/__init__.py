@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "acvm_debug_table_info", "acvm_debug_table_read", "acvm_debug_batch_tables",
     "acvm_batch_outcomes_device", "acvm_batch_export_device_list", "acvm_debug_export_h2d_bytes", "acvm_debug_select",
     "acvm_node_solve_device", "acvm_debug_node_io_bytes",
-    "acvm_batch_foreign_call_sites", "acvm_batch_foreign_call_inputs_device", "acvm_batch_resolve_foreign_calls_device", "acvm_debug_foreign_call_stats",
+    "acvm_batch_foreign_call_sites", "acvm_batch_foreign_call_inputs_device", "acvm_batch_resolve_foreign_calls_device", "acvm_debug_foreign_call_stats", "acvm_debug_brillig_resume_stats",
     "acvm_batch_resolve_foreign_calls_device_rows",
     "acvm_node_set_foreign_call_handler", "acvm_node_foreign_stats",
     "acvm_batch_import_device_records", "acvm_batch_set_initial_witness_records", "acvm_node_solve_records",
@@ -661,6 +661,8 @@ def lib():
         L.acvm_batch_resolve_foreign_calls_device.argtypes = [C.c_void_p, C.POINTER(ForeignCallAnswersDesc)]
         L.acvm_debug_foreign_call_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                      C.POINTER(C.c_uint64)]
+    if hasattr(L, "acvm_debug_brillig_resume_stats"):
+        L.acvm_debug_brillig_resume_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     if hasattr(L, "acvm_batch_resolve_foreign_calls_device_rows"):
         L.acvm_batch_resolve_foreign_calls_device_rows.argtypes = [C.c_void_p, C.POINTER(ForeignCallAnswersRowsDesc)]
     if hasattr(L, "acvm_node_set_foreign_call_handler"):
@@ -1892,6 +1894,12 @@ class Batch:
         h2d, d2h, t_in, t_app, store = C.c_uint64(), C.c_uint64(), C.c_double(), C.c_double(), C.c_uint64()
         _check(lib().acvm_debug_foreign_call_stats(self._h, C.byref(h2d), C.byref(d2h), C.byref(t_in), C.byref(t_app), C.byref(store)))
         return dict(h2d_bytes=h2d.value, d2h_bytes=d2h.value, inputs_kernel_ms=t_in.value, append_kernel_ms=t_app.value, store_bytes=store.value)
+
+    def brillig_resume_stats(self) -> dict:
+        """what the Brillig retry passes of the last solve did under tuning(brillig_resume=1), all zero otherwise (acvm_debug_brillig_resume_stats)"""
+        out = (C.c_uint64 * 6)()
+        _check(lib().acvm_debug_brillig_resume_stats(self._h, out))
+        return dict(zip(("passes", "lanes_continued", "lanes_restarted", "cells_relocated", "steps_executed", "relocation_launches"), (int(v) for v in out)))
 
     def stats(self) -> dict:
         s = Stats()

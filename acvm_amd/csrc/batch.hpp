@@ -275,6 +275,16 @@ struct acvm_batch {
     bool br_retry_active = false;
     uint32_t br_max_regs = 1;  // most registers any Brillig opcode of the circuit uses
     uint32_t n_brillig_retries = 0;  // retry passes of the last solve
+    // brillig_resume (brillig_resume.hpp): the exact lanes' checkpoint records, the host's per-lane "valid" column, the per-pass step counters,
+    // the relocation descriptors; what the last solve did (acvm_debug_brillig_resume_stats: passes, lanes continued, lanes restarted, cells
+    // relocated, VM steps executed in compact passes, relocation launches)
+    uint32_t *d_br_ckpt = nullptr, *d_br_resume = nullptr;
+    unsigned long long *d_br_pass_steps = nullptr;
+    void *d_br_reloc = nullptr;
+    uint32_t br_ckpt_cap = 0, br_reloc_cap = 0;
+    bool br_resume_active = false;
+    uint64_t br_total_steps = 0;
+    uint64_t br_resume_stats[6] = {0, 0, 0, 0, 0, 0};
 
     ~acvm_batch() {
         hipSetDevice(device);
@@ -321,6 +331,8 @@ struct acvm_batch {
             if (d_x_scratch[k]) hipFree(d_x_scratch[k]);
         if (d_br_scratch) hipFree(d_br_scratch);
         if (d_br_lane) hipFree(d_br_lane);
+        for (void *p : {(void *)d_br_ckpt, (void *)d_br_resume, (void *)d_br_pass_steps, d_br_reloc})
+            if (p) hipFree(p);
         for (void *p : {(void *)d_fc_store, (void *)d_fc_pend_desc, (void *)d_fc_pend_vals})
             if (p) hipFree(p);
         for (auto &sl : fc_slots)

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 #include "batch_internal.hpp"
+#include "brillig_retry_plan.hpp"
 
 int ensure_slow_capacity(acvm_batch *b, uint32_t n) {
     if (n <= b->slow_cap) return 0;
@@ -30,7 +31,15 @@ int ensure_slow_capacity(acvm_batch *b, uint32_t n) {
 
 ExactLanes exact_lanes(acvm_batch *b, uint32_t n_slow) {
     FcLanes fc{b->d_fc_pend_desc, b->fc_pend_desc_words, b->d_fc_pend_vals, b->fc_pend_vals_cap};
-    return ExactLanes{b->xids(), n_slow, b->d_assigned, b->d_slow_start, b->d_slow_res, fc, b->br_retry_active ? b->d_br_lane : nullptr};
+    ExactLanes L{b->xids(), n_slow, b->d_assigned, b->d_slow_start, b->d_slow_res, fc, b->br_retry_active ? b->d_br_lane : nullptr};
+    if (b->br_retry_active && b->br_resume_active) {
+        L.br_max_regs = b->br_max_regs;
+        L.br_ckpt = b->d_br_ckpt;
+        L.br_resume = b->d_br_resume;
+        L.br_pass_steps = b->d_br_pass_steps;
+        L.br_total = b->br_total_steps;
+    }
+    return L;
 }
 
 // Foreign-call round trip, device side: the buffers a pending call's inputs are written to (per exact lane, FcLanes::pend_*) and
@@ -289,7 +298,7 @@ int run_exact_segments(acvm_batch *b, uint32_t n_slow, uint32_t min_start, bool 
 // RETRIED here: their opcode runs again (a failed VM run has no side effects: outputs are inserted after it finishes) with the
 // limit that was hit raised -- memory to twice the cell the write wanted, steps and depth sixteen-fold -- in a scratch that holds
 // only the retried lanes, until nothing hits a limit or a stated maximum of the library is reached (tuning.hpp: 2^26 steps, 2^16
-// frames, 2^22 cells by default). Past a maximum THAT INSTANCE ends with status Failure / ACVM_ERR_DEVICE_LIMIT -- an outcome the
+// frames, 2^22 cells by default; brillig_resume = 1 continues a lane instead: see retry_device_limits below). Past a maximum THAT INSTANCE ends with status Failure / ACVM_ERR_DEVICE_LIMIT -- an outcome the
 // reference does not have and the header says so: "this library could not finish the instance, run it with the reference" -- and every
 // other instance of the batch keeps its result (round 3 failed the whole solve call and lost them: the reference's caller loop,
 // acvm_js/src/execute.rs:60-119, loses one instance at most). Called with the lanes' results on the host (stream synchronised).
@@ -308,84 +317,138 @@ static void give_up_lane(SlowResult &r, uint32_t kind, uint64_t limit, uint64_t 
     r.msg = 29u;  // DM_DEVICE_LIMIT (ops_common.hpp): format_message words it
     r.x0 = (uint32_t)std::min<uint64_t>(wanted, 0xFFFFFFFFu);
 }
+static_assert(BR_KIND_STEPS == ACVM_LIMIT_BRILLIG_STEPS && BR_KIND_CALL_DEPTH == ACVM_LIMIT_BRILLIG_CALL_DEPTH && BR_KIND_MEMORY == ACVM_LIMIT_BRILLIG_MEMORY &&
+              BR_KIND_DEVICE_MEMORY == ACVM_LIMIT_DEVICE_MEMORY, "brillig_retry_plan.hpp names the limits of the header");
+// Under brillig_resume (tuning.hpp) a lane that reaches a limit in a compact pass is CONTINUED: the kernel left its checkpoint record
+// (brillig_resume.hpp), its registers, memory and call stack lie in the compact scratch, and when the next pass's scratch differs -- another
+// stride, column, capacity or depth -- one launch relocates the live state into a NEW buffer before the old one is freed. A pass then is a
+// slice of at most 2^brillig_steps_max_log2 steps and the run ends at 2^brillig_steps_total_log2 steps in all. Who continues, who restarts,
+// who is final and what the next pass looks like is decided by brillig_retry_plan (a pure function, tested on the host); this loop carries
+// the decisions out -- for the blocking solve, the asynchronous job of the node driver, the replay after a foreign call and the stepping alike.
 int retry_device_limits(acvm_batch *b, uint32_t n_slow, bool replay, uint32_t end_opcode) {
     const Plan &p = b->plan();
     const Tuning &tn = p.tune;
     hipStream_t s = b->xstream();
     const BrilligLimits base = b->dp.brillig;
-    const uint64_t max_steps = 1ull << (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.brillig_steps_max_log2, 0), 31);
-    const uint64_t max_depth = (uint64_t)std::min<int64_t>(std::max<int64_t>(tn.brillig_call_depth_max, 1), 1 << 24);
-    const uint64_t max_cells = 1ull << (uint32_t)std::min<int64_t>(std::max<int64_t>(tn.brillig_mem_max_log2, 0), 30);
-    BrilligLimits lim = base;
+    const BrRetryCaps caps = brillig_retry_caps(tn.brillig_steps_max_log2, tn.brillig_call_depth_max, tn.brillig_mem_max_log2, tn.brillig_resume, tn.brillig_steps_total_log2);
+    BrRetryLimits cur;
+    cur.steps = base.steps; cur.call_depth = base.call_depth; cur.mem_cap = base.mem_cap; cur.stride = base.stride;
+    bool compact = false;  // the pass that just ended ran in the compact scratch: only then a lane can have a checkpoint
+    std::vector<uint32_t> prev_col(n_slow, BR_NO_COLUMN), ckpt((size_t)n_slow * BR_CKPT_WORDS, 0u);
+    std::vector<unsigned long long> pass_steps(n_slow, 0ull);
+    std::vector<BrRetryLane> lanes(n_slow);
     int rc = 0;
     for (;;) {
-        // the memory a retried lane runs with so far (0 = the planner's estimate of its record)
-        uint64_t record_cells = 0;
+        bool any = false;
         for (uint32_t t = 0; t < n_slow; t++) {
             const SlowResult &r = b->slow_res[t];
-            if (is_device_limit(r) && r.opcode_index < p.n_opcodes && p.prog[p.prog_offset[r.opcode_index]] == PK_BRILLIG)
-                record_cells = std::max<uint64_t>(record_cells, p.prog[p.prog_offset[r.opcode_index] + 8]);
-        }
-        const uint64_t cur_cells = lim.mem_cap ? lim.mem_cap : record_cells;
-        // lanes past a stated maximum are final; the rest is retried with the limits they reached raised
-        std::vector<uint32_t> lanes;
-        bool hit_steps = false, hit_depth = false, hit_mem = false;
-        uint64_t want_cells = 0;
-        for (uint32_t t = 0; t < n_slow; t++) {
-            SlowResult &r = b->slow_res[t];
+            lanes[t] = BrRetryLane();
             if (!is_device_limit(r)) continue;
-            if (r.msg == 18u && lim.steps >= max_steps) { give_up_lane(r, ACVM_LIMIT_BRILLIG_STEPS, max_steps, 0); continue; }
-            if (r.msg == 28u && lim.call_depth >= max_depth) { give_up_lane(r, ACVM_LIMIT_BRILLIG_CALL_DEPTH, max_depth, 0); continue; }
-            // (the lane's own capacity so far: the raised one of an earlier pass, else the planner's estimate of ITS record -- not the largest
-            // estimate among the lanes of this pass, which gave up a lane whose own need still fitted)
-            const uint64_t own_cells = lim.mem_cap ? lim.mem_cap : (r.opcode_index < p.n_opcodes && p.prog[p.prog_offset[r.opcode_index]] == PK_BRILLIG ? p.prog[p.prog_offset[r.opcode_index] + 8] : 0u);
-            if (r.msg == 17u && ((uint64_t)r.x0 + 1 > max_cells || own_cells >= max_cells)) { give_up_lane(r, ACVM_LIMIT_BRILLIG_MEMORY, max_cells, r.x0); continue; }
-            lanes.push_back(t);
-            hit_steps |= r.msg == 18u;
-            hit_depth |= r.msg == 28u;
-            if (r.msg == 17u) {
-                hit_mem = true;
-                want_cells = std::max<uint64_t>(want_cells, (uint64_t)r.x0 + 1);
+            any = true;
+            lanes[t].msg = r.msg;
+            lanes[t].x0 = r.x0;
+            lanes[t].opcode = r.opcode_index;
+            if (r.opcode_index < p.n_opcodes && p.prog[p.prog_offset[r.opcode_index]] == PK_BRILLIG) {
+                lanes[t].n_regs = p.prog[p.prog_offset[r.opcode_index] + 7];
+                lanes[t].record_cells = p.prog[p.prog_offset[r.opcode_index] + 8];
             }
+            lanes[t].prev_col = prev_col[t];
+            if (compact && caps.resume) lanes[t].ckpt = br_ckpt_decode(&ckpt[(size_t)t * BR_CKPT_WORDS]);
         }
-        if (lanes.empty()) break;
-        if (hit_steps) lim.steps = (uint32_t)std::min<uint64_t>((uint64_t)lim.steps * 16, max_steps);
-        if (hit_depth) lim.call_depth = (uint32_t)std::min<uint64_t>((uint64_t)lim.call_depth * 16, max_depth);
-        uint64_t cells = std::max<uint64_t>(cur_cells, 64);
-        if (hit_mem) cells = std::min<uint64_t>(std::max<uint64_t>(2 * want_cells, 4 * cells), max_cells);
-        lim.mem_cap = (uint32_t)cells;
-        lim.stride = ((uint64_t)lanes.size() + 63) / 64 * 64;
-        const uint64_t words = ((uint64_t)b->br_max_regs + cells) * 8 + lim.call_depth + cells / 4 + 16;
-        const size_t bytes = (size_t)words * lim.stride * 4;
-        if (bytes > b->br_scratch_bytes) {
+        if (!any) break;
+        BrRetryPlan plan;
+        brillig_retry_plan(caps, cur, compact, b->br_max_regs, lanes, &plan);
+        // the scratch of the next pass. Lanes that continue and move: a second buffer, the relocation, then the old one is freed; nobody
+        // continues: the old buffer serves when it is large enough, else it is freed first and the larger one allocated
+        if (plan.n_continued && plan.relocate) {
+            uint32_t *fresh = nullptr;
+            if (hipMalloc((void **)&fresh, plan.scratch_bytes) != hipSuccess) {
+                (void)hipGetLastError();  // the device cannot hold both scratches: the lanes of this pass are final
+                brillig_retry_refused(&plan);
+            } else {
+                const uint32_t n_reloc = (uint32_t)plan.reloc.size();
+                uint64_t max_items = 0;
+                for (const BrRelocLane &rl : plan.reloc) max_items = std::max(max_items, br_reloc_items(rl));
+                hipError_t e = hipSuccess;
+                if (n_reloc > b->br_reloc_cap) {
+                    if (b->d_br_reloc) hipFree(b->d_br_reloc);
+                    b->d_br_reloc = nullptr;
+                    b->br_reloc_cap = 0;
+                    e = hipMalloc(&b->d_br_reloc, (size_t)n_reloc * sizeof(BrRelocLane));
+                    if (e == hipSuccess) b->br_reloc_cap = n_reloc;
+                }
+                if (e == hipSuccess) e = hipMemcpyAsync(b->d_br_reloc, plan.reloc.data(), (size_t)n_reloc * sizeof(BrRelocLane), hipMemcpyHostToDevice, s);
+                if (e == hipSuccess) {
+                    launch_brillig_relocate(s, (const BrRelocLane *)b->d_br_reloc, n_reloc, max_items, plan.from, b->d_br_scratch, plan.to, fresh);
+                    e = hipGetLastError();
+                }
+                if (e == hipSuccess) e = hipStreamSynchronize(s);  // the copy has read the old buffer: now it may go
+                if (e != hipSuccess) {
+                    hipFree(fresh);
+                    rc = set_err(ACVM_E_DEVICE, std::string("relocating the Brillig VM scratch failed: ") + hipGetErrorString(e));
+                    break;
+                }
+                hipFree(b->d_br_scratch);
+                b->d_br_scratch = fresh;
+                b->br_scratch_bytes = (size_t)plan.scratch_bytes;
+                b->br_resume_stats[3] += plan.cells_relocated;
+                if (n_reloc && max_items) b->br_resume_stats[5]++;  // (lanes without a register, a cell or a frame: a new buffer, no launch)
+            }
+        } else if (plan.n_retried && !plan.n_continued && plan.scratch_bytes > b->br_scratch_bytes) {
             if (b->d_br_scratch) hipFree(b->d_br_scratch);
             b->d_br_scratch = nullptr;
             b->br_scratch_bytes = 0;
-            if (hipMalloc((void **)&b->d_br_scratch, bytes) != hipSuccess) {
+            if (hipMalloc((void **)&b->d_br_scratch, (size_t)plan.scratch_bytes) != hipSuccess) {
                 (void)hipGetLastError();  // the device cannot hold the VM scratch of these lanes: they are final too
-                for (uint32_t t : lanes) give_up_lane(b->slow_res[t], ACVM_LIMIT_DEVICE_MEMORY, bytes >> 20, 0);
-                break;
-            }
-            b->br_scratch_bytes = bytes;
+                brillig_retry_refused(&plan);
+            } else b->br_scratch_bytes = (size_t)plan.scratch_bytes;
         }
+        for (uint32_t t = 0; t < n_slow; t++)
+            if (plan.lanes[t].action == BR_FINAL) give_up_lane(b->slow_res[t], plan.lanes[t].kind, plan.lanes[t].limit, plan.lanes[t].wanted);
+        if (!plan.n_retried) break;
+        BrilligLimits lim = base;
+        lim.steps = plan.next.steps;
+        lim.call_depth = plan.next.call_depth;
+        lim.mem_cap = plan.next.mem_cap;
+        lim.stride = plan.next.stride;
         if (n_slow > b->br_lane_cap) {
             if (b->d_br_lane) hipFree(b->d_br_lane);
             b->d_br_lane = nullptr;
             HIPCHK(hipMalloc((void **)&b->d_br_lane, (size_t)n_slow * 4));
             b->br_lane_cap = n_slow;
         }
-        std::vector<uint32_t> col(n_slow, 0xFFFFFFFFu);
+        if (caps.resume && n_slow > b->br_ckpt_cap) {
+            for (void *q : {(void *)b->d_br_ckpt, (void *)b->d_br_resume, (void *)b->d_br_pass_steps})
+                if (q) hipFree(q);
+            b->d_br_ckpt = b->d_br_resume = nullptr;
+            b->d_br_pass_steps = nullptr;
+            b->br_ckpt_cap = 0;
+            HIPCHK(hipMalloc((void **)&b->d_br_ckpt, (size_t)n_slow * BR_CKPT_WORDS * 4));
+            HIPCHK(hipMalloc((void **)&b->d_br_resume, (size_t)n_slow * 4));
+            HIPCHK(hipMalloc((void **)&b->d_br_pass_steps, (size_t)n_slow * 8));
+            b->br_ckpt_cap = n_slow;
+        }
+        std::vector<uint32_t> col(n_slow, 0xFFFFFFFFu), valid(n_slow, 0u);
         uint32_t min_start = 0xFFFFFFFFu;
-        for (size_t i = 0; i < lanes.size(); i++) {
-            const uint32_t t = lanes[i];
-            col[t] = (uint32_t)i;
+        for (uint32_t t = 0; t < n_slow; t++) {
+            const BrRetryDecision &d = plan.lanes[t];
+            if (d.action != BR_CONTINUE && d.action != BR_RESTART) continue;
+            col[t] = d.col;
+            valid[t] = d.action == BR_CONTINUE ? 1u : 0u;
             const uint32_t at = b->slow_res[t].opcode_index;
-            b->slow_start[t] = at;  // the opcode runs again
+            b->slow_start[t] = at;  // the opcode runs again -- from its first instruction, or from its checkpoint
             min_start = std::min(min_start, at);
             memset(&b->slow_res[t], 0, sizeof(SlowResult));
             b->slow_res[t].status = ACVM_STATUS_IN_PROGRESS;
         }
         HIPCHK(hipMemcpyAsync(b->d_br_lane, col.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
+        if (caps.resume) {
+            // (the records of a handle's earlier solve, opcode or foreign-call round are never read: `valid` is 1 only for a record this very
+            // loop saw written by the pass that just ended; the first compact pass clears them all the same)
+            if (!compact) HIPCHK(hipMemsetAsync(b->d_br_ckpt, 0, (size_t)n_slow * BR_CKPT_WORDS * 4, s));
+            HIPCHK(hipMemcpyAsync(b->d_br_resume, valid.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemsetAsync(b->d_br_pass_steps, 0, (size_t)n_slow * 8, s));
+        }
         HIPCHK(hipMemcpyAsync(b->d_slow_start, b->slow_start.data(), (size_t)n_slow * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(b->d_slow_res, b->slow_res.data(), (size_t)n_slow * sizeof(SlowResult), hipMemcpyHostToDevice, s));
         // (the lanes that were given up stay Failure on the host and on the device: the exact kernels skip a lane that is not InProgress;
@@ -395,16 +458,33 @@ int retry_device_limits(acvm_batch *b, uint32_t n_slow, bool replay, uint32_t en
             if (b->slow_res[t].err == ACVM_ERR_DEVICE_LIMIT) final_lanes.push_back({t, b->slow_res[t]});
         b->dp.brillig = lim;
         b->br_retry_active = true;
+        b->br_resume_active = caps.resume;
+        b->br_total_steps = caps.total_steps;
         rc = run_exact_segments(b, n_slow, min_start, replay, end_opcode);
         if (!rc && b->pending) {  // (an asynchronous job leaves its results on the device: fetch them for the next look at the limits)
             if (hipMemcpyAsync(b->slow_res.data(), b->d_slow_res, (size_t)n_slow * sizeof(SlowResult), hipMemcpyDeviceToHost, s) != hipSuccess) rc = set_err(ACVM_E_DEVICE, "hipMemcpyAsync failed in a Brillig retry pass");
+        }
+        if (!rc && caps.resume) {
+            if (hipMemcpyAsync(ckpt.data(), b->d_br_ckpt, ckpt.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(pass_steps.data(), b->d_br_pass_steps, (size_t)n_slow * 8, hipMemcpyDeviceToHost, s) != hipSuccess)
+                rc = set_err(ACVM_E_DEVICE, "hipMemcpyAsync failed in a Brillig retry pass");
         }
         if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = set_err(ACVM_E_DEVICE, "hipStreamSynchronize failed in a Brillig retry pass");
         for (auto &fl : final_lanes) b->slow_res[fl.first] = fl.second;
         b->dp.brillig = base;
         b->br_retry_active = false;
+        b->br_resume_active = false;
         b->n_brillig_retries++;
         if (rc) break;
+        if (caps.resume) {
+            b->br_resume_stats[0]++;
+            b->br_resume_stats[1] += plan.n_continued;
+            b->br_resume_stats[2] += plan.n_restarted;
+            for (uint32_t t = 0; t < n_slow; t++) b->br_resume_stats[4] += pass_steps[t];
+        }
+        for (uint32_t t = 0; t < n_slow; t++) prev_col[t] = col[t];
+        cur = plan.next;
+        compact = true;
     }
     // The lanes that were given up are final on the DEVICE too: a caller that keeps stepping (solve_stepping) fetches the device's records
     // after every step, and a lane whose device record still said "panic at a device limit" came back as ACVM_ERR_PANIC and was retried
@@ -415,6 +495,12 @@ int retry_device_limits(acvm_batch *b, uint32_t n_slow, bool replay, uint32_t en
         if (any_final) HIPCHK(hipMemcpyAsync(b->d_slow_res, b->slow_res.data(), (size_t)n_slow * sizeof(SlowResult), hipMemcpyHostToDevice, s));
     }
     return rc;
+}
+
+int acvm_debug_brillig_resume_stats(const acvm_batch_t *b, uint64_t out[6]) {
+    if (!b || !out) return set_err(ACVM_E_INVALID, "null argument");
+    for (int k = 0; k < 6; k++) out[k] = b->br_resume_stats[k];
+    return 0;
 }
 
 int count_not_solved(acvm_batch *b) {

@@ -131,6 +131,7 @@ int batch_solve_impl(acvm_batch *b, const ImportPlan *next) {
     if (int rc = upload_fc_tables(b, 0)) return rc;  // the level kernels read the resolved results too
     b->n_launches = 0;
     b->n_brillig_retries = 0;
+    for (uint64_t &v : b->br_resume_stats) v = 0;
     b->host_bb_msg.clear();
     b->arith_kernel_ms = 0;
     b->dyn_kernel_ms = 0;

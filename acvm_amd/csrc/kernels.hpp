@@ -49,6 +49,14 @@ struct ExactLanes {
     SlowResult *results;
     FcLanes fc;
     const uint32_t *br_lane = nullptr;  // Brillig retry pass: column of lane t in the compact VM scratch (0xFFFFFFFF: not retried); null otherwise
+    uint32_t br_max_regs = 0;           // brillig_resume: the registers of the circuit's largest Brillig record -- the scratch's word region lies behind that many slots
+    // brillig_resume (null otherwise): the lanes' checkpoint records [n_slow][BR_CKPT_WORDS]; per lane 1 = "the record is valid for the opcode
+    // the lane starts at", written by the HOST before every pass; VM steps lane t executed in this pass (the host zeroes it before the pass)
+    uint32_t *br_ckpt = nullptr;
+    const uint32_t *br_resume = nullptr;
+    unsigned long long *br_pass_steps = nullptr;
+    uint64_t br_total = 0;  // ... VM steps one run of an opcode may execute over all its passes; BrilligLimits::steps is the slice of this pass
+    // (these live here and not in BrilligLimits: DeviceProgram is copied into every level kernel's private memory, the exact kernel alone reads these)
 };
 
 // everything a record needs besides the witness table
@@ -335,6 +343,12 @@ void launch_exact_init(hipStream_t s, const ExactLanes &L);
 // opcodes [op_begin, op_end) of EVERY class but CLS_HOSTBB in one launch (kernels_brillig.hip exact_run_kernel); prog_class: device
 // array, OpClass per opcode; the class scratch buffers as the per-opcode kernels take them
 struct ExactScratch { uint32_t *hash, *grumpkin, *brillig; };
+// brillig_resume: the continuing lanes' registers, live cells and call-stack words from the old compact scratch into the new one
+// (kernels_brillig_resume.hip; d_lanes: n_lanes BrRelocLane records on the device)
+struct BrLayout;
+struct BrRelocLane;
+void launch_brillig_relocate(hipStream_t s, const BrRelocLane *d_lanes, uint32_t n_lanes, uint64_t max_items, const BrLayout &from, const uint32_t *old_scratch,
+                             const BrLayout &to, uint32_t *new_scratch);
 void launch_exact_run(hipStream_t s, uint4 *W, uint64_t Bp, const DeviceProgram &dp, const ExactLanes &L, uint32_t op_begin, uint32_t op_end, bool replay_memory,
                       const uint8_t *prog_class, const ExactScratch &sc);
 void launch_grumpkin_probe(hipStream_t s, const GrumpkinTables &T, uint32_t what, uint32_t param, const uint32_t *in, uint32_t n_in, uint32_t *out);

@@ -7,10 +7,12 @@
 // stack and the hash staging bytes behind them. Control flow is per lane (SIMT divergence does the masking). The reference's VM has
 // no limits (memory grows on write, memory.rs:27-39; no step or call-depth bound, lib.rs:154-307); a kernel needs them: a memory
 // capacity, a step limit and a call-stack depth arrive with the launch (BrilligLimits). An instance that reaches one leaves the level
-// schedule, and the exact path RETRIES its opcode with the limits raised (batch.cpp retry_device_limits) up to the library's stated
-// maxima; past those acvm_batch_solve fails as a whole with ACVM_E_UNSUPPORTED -- an instance never reports a failure the reference
-// would not.
+// schedule, and the exact path RETRIES its opcode with the limits raised (batch_exact.cpp retry_device_limits) up to the library's stated
+// maxima; past those THAT INSTANCE ends with Failure / ACVM_ERR_DEVICE_LIMIT -- the one outcome the reference does not have -- and every
+// other instance of the batch keeps its result. Under brillig_resume a lane of a compact retry pass does not start over: it writes a
+// checkpoint when it leaves the VM loop and the next pass continues it (brillig_resume.hpp; X = true below, the exact kernel alone).
 #pragma once
+#include "brillig_resume.hpp"
 #include "kernels.hpp"
 #include "ops_ecdsa.hpp"
 #include "ops_grumpkin.hpp"
@@ -65,6 +67,16 @@ struct BrVm {
         if ((uint32_t)ptr + 1u > n_mem) n_mem = (uint32_t)ptr + 1u;
         return true;
     }
+    // brillig_resume: the capacity an instruction with several writes needs, asked for BEFORE its first write -- a lane that stops at the
+    // memory limit has left no side effect of the instruction it stopped in, the continued pass executes it again from its start
+    __device__ __forceinline__ bool mem_reserve(uint64_t ptr, uint64_t n) {
+        if (ptr <= mem_cap && n <= mem_cap - ptr) return true;
+        if (!status) {
+            const uint64_t last = ptr + n < ptr ? ~0ull : ptr + n - 1u;  // (ptr + n >= 1 here)
+            status = 5; code = DM_BRILLIG_MEM_CAP; x0 = last > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)last;
+        }
+        return false;
+    }
     // memory.rs:32-39 with NO values: resize(max(len, ptr + 0)) grows the memory to ptr cells all the same
     __device__ __forceinline__ bool mem_grow(uint64_t ptr) {
         if (ptr <= n_mem) return true;
@@ -87,8 +99,11 @@ static inline __device__ __noinline__ Fr brillig_int_op(BrVm &vm, uint32_t op, u
 }
 
 // black_box.rs:42-165. Operand words: see plan.cpp (HeapVector = pointer reg + size reg, HeapArray = pointer reg + literal)
+// (X: the exact kernel's copy. atomic: the pass runs under brillig_resume -- the capacity of the outputs is reserved before the first write.
+// The level kernel's copy never gets the argument and never reads it.)
+template <bool X>
 static inline __device__ __noinline__ void brillig_black_box(BrVm &vm, uint32_t bbop, const uint32_t *__restrict__ w, const GrumpkinTables &T,
-                                                             const uint32_t *__restrict__ ecdsa_g) {
+                                                             const uint32_t *__restrict__ ecdsa_g, bool atomic = false) {
     MsgBuf m{vm.words + (uint64_t)vm.cs_cap * vm.Bp, vm.Bp, vm.j, 0u, 0u};
     auto heap_vector = [&](uint32_t preg, uint32_t sreg, uint64_t &ptr, uint64_t &len) {
         const Fr pv = vm.reg_get(preg), sv = vm.reg_get(sreg);
@@ -106,6 +121,7 @@ static inline __device__ __noinline__ void brillig_black_box(BrVm &vm, uint32_t 
         if (bbop == 3u) { vm.reg_set(w[2], digest_to_field(d)); return; }
         const Fr ov = vm.reg_get(w[2]);
         if (vm.status || !vm.to_usize(ov, optr)) return;
+        if (X && atomic && !vm.mem_reserve(optr, 32u)) return;
         for (uint32_t i = 0; i < 32u; i++)
             if (!vm.mem_write(optr + i, fr_from_byte(d.byte(i)))) return;
         return;
@@ -147,6 +163,7 @@ static inline __device__ __noinline__ void brillig_black_box(BrVm &vm, uint32_t 
         grumpkin_pedersen(T, (uint32_t)len, ds.v[0], [&](uint32_t i) { return vm.mem_get((uint32_t)ptr + i); }, x, y);
         const Fr ov = vm.reg_get(w[3]);
         if (vm.status || !vm.to_usize(ov, optr)) return;
+        if (X && atomic && !vm.mem_reserve(optr, 2u)) return;
         if (vm.mem_write(optr, x)) vm.mem_write(optr + 1, y);
         return;
     }
@@ -167,6 +184,7 @@ static inline __device__ __noinline__ void brillig_black_box(BrVm &vm, uint32_t 
         }
         const Fr ov = vm.reg_get(w[2]);
         if (vm.status || !vm.to_usize(ov, optr)) return;
+        if (X && atomic && !vm.mem_reserve(optr, 2u)) return;
         if (vm.mem_write(optr, x)) vm.mem_write(optr + 1, y);
         return;
     }
@@ -180,8 +198,10 @@ static inline __device__ __noinline__ void brillig_black_box(BrVm &vm, uint32_t 
 // from what the host resolved for this instance and opcode (the batch-wide store, kernels.hpp FcStoreSlot: level kernels and
 // exact kernels alike). Without a result the VM stops with status 3 and, on the exact path, hands the resolved inputs to the
 // host (ForeignCallWaitInfo, pwg/brillig.rs:157-163).
+template <bool X>
 static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const uint32_t *__restrict__ ex, const DeviceProgram &dp, uint32_t fc_desc_off,
                                                                 uint32_t fc_vals_off, uint32_t &fc_counter, uint32_t n_bc, uint32_t fc_slot, const ExactLanes *L, uint32_t t) {
+    const bool atomic = X && L && L->br_lane && L->br_ckpt;  // a compact pass under brillig_resume (op_brillig)
     const uint32_t n_dests = ex[0], n_in = ex[1];
     const uint32_t *dests = ex + 2, *ins = dests + 3 * n_dests;
     // locate result number fc_counter: static table first, then the instance's table
@@ -248,6 +268,34 @@ static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const 
     }
     bool invalid = false;
     const uint32_t nz = n_dests < n_res ? n_dests : n_res;
+    if (X && atomic) {
+        // brillig_resume: a sizing walk over the destinations BEFORE the first write. A register written for destination i -- a value, or a
+        // vector's size -- may be the pointer register of a later destination (or of its own vector), so a pointer is read through the
+        // writes that precede it: the last one wins. The walk ends where the writing loop below would panic or find a wrong size: what
+        // that loop does up to there needs no more memory than the walk has seen.
+        uint32_t wpos = pos;
+        for (uint32_t i = 0; i < nz; i++, wpos += 2) {
+            const uint32_t is_array = desc(wpos), n = desc(wpos + 1);
+            const uint32_t kind = dests[3 * i], rg = dests[3 * i + 1], sz = dests[3 * i + 2];
+            if (rg >= 65536u) break;
+            if (kind == 0u) {
+                if (is_array) break;
+                continue;
+            }
+            if (!is_array || (kind == 1u && n != sz) || (kind == 2u && sz >= 65536u)) break;
+            Fr pv = vm.reg_get(rg);
+            uint32_t spos = pos, sv = vpos;
+            for (uint32_t q = 0; q <= i; q++, spos += 2) {
+                const uint32_t qn = desc(spos + 1), qkind = dests[3 * q];
+                if (q < i && qkind == 0u && dests[3 * q + 1] == rg) pv = value(sv);
+                if (qkind == 2u && dests[3 * q + 2] == rg) pv = fr_from_u32(qn);
+                sv += qn;
+            }
+            const Fr pc = fr_to_canonical(pv);
+            if (pc.v[2] | pc.v[3] | pc.v[4] | pc.v[5] | pc.v[6] | pc.v[7]) break;  // (Value::to_usize panics in the loop below)
+            if (!vm.mem_reserve((uint64_t)pc.v[1] << 32 | pc.v[0], n)) return;
+        }
+    }
     for (uint32_t i = 0; i < nz; i++, pos += 2) {
         const uint32_t is_array = desc(pos), n = desc(pos + 1);
         const uint32_t kind = dests[3 * i], rg = dests[3 * i + 1], sz = dests[3 * i + 2];
@@ -277,7 +325,7 @@ static inline __device__ __noinline__ void brillig_foreign_call(BrVm &vm, const 
     if (failed) vm.status = vm.pc + 1u >= n_bc ? 1u : 2u;  // running off the end turns the failure into Finished
 }
 
-template <class P>
+template <class P, bool X = false>
 __device__ __forceinline__ OpResult op_brillig(const P &p, const uint32_t *__restrict__ r, const DeviceProgram &dp, uint32_t *scratch, SlowResult *res,
                                                const ExactLanes *L, uint32_t t) {
     const uint32_t has_pred = r[2], n_inputs = r[3], n_outputs = r[4], n_bc = r[6];
@@ -323,13 +371,33 @@ __device__ __forceinline__ OpResult op_brillig(const P &p, const uint32_t *__res
     vm.j = compact ? L->br_lane[t] : p.scratch_lane();
     vm.iBp = p.Bp;
     vm.ij = p.j;
-    vm.words = scratch + (uint64_t)(vm.n_regs + vm.mem_cap) * 8u * vm.Bp;
+    // brillig_resume (compact passes of the exact kernel): the lane's checkpoint record. The HOST says whether it is valid for the opcode the
+    // lane starts at (L->br_resume); a later Brillig opcode of the same pass starts fresh.
+    const bool resume = X && compact && L->br_ckpt != nullptr;
+    // (under resume the word region lies behind the slots of the circuit's largest record, by the index functions the relocation uses --
+    // brillig_resume.hpp says why; every other pass keeps the layout it had: behind the record's own slots)
+    vm.words = scratch + (X && resume ? br_words_base(BrLayout{vm.Bp, vm.mem_cap, vm.cs_cap, L->br_max_regs}) : (uint64_t)(vm.n_regs + vm.mem_cap) * 8u * vm.Bp);
     vm.n_mem = vm.n_cs = vm.pc = vm.status = vm.code = vm.x0 = 0u;
     vm.val = fr_zero();
-    for (uint32_t i = 0; i < vm.n_regs; i++) fr_store(vm.slots, i, vm.Bp, vm.j, fr_zero());  // unset registers read 0 (registers.rs:25-33)
+    uint32_t *ck = nullptr;
+    uint64_t done = 0;
+    bool cont = false;
+    if (X && resume) {
+        ck = L->br_ckpt + (uint64_t)t * BR_CKPT_WORDS;
+        cont = L->br_resume[t] != 0u && r[1] == L->start_opcode[t];
+        if (cont) {  // the registers, the memory and the call stack are where the relocation put them: restore the scalars
+            const BrCkpt c = br_ckpt_decode(ck);
+            vm.pc = c.pc;
+            vm.n_mem = c.n_mem;
+            vm.n_cs = c.n_cs;
+            fc_counter = c.fc_counter;
+            done = c.steps;
+        } else ck[7] = BR_CKPT_NONE;  // (a lane that stops while it loads its inputs has no checkpoint: it restarts)
+    }
+    if (!cont) for (uint32_t i = 0; i < vm.n_regs; i++) fr_store(vm.slots, i, vm.Bp, vm.j, fr_zero());  // unset registers read 0 (registers.rs:25-33)
     // inputs (brillig.rs:46-74): an expression that does not reduce to a constant is ExpressionHasTooManyUnknowns
     q = inputs;
-    for (uint32_t i = 0; i < n_inputs; i++) {
+    for (uint32_t i = 0; i < (cont ? 0u : n_inputs); i++) {
         const uint32_t is_array = q[0], n = q[1];
         q += 2;
         const uint32_t base = vm.n_mem;
@@ -345,9 +413,14 @@ __device__ __forceinline__ OpResult op_brillig(const P &p, const uint32_t *__res
     }
     // process_opcodes (lib.rs:136-142)
     if (n_bc == 0) vm.panic(BP_BYTECODE_OOB);
-    uint32_t steps = 0;
+    uint32_t steps = 0, budget = lim.steps;
+    if (X && resume) {  // the slice of this pass, cut at what is left of the run's total
+        const uint64_t left = L->br_total > done ? L->br_total - done : 0u;
+        if (left < budget) budget = (uint32_t)left;
+    }
     while (!vm.status) {
-        if (++steps > lim.steps) { vm.status = 5; vm.code = DM_BRILLIG_STEP_LIMIT; break; }
+        // (the level kernel reads its limit where it did: a copy in a register costs it one)
+        if (++steps > (X && resume ? budget : lim.steps)) { vm.status = 5; vm.code = DM_BRILLIG_STEP_LIMIT; break; }
         const uint32_t *__restrict__ ins = bc + 8u * vm.pc;
         const uint32_t op = ins[0], a = ins[1], b = ins[2], c = ins[3];
         uint32_t next = vm.pc + 1u;
@@ -405,13 +478,27 @@ __device__ __forceinline__ OpResult op_brillig(const P &p, const uint32_t *__res
         }
         case BRO_TRAP: vm.status = 2; vm.code = DM_BRILLIG_TRAP; break;
         case BRO_STOP: vm.status = 1; break;
-        case BRO_BLACK_BOX: brillig_black_box(vm, ins[4], dp.bytecode + ins[7], dp.grumpkin, dp.ecdsa_g); break;
-        case BRO_FOREIGN_CALL: brillig_foreign_call(vm, dp.bytecode + ins[7], dp, r[9], r[10], fc_counter, n_bc, r[11], L, t); break;
+        case BRO_BLACK_BOX:
+            if (X) brillig_black_box<X>(vm, ins[4], dp.bytecode + ins[7], dp.grumpkin, dp.ecdsa_g, resume);
+            else brillig_black_box<X>(vm, ins[4], dp.bytecode + ins[7], dp.grumpkin, dp.ecdsa_g);
+            break;
+        case BRO_FOREIGN_CALL: brillig_foreign_call<X>(vm, dp.bytecode + ins[7], dp, r[9], r[10], fc_counter, n_bc, r[11], L, t); break;
         default: vm.panic(BP_BAD_OPCODE); break;
         }
         if (vm.status) break;
         vm.pc = next;  // set_program_counter (lib.rs:322-329)
         if (vm.pc >= n_bc) vm.status = 1;
+    }
+    if (X && resume) {
+        // every exit of the loop leaves the record: an instruction that stopped at a limit (status 5) was counted but has not executed
+        const uint64_t executed = vm.status == 5u && steps ? steps - 1u : steps;
+        BrCkpt c;
+        c.pc = vm.pc; c.n_mem = vm.n_mem; c.n_cs = vm.n_cs; c.fc_counter = fc_counter;
+        c.steps = done + executed;
+        c.opcode = r[1];
+        c.state = vm.status;
+        br_ckpt_encode(c, ck);
+        L->br_pass_steps[t] += executed;
     }
     if (vm.status == 1) {  // Finished (brillig.rs:95-111): register i -> output i
         q = outputs;

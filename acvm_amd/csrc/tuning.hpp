@@ -68,6 +68,11 @@ struct Tuning {
     int64_t brillig_steps_log2 = 22, brillig_steps_max_log2 = 26;
     int64_t brillig_call_depth = 64, brillig_call_depth_max = 1 << 16;
     int64_t brillig_mem_max_log2 = 22;  // cells of one lane's memory on the exact path at most (32 B each)
+    // 1: a lane that reaches a limit in a compact retry pass CONTINUES from a checkpoint instead of running its opcode again (brillig_resume.hpp,
+    // brillig_retry_plan.hpp). brillig_steps_max_log2 then bounds ONE pass (the slice) and no launch runs longer than that; what ends an
+    // instance is the total below, counted over all passes of one run of the opcode. 0: every retry starts the opcode over, as before.
+    int64_t brillig_resume = 0;
+    int64_t brillig_steps_total_log2 = 32;  // (0..62) under brillig_resume: 2^this VM steps finish, one more is ACVM_ERR_DEVICE_LIMIT. A stated maximum like its neighbours, not a measurement
     // ---- tables (grumpkin_host.cpp)
     int64_t pedersen_window_bits = 24; // nonzero: the level Pedersen kernel reads 24-bit windows of the scalar (GRUMPKIN_PEDW_BITS: 23.6 GB of tables, 11 additions per hash_single) instead of slice pairs (0: 503 MB, 15)
     int64_t win16 = 1;             // 16-bit window tables of the four fixed bases

@@ -67,7 +67,9 @@ enum {
     /* NOT a reference outcome. The reference's Brillig VM has no resource limits (brillig_vm/src/memory.rs:27-39, lib.rs:154-307); the device
      * runs a program with limits, raises them on the exact path, and past the stated maxima of the library (acvm_tuning_set: brillig_steps_max_log2,
      * brillig_call_depth_max, brillig_mem_max_log2) or of the device's memory THIS INSTANCE ends here: status Failure at its Brillig opcode,
-     * aux0 = ACVM_LIMIT_* (what was reached), aux1 = the limit. It says "this library could not finish the instance", not "the circuit is
+     * aux0 = ACVM_LIMIT_* (what was reached), aux1 = the limit. With brillig_resume = 1 a lane is continued at a limit instead of started over,
+     * brillig_steps_max_log2 bounds one pass only, and the step limit that ends an instance is the total 2^brillig_steps_total_log2
+     * (aux1 = min(that, 2^32 - 1)): below a total the caller chooses, ACVM_LIMIT_BRILLIG_STEPS is not reached. It says "this library could not finish the instance", not "the circuit is
      * unsatisfied": re-run the instance with the reference (or with raised maxima). Every other instance of the batch keeps its result, as the
      * reference's caller loop loses one instance at most (acvm_js/src/execute.rs:60-119). */
     ACVM_ERR_DEVICE_LIMIT = 9
@@ -195,7 +197,9 @@ long long acvm_device_release_tables(int device);
  * none (brillig_vm/src/memory.rs:27-39 grows memory on write, lib.rs:154-307 runs any number of steps at any call depth); the device
  * runs with brillig_steps_log2 / brillig_call_depth / the planner's memory estimate, retries an instance that reaches one with the
  * limit raised, and past brillig_steps_max_log2 / brillig_call_depth_max / brillig_mem_max_log2 that instance ends with
- * ACVM_ERR_DEVICE_LIMIT (the others keep their results). Command-line tools may preset values through the environment: ACVM_TUNING="key=value,key=value".
+ * ACVM_ERR_DEVICE_LIMIT (the others keep their results). brillig_resume = 1 (default 0) continues such an instance from a checkpoint instead of
+ * running its opcode again: brillig_steps_max_log2 is then the most steps of ONE pass, and brillig_steps_total_log2 (default 32, 0..62) the most
+ * steps of one run of an opcode over all its passes. Command-line tools may preset values through the environment: ACVM_TUNING="key=value,key=value".
  */
 int acvm_tuning_set(const char *key, long long value);
 int acvm_tuning_get(const char *key, long long *value);
@@ -574,6 +578,11 @@ typedef struct {
 int acvm_batch_resolve_foreign_calls_device_rows(acvm_batch_t *b, const acvm_foreign_call_answers_rows_desc_t *d);
 int acvm_debug_foreign_call_stats(const acvm_batch_t *b, uint64_t *h2d_bytes, uint64_t *d2h_bytes, double *inputs_kernel_ms, double *append_kernel_ms,
                                   uint64_t *store_bytes);
+/* What the Brillig retry passes of the last solve did under brillig_resume = 1 (acvm_tuning_set; all zero otherwise): out[0] passes, out[1] lanes
+ * continued from a checkpoint, out[2] lanes that ran their opcode again, out[3] memory cells relocated between two scratches (live cells only),
+ * out[4] VM steps executed in those passes summed over lanes and passes, out[5] relocation launches (a change of buffers with nothing live to copy launches nothing and is not counted). Counted like n_brillig_retries: cleared by
+ * acvm_batch_solve, accumulated over the acvm_batch_solve_opcode steps and the continuations after a foreign call. */
+int acvm_debug_brillig_resume_stats(const acvm_batch_t *b, uint64_t out[6]);
 /* enable per-kernel HIP-event timing of the level kernels (small overhead) */
 int acvm_batch_set_profiling(acvm_batch_t *b, int on);
 
