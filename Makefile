@@ -24,7 +24,10 @@
 #               decisions of the Brillig retry loop -- continue, restart or final, the next pass's limits, columns and bytes:
 #               tools/asan/brillig_retry_plan_host_test (tests/test_brillig_retry_plan_on_host.py), and the checkpoint record, the scratch's index
 #               functions and the relocation run on host arrays of exactly their sizes: tools/asan/brillig_resume_host_test (hipcc, host side
-#               sanitized; tests/test_brillig_resume_on_host.py)
+#               sanitized; tests/test_brillig_resume_on_host.py), and the packed wire export's checks, chunk rule, arena carve and capacity rule:
+#               tools/asan/wire_pack_plan_host_test (tests/test_wire_pack_plan_on_host.py), and the repitch kernel's per-lane body, the scan's block
+#               arithmetic and the offsets judgement on heap blocks of exactly the stated sizes: tools/asan/wire_repitch_host_test (hipcc, host
+#               side sanitized; tests/test_wire_pack_on_host.py)
 CXX ?= g++
 ASAN_FLAGS = -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wall -Wno-sign-compare
 ASAN_SRCS = tools/asan/fuzz_driver.cpp acvm_amd/csrc/circuit.cpp acvm_amd/csrc/plan.cpp acvm_amd/csrc/tuning.cpp acvm_amd/csrc/schedule.cpp acvm_amd/csrc/schedule_check.cpp
@@ -46,7 +49,7 @@ asan: tools/asan/fuzz_driver tools/asan/import_plan_host_test tools/asan/assigne
       tools/asan/foreign_rows_plan_host_test tools/asan/foreign_rows_store_host_test tools/asan/node_foreign_plan_host_test tools/asan/import_mask_host_test \
       tools/asan/record_plan_host_test tools/asan/record_out_plan_host_test tools/asan/record_mask_plan_host_test tools/asan/wire_plan_host_test \
       tools/asan/wire_in_plan_host_test tools/asan/wire_deflate_plan_host_test tools/asan/wire_inflate_plan_host_test tools/asan/wire_inflate_host_test \
-      tools/asan/brillig_retry_plan_host_test tools/asan/brillig_resume_host_test
+      tools/asan/brillig_retry_plan_host_test tools/asan/brillig_resume_host_test tools/asan/wire_pack_plan_host_test tools/asan/wire_repitch_host_test
 tools/asan/fuzz_driver: $(ASAN_SRCS) $(wildcard acvm_amd/csrc/*.hpp)
 	$(CXX) $(ASAN_FLAGS) -o $@ $(ASAN_SRCS) -lz
 tools/asan/import_plan_host_test: $(PLAN_SRCS) acvm_amd/csrc/import_plan.hpp include/acvm_amd.h
@@ -86,4 +89,9 @@ tools/asan/brillig_retry_plan_host_test: $(BRILLIG_RETRY_SRCS) acvm_amd/csrc/bri
 	$(CXX) $(ASAN_FLAGS) -o $@ $(BRILLIG_RETRY_SRCS)
 tools/asan/brillig_resume_host_test: tools/brillig_resume_host_test.hip acvm_amd/csrc/brillig_resume.hpp
 	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/brillig_resume_host_test.hip
+WIRE_PACK_SRCS = tools/wire_pack_plan_host_test.cpp acvm_amd/csrc/wire_pack_plan.cpp acvm_amd/csrc/wire_plan.cpp
+tools/asan/wire_pack_plan_host_test: $(WIRE_PACK_SRCS) acvm_amd/csrc/wire_pack_plan.hpp acvm_amd/csrc/wire_plan.hpp acvm_amd/csrc/assigned_view.hpp include/acvm_amd.h
+	$(CXX) $(ASAN_FLAGS) -o $@ $(WIRE_PACK_SRCS)
+tools/asan/wire_repitch_host_test: tools/wire_repitch_host_test.hip acvm_amd/csrc/wire_repitch.hpp acvm_amd/csrc/wire_encode.hpp
+	$(HIPCC) --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -o $@ tools/wire_repitch_host_test.hip
 .PHONY: asan

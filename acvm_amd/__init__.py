@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "acvm_debug_lin_add", "acvm_debug_lin_plan", "acvm_debug_bundle_plan",
     "acvm_batch_import_device_wire", "acvm_batch_set_initial_witness_maps_wire",
     "acvm_batch_import_device_wire_gzip", "acvm_batch_set_initial_witness_maps_gzip", "acvm_debug_inflate_rows",
+    "acvm_batch_witness_maps_wire_packed_device", "acvm_batch_witness_maps_wire_packed", "acvm_batch_import_device_wire_packed", "acvm_debug_wire_repitch",
     "acvm_debug_gate_records", "acvm_debug_record_scratch",
 ]
 
@@ -645,6 +646,12 @@ def lib():
         L.acvm_batch_import_device_wire_gzip.argtypes = [C.c_void_p, C.POINTER(WireInDesc), C.c_void_p, C.c_void_p]
         L.acvm_batch_set_initial_witness_maps_gzip.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.acvm_debug_inflate_rows.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "acvm_batch_witness_maps_wire_packed_device"):
+        L.acvm_batch_witness_maps_wire_packed_device.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.acvm_batch_witness_maps_wire_packed.argtypes = [C.c_void_p, C.POINTER(WireDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.acvm_batch_import_device_wire_packed.argtypes = [C.c_void_p, C.POINTER(WireInDesc), C.c_void_p, C.c_uint64, C.c_void_p]
+        L.acvm_debug_wire_repitch.argtypes = [C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32,
+                                              C.c_void_p, C.c_void_p]
     if hasattr(L, "acvm_batch_outcomes_device"):
         L.acvm_batch_outcomes_device.argtypes = [C.c_void_p, C.POINTER(OutcomesDesc), C.POINTER(C.c_uint32)]
         L.acvm_batch_export_device_list.argtypes = [C.c_void_p, C.POINTER(ExportDesc), C.c_void_p, C.c_void_p, C.c_void_p]
@@ -976,6 +983,40 @@ def debug_inflate_rows(rows, out_cap, fill=0, pitch=None, lengths=None):
     _check(lib().acvm_debug_inflate_rows(buf.ctypes.data if buf.size else None, pitch, None if lens is None else lens.ctypes.data, n, out_cap,
                                          out.ctypes.data if out.size else None, out_lengths.ctypes.data, findings.ctypes.data, crcs.ctypes.data))
     return out, out_lengths, findings, crcs
+
+
+def debug_wire_repitch(rows=None, packed=None, offsets=None, pitch=None, displacement=0, capacity=None, scan_chunk=0, fill=0xA5, lengths=None):
+    """The shipped scan and repitch kernels on rows of the caller's, no handle (acvm_debug_wire_repitch); any bytes at any lengths, zero included.
+    Pack (rows: a list of bytes objects): row i lies at i * pitch (default: the longest row, at least 1) with lengths[i] (default: len(rows[i]))
+    bytes; the packed buffer has `packed` bytes (an int; default: their sum) of `fill`, at device address `displacement` mod 16; a row is
+    copied when it ends at or in front of `capacity` (default: the buffer's size); the scan runs in chunks of scan_chunk rows (0: one).
+    Returns (packed uint8 [packed], offsets uint64 [n + 1], total, n_fit).
+    Unpack (rows None): `packed` is a bytes object, `offsets` n + 1 numbers, pitch the slots' pitch. Returns (rows uint8 [n][pitch], which started
+    as `fill` everywhere; lengths uint64 [n]; findings uint32 [n], the class or 0; count; key = ~(instance << 4 | class) of the smallest)."""
+    import numpy as np
+    result = np.zeros(2, dtype=np.uint64)
+    if rows is not None:
+        rows = [bytes(r) for r in rows]
+        n = len(rows)
+        pitch = pitch or max([len(r) for r in rows] + [1])
+        lens = np.array([len(r) for r in rows] if lengths is None else lengths, dtype=np.uint64).reshape(n)
+        buf = np.zeros(n * pitch, dtype=np.uint8)
+        for i, r in enumerate(rows):
+            buf[i * pitch:i * pitch + min(len(r), pitch)] = np.frombuffer(r[:pitch], dtype=np.uint8)
+        size = int(lens.sum()) if packed is None else int(packed)
+        out = np.full(size, fill, dtype=np.uint8)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        _check(lib().acvm_debug_wire_repitch(0, n, pitch, buf.ctypes.data if buf.size else None, lens.ctypes.data if n else None, out.ctypes.data if size else None, size, displacement,
+                                             offs.ctypes.data, size if capacity is None else capacity, scan_chunk, None, result.ctypes.data))
+        return out, offs, int(result[0]), int(result[1])
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    n = offs.size - 1
+    buf = np.frombuffer(bytes(packed), dtype=np.uint8).copy()
+    out = np.full((n, pitch), fill, dtype=np.uint8)
+    lens, findings = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32)
+    _check(lib().acvm_debug_wire_repitch(1, n, pitch, out.ctypes.data if out.size else None, lens.ctypes.data, buf.ctypes.data if buf.size else None, buf.size, displacement,
+                                         offs.ctypes.data, 0, 0, findings.ctypes.data, result.ctypes.data))
+    return out, lens[:n], findings[:n], int(result[0]), int(result[1])
 
 
 def debug_select(status, select_mask, out=None, want_list=True):
@@ -1769,6 +1810,46 @@ class Batch:
         lengths = np.zeros(max(n, 1), dtype=np.uint64)
         _check(lib().acvm_batch_witness_maps_wire(self._h, C.byref(desc), out.ctypes.data, lengths.ctypes.data))
         return [out[i * pitch:i * pitch + int(lengths[i])].tobytes() for i in range(n)]
+
+    def witness_maps_wire_packed_device(self, d_ptr, capacity: int, d_offsets: int, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None, d_instances=None):
+        """witness_maps_wire_device into a PACKED buffer (acvm_batch_witness_maps_wire_packed_device): row i occupies bytes [offsets[i],
+        offsets[i + 1]) of d_ptr (16-byte aligned), no byte between rows; d_offsets: device pointer of uint64 [n + 1], always written. Rows
+        that end at or in front of `capacity` are written complete, nothing at or behind the end of the last of them. d_ptr None with capacity 0
+        is the sizing call. Returns (total, n_fit): offsets[n] and the leading rows that fit. A packed buffer of gzip members is one
+        multi-member .gz file. Nothing per instance is copied to the host."""
+        if n is None:
+            if d_instances is not None:
+                raise ValueError("a list export needs n, the list's length")
+            n = self.B - first
+        desc, _keep = wire_desc(container, first, n, witnesses, 0)
+        total, n_fit = C.c_uint64(), C.c_uint32()
+        _check(lib().acvm_batch_witness_maps_wire_packed_device(self._h, C.byref(desc), d_instances, d_ptr, capacity, d_offsets, C.byref(total), C.byref(n_fit)))
+        return total.value, n_fit.value
+
+    def witness_maps_wire_packed(self, container=WIRE_GZIP_STORED, witnesses=None, first=0, n=None, capacity=None):
+        """witness_maps_wire_packed_device into host memory (acvm_batch_witness_maps_wire_packed): (bytes, offsets) -- the packed rows and
+        uint64 [n + 1]. capacity None: a sizing call first, then every row; else the rows that end at or in front of it: len(bytes) is the end
+        of the last of them."""
+        import numpy as np
+        n = self.B - first if n is None else n
+        desc, _keep = wire_desc(container, first, n, witnesses, 0)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        total, n_fit = C.c_uint64(), C.c_uint32()
+        if capacity is None:
+            _check(lib().acvm_batch_witness_maps_wire_packed(self._h, C.byref(desc), None, 0, offsets.ctypes.data, C.byref(total), C.byref(n_fit)))
+            capacity = total.value
+        out = np.zeros(max(capacity, 1), dtype=np.uint8)
+        _check(lib().acvm_batch_witness_maps_wire_packed(self._h, C.byref(desc), out.ctypes.data, capacity, offsets.ctypes.data, C.byref(total), C.byref(n_fit)))
+        return out[:int(offsets[n_fit.value])].tobytes(), offsets
+
+    def import_device_wire_packed(self, d_ptr: int, n_bytes: int, d_offsets: int, container, pitch: int):
+        """The initial witnesses read from a PACKED buffer of serialised WitnessMaps in device memory (acvm_batch_import_device_wire_packed):
+        instance j's map is bytes [offsets[j], offsets[j + 1]) of d_ptr (16-byte aligned, n_bytes long; d_offsets: device pointer of uint64
+        [B + 1]), in any of the three containers -- what witness_maps_wire_packed_device writes. pitch: the staging pitch, a nonzero multiple of
+        16 and the longest row accepted; B * pitch bytes of device memory are taken. Offsets that are no rows of the buffer raise
+        ("wire offsets: ...") and the batch keeps the initial witnesses it had; then import_device_wire / import_device_wire_gzip run."""
+        desc = WireInDesc(container=container, pitch=pitch)
+        _check(lib().acvm_batch_import_device_wire_packed(self._h, C.byref(desc), d_ptr, n_bytes, d_offsets))
 
     def outcomes_device(self, first=0, n=None, d_status=None, d_err=None, d_opcode_index=None, select_mask=0, d_selected=None, count=True):
         """The outcomes of instances [first, first + n) as device columns (acvm_batch_outcomes_device): d_status / d_err uint8 [n], d_opcode_index uint32 [n],

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libacvm_amd.so")
-SOURCES = ["circuit.cpp", "tuning.cpp", "display.cpp", "plan.cpp", "schedule.cpp", "schedule_check.cpp", "batch.cpp", "import_plan.cpp", "record_plan.cpp", "record_out_plan.cpp", "wire_plan.cpp", "wire_in_plan.cpp", "wire_inflate_plan.cpp", "node_io_plan.cpp", "node_foreign_plan.cpp", "brillig_retry_plan.cpp", "batch_import.cpp", "batch_schedule.cpp", "batch_exact.cpp", "batch_export.cpp", "batch_messages.cpp", "foreign_plan.cpp", "batch_foreign.cpp", "kernels_foreign.hip", "probes.cpp", "kernels.hip", "kernels_import.hip", "kernels_import_mask.hip", "kernels_typed_io.hip", "kernels_records.hip", "kernels_records_masked.hip", "kernels_records_out.hip", "kernels_wire.hip", "kernels_wire_deflate.hip", "kernels_wire_in.hip", "kernels_wire_inflate.hip", "kernels_select.hip", "kernels_ops.hip", "kernels_hash.hip", "kernels_grumpkin.hip", "grumpkin_host.cpp", "kernels_brillig.hip", "kernels_brillig_resume.hip", "kernels_ecdsa.hip", "shim.cpp", "node.cpp"]
+SOURCES = ["circuit.cpp", "tuning.cpp", "display.cpp", "plan.cpp", "schedule.cpp", "schedule_check.cpp", "batch.cpp", "import_plan.cpp", "record_plan.cpp", "record_out_plan.cpp", "wire_plan.cpp", "wire_in_plan.cpp", "wire_inflate_plan.cpp", "wire_pack_plan.cpp", "node_io_plan.cpp", "node_foreign_plan.cpp", "brillig_retry_plan.cpp", "batch_import.cpp", "batch_schedule.cpp", "batch_exact.cpp", "batch_export.cpp", "batch_messages.cpp", "foreign_plan.cpp", "batch_foreign.cpp", "kernels_foreign.hip", "probes.cpp", "kernels.hip", "kernels_import.hip", "kernels_import_mask.hip", "kernels_typed_io.hip", "kernels_records.hip", "kernels_records_masked.hip", "kernels_records_out.hip", "kernels_wire.hip", "kernels_wire_deflate.hip", "kernels_wire_in.hip", "kernels_wire_inflate.hip", "kernels_wire_pack.hip", "kernels_select.hip", "kernels_ops.hip", "kernels_hash.hip", "kernels_grumpkin.hip", "grumpkin_host.cpp", "kernels_brillig.hip", "kernels_brillig_resume.hip", "kernels_ecdsa.hip", "shim.cpp", "node.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-Wall", "-Wno-unused-result", "-Wno-unused-value",
          "-ffp-contract=off"] + os.environ.get("ACVM_EXTRA_FLAGS", "").split()

@@ -265,6 +265,10 @@ struct acvm_batch {
     // grow-only device staging arena of the entry points that move data in or out (no hipMalloc / hipFree per call)
     uint8_t *d_stage = nullptr;
     size_t stage_cap = 0;
+    // acvm_batch_import_device_wire_packed: the pitched slots the packed rows are unpacked into, with their lengths and result words. Apart from
+    // d_stage, which the import that reads the slots reserves -- and may move -- for itself. Grow-only.
+    uint8_t *d_unpack = nullptr;
+    size_t unpack_cap = 0;
     uint8_t *d_fetch = nullptr;  // 512 bytes for single-value fetches (message texts): usable while d_stage serves another stream
     // acvm_batch_solve_opcode: every instance is an exact lane, slow_start[t] is its instruction pointer
     bool stepping = false;
@@ -315,6 +319,7 @@ struct acvm_batch {
             if (p) hipFree(p);
         if (d_ped_seed) hipFree(d_ped_seed);
         if (d_stage) hipFree(d_stage);
+        if (d_unpack) hipFree(d_unpack);
         if (d_fetch) hipFree(d_fetch);
         if (d_import_lists) hipFree(d_import_lists);
         if (d_missing) hipFree(d_missing);

@@ -15,7 +15,9 @@
 #include "batch_internal.hpp"
 #include "export_encode.hpp"
 #include "record_out_plan.hpp"
+#include "wire_pack_plan.hpp"
 #include "wire_plan.hpp"
+#include "wire_repitch.hpp"
 
 static const uint8_t DIGEST_G[32] = {0x23, 0x35, 0x53, 0x18, 0xdb, 0xff, 0xab, 0x2f, 0xb7, 0x72, 0x11, 0x7c, 0x57, 0x5c, 0x61, 0xb1,
                                      0x79, 0xf8, 0xc9, 0x83, 0x3c, 0x83, 0xba, 0x65, 0x59, 0x7e, 0x17, 0x3c, 0x35, 0xc4, 0xbb, 0xe3};
@@ -526,13 +528,30 @@ int acvm_batch_witness_records(acvm_batch_t *b, const acvm_record_out_desc_t *d,
 // (nothing per instance); a pre-pass makes the exact lanes' ranks from their assigned bitmap; kernels_wire.hip writes the slots. Range and list
 // are the same kernels, and both find the exact lanes through the lane map. Host form: the slots are made in the staging arena in chunks of
 // instances, one copy down per chunk, and row i's bytes [0, lengths[i]) reach the caller's buffer.
-static constexpr size_t WIRE_HOST_CHUNK_BYTES = (size_t)64 << 20;
-static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *bytes, uint64_t *lengths, bool host) {
+//
+// The packed forms (acvm_batch_witness_maps_wire_packed_device): the same slots, made chunk by chunk in the arena by the same launches; behind
+// each chunk kernels_wire_pack.hip scans its lengths into the offsets column -- the running base stays in a device word -- and packs its rows
+// into the caller's buffer. Host form: the chunk is packed into a second region of the arena and its packed range comes down in one copy,
+// straight to out + the chunk's base.
+struct WirePacked {
+    uint64_t capacity;
+    uint64_t *offsets;  // [n + 1], where the buffer is: device or host
+    uint64_t *total;
+    uint32_t *n_fit;
+};
+static WireRepitch wire_pack_call(const uint8_t *slots, uint64_t pitch, const uint64_t *lengths, uint32_t m, uint8_t *dst, const uint64_t *dst_offsets, uint64_t rebase, uint64_t capacity) {
+    return WireRepitch{m, slots, pitch, nullptr, (uint64_t)m * pitch, (uint32_t)((uintptr_t)slots & 15u), lengths, dst, 0u, dst_offsets, rebase, capacity,
+                       (uint32_t)((uintptr_t)dst & 15u), wire_repitch_units(pitch)};
+}
+static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *bytes, uint64_t *lengths, bool host, const WirePacked *packed = nullptr) {
     WirePlan plan;
     std::string refusal;
-    if (int rc = wire_plan(b ? &b->B : nullptr, b ? b->plan().producer.data() : nullptr, b ? b->plan().n_witnesses : 0u, d, d_instances != nullptr, bytes, !host, &plan, &refusal))
+    const uint32_t *live = b ? &b->B : nullptr, *producer = b ? b->plan().producer.data() : nullptr;
+    const uint32_t n_witnesses = b ? b->plan().n_witnesses : 0u;
+    if (int rc = packed ? wire_pack_plan(live, producer, n_witnesses, d, d_instances != nullptr, bytes, packed->capacity, packed->offsets, !host, &plan, &refusal)
+                        : wire_plan(live, producer, n_witnesses, d, d_instances != nullptr, bytes, !host, &plan, &refusal))
         return set_err(rc, refusal);
-    if (host && plan.n && !lengths) return set_err(ACVM_E_INVALID, "null lengths");
+    if (host && !packed && plan.n && !lengths) return set_err(ACVM_E_INVALID, "null lengths");
     if (int rc = finish_pending_and_require_solved(b)) return rc;
     if (plan.whole) {
         if (b->side()) return set_err(ACVM_E_STATE, "the batch recycles witness rows (ACVM_BATCH_REUSE_SLOTS) or solved its exact lanes in the side table: full maps are not kept; read the kept witnesses and the digest");
@@ -541,21 +560,33 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
         if (int rc = refuse_if_next_imported(b, plan.witnesses.data(), plan.n_positions, false)) return rc;
         if (int rc = reuse_check_kept(b, plan.witnesses.data(), plan.n_positions)) return rc;
     }
-    if (!plan.n) return 0;
+    if (!plan.n && !packed) return 0;
     HIPCHK(hipSetDevice(b->device));
+    if (!plan.n) {  // (the offsets column is always written)
+        if (host) packed->offsets[0] = 0u;
+        else HIPCHK(hipMemset(packed->offsets, 0, 8));
+        if (packed->total) *packed->total = 0u;
+        if (packed->n_fit) *packed->n_fit = 0u;
+        return 0;
+    }
     const bool gzip = plan.container == ACVM_WIRE_GZIP_STORED;
     const uint32_t n_slow = (uint32_t)b->slow_ids.size(), n_words = (uint32_t)plan.list_mask.size();
     const bool map_stale = !(b->d_lane_map && b->lane_map_epoch == b->slow_epoch);
     // the rows of one pass: all of them into the caller's device buffer, or what fits the chunk of the staging arena (whole blocks of 64 rows)
     uint32_t chunk = plan.n;
-    if (host) chunk = (uint32_t)std::min<uint64_t>(plan.n, std::max<uint64_t>(64, WIRE_HOST_CHUNK_BYTES / plan.pitch / 64 * 64));
-    // the arena: [witness list][rank][list mask][crc powers][slow ids][lane prefix][deflate table][crc words][host: lengths, slots]
+    const bool staged = host || packed;  // the slots are made in the arena
+    if (staged) chunk = wire_chunk_rows(plan.n, plan.pitch);
+    // the arena: [witness list][rank][list mask][crc powers][slow ids][lane prefix][deflate table][crc words][host: lengths, slots], or behind
+    // the crc words [packed: wire_pack_arena's pieces]
     size_t at = 0;
     auto carve = [&](size_t n_bytes) { const size_t begin = at; at += align256(n_bytes); return begin; };
     const size_t at_sel = carve(plan.whole ? 0 : (size_t)plan.n_positions * 4), at_rank = carve(plan.rank.size() * 4), at_mask = carve((size_t)n_words * 4);
     const size_t at_pow = carve(plan.crc_pow.size() * 4), at_ids = carve(map_stale ? (size_t)n_slow * 4 : 0), at_prefix = carve(((size_t)n_words + 1) * n_slow * 4);
     const size_t at_deflate = carve(plan.deflate.size() * 4);
-    const size_t at_crc = carve(gzip ? (size_t)chunk * 4 : 0), at_lengths = carve(host ? (size_t)chunk * 8 : 0), at_slots = carve(host ? (size_t)chunk * plan.pitch : 0);
+    const size_t at_crc = carve(gzip ? (size_t)chunk * 4 : 0);
+    const WirePackArena pack = wire_pack_arena(at, chunk, plan.pitch, host);
+    const size_t at_lengths = packed ? (size_t)pack.at_lengths : carve(host ? (size_t)chunk * 8 : 0), at_slots = packed ? (size_t)pack.at_slots : carve(host ? (size_t)chunk * plan.pitch : 0);
+    if (packed) at = (size_t)pack.end;
     if (int rc = stage_reserve(b, at)) return rc;
     hipStream_t s = b->stream;
     auto put = [&](size_t where, const std::vector<uint32_t> &v) -> hipError_t {
@@ -572,7 +603,9 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
     uint32_t *d_prefix = n_slow ? (uint32_t *)(b->d_stage + at_prefix) : nullptr;
     launch_wire_lane_prefix(s, b->d_assigned, n_slow, n_words, (const uint32_t *)(b->d_stage + at_mask), d_prefix);
     std::vector<uint8_t> slots;
-    if (host) slots.resize((size_t)chunk * plan.pitch);
+    if (host && !packed) slots.resize((size_t)chunk * plan.pitch);
+    uint64_t *d_state = (uint64_t *)(b->d_stage + pack.at_state);
+    if (packed) HIPCHK(hipMemsetAsync(d_state, 0, REPITCH_STATE_WORDS * 8, s));
     for (uint32_t done = 0; done < plan.n; done += chunk) {
         const uint32_t m = std::min(chunk, plan.n - done);
         uint32_t *d_crc = gzip ? (uint32_t *)(b->d_stage + at_crc) : nullptr;
@@ -582,18 +615,48 @@ static int export_wire(acvm_batch *b, const acvm_wire_desc_t *d, const uint32_t 
                            b->plan().n_witnesses, b->d_slot_of, b->d_producer, b->unscale.index, b->unscale.consts_plain,
                            plan.whole ? nullptr : (const uint32_t *)(b->d_stage + at_sel), plan.n_positions,
                            (const uint32_t *)(b->d_stage + at_rank), (const uint32_t *)(b->d_stage + at_mask), d_prefix, (const uint32_t *)(b->d_stage + at_pow), plan.crc_x64, d_crc,
-                           plan.container, host ? b->d_stage + at_slots : (uint8_t *)bytes, plan.pitch, host ? (uint64_t *)(b->d_stage + at_lengths) : lengths,
+                           plan.container, staged ? b->d_stage + at_slots : (uint8_t *)bytes, plan.pitch, staged ? (uint64_t *)(b->d_stage + at_lengths) : lengths,
                            plan.deflate.empty() ? nullptr : (const uint32_t *)(b->d_stage + at_deflate), plan.deflate_prefix_bits};
         launch_wire_export(s, x, plan.n_windows);
         HIPCHK(hipGetLastError());
-        if (host) {
+        if (packed && !host) {
+            launch_wire_scan(s, x.lengths, m, packed->offsets + done, packed->capacity, d_state);
+            if (bytes) launch_wire_repitch(s, wire_pack_call(x.out, plan.pitch, x.lengths, m, (uint8_t *)bytes, packed->offsets + done, 0u, packed->capacity));
+            HIPCHK(hipGetLastError());
+        } else if (packed) {
+            // the chunk's offsets come down first: they say which of its rows fit and how many bytes those are
+            uint64_t *d_offsets = (uint64_t *)(b->d_stage + pack.at_offsets), *offsets = packed->offsets + done;
+            launch_wire_scan(s, x.lengths, m, d_offsets, packed->capacity, d_state);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(offsets, d_offsets, ((size_t)m + 1) * 8, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            uint32_t fit = 0;
+            uint64_t end = 0;
+            wire_pack_fit(offsets, m, packed->capacity, &fit, &end);
+            if (bytes && fit) {
+                uint8_t *d_packed = b->d_stage + pack.at_packed;
+                launch_wire_repitch(s, wire_pack_call(x.out, plan.pitch, x.lengths, fit, d_packed, d_offsets, offsets[0], packed->capacity));
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync((uint8_t *)bytes + offsets[0], d_packed, (size_t)(offsets[fit] - offsets[0]), hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+            }
+        } else if (host) {
             HIPCHK(hipMemcpyAsync(lengths + done, x.lengths, (size_t)m * 8, hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(slots.data(), x.out, (size_t)m * plan.pitch, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
             for (uint32_t i = 0; i < m; i++) memcpy((uint8_t *)bytes + (size_t)(done + i) * plan.pitch, &slots[(size_t)i * plan.pitch], (size_t)lengths[done + i]);
         }
     }
+    uint64_t state[REPITCH_STATE_WORDS] = {0u, 0u};
+    if (packed && !host) HIPCHK(hipMemcpyAsync(state, d_state, sizeof state, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));  // (also what keeps the plan's tables and slow_ids alive for their copies)
+    if (packed) {
+        uint32_t fit = (uint32_t)state[REPITCH_STATE_FIT];
+        uint64_t total = state[REPITCH_STATE_BASE];
+        if (host) wire_pack_fit(packed->offsets, plan.n, packed->capacity, &fit, &total);
+        if (packed->total) *packed->total = total;
+        if (packed->n_fit) *packed->n_fit = fit;
+    }
     return 0;
 }
 long long acvm_batch_wire_bound(const acvm_batch_t *b, const acvm_wire_desc_t *d) try {
@@ -608,6 +671,15 @@ int acvm_batch_witness_maps_wire_device(acvm_batch_t *b, const acvm_wire_desc_t 
 } ABI_CATCH
 int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out, uint64_t *lengths) try {
     return export_wire(b, d, nullptr, out, lengths, true);
+} ABI_CATCH
+int acvm_batch_witness_maps_wire_packed_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances, void *d_bytes, uint64_t capacity, uint64_t *d_offsets,
+                                               uint64_t *total, uint32_t *n_fit) try {
+    const WirePacked packed{capacity, d_offsets, total, n_fit};
+    return export_wire(b, d, d_instances, d_bytes, nullptr, false, &packed);
+} ABI_CATCH
+int acvm_batch_witness_maps_wire_packed(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out, uint64_t capacity, uint64_t *offsets, uint64_t *total, uint32_t *n_fit) try {
+    const WirePacked packed{capacity, offsets, total, n_fit};
+    return export_wire(b, d, nullptr, out, nullptr, true, &packed);
 } ABI_CATCH
 
 uint64_t acvm_debug_export_h2d_bytes(const acvm_batch_t *b) { return b ? b->n_export_h2d_bytes : 0; }

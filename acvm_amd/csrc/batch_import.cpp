@@ -10,6 +10,7 @@
 #include "wire_in_plan.hpp"
 #include "wire_inflate.hpp"
 #include "wire_inflate_plan.hpp"
+#include "wire_repitch.hpp"
 
 static_assert(EXPORT_ENC_BE32 == ACVM_ENC_BE32 && EXPORT_ENC_MONT256_LE == ACVM_ENC_MONT256_LE && EXPORT_ENC_U8 == ACVM_ENC_U8 && EXPORT_ENC_U128 == ACVM_ENC_U128 &&
                   EXPORT_INSTANCE_MAJOR == ACVM_LAYOUT_INSTANCE_MAJOR && EXPORT_WITNESS_MAJOR == ACVM_LAYOUT_WITNESS_MAJOR && EXPORT_LAYOUT_BROADCAST == ACVM_LAYOUT_BROADCAST,
@@ -459,6 +460,112 @@ int acvm_batch_set_initial_witness_maps_gzip(acvm_batch_t *b, const uint8_t *byt
     const acvm_wire_in_desc_t d{ACVM_WIRE_GZIP_DEFLATE, pitch};
     return import_wire_gzip(b, &d, bytes, lengths, false);
 } ABI_CATCH
+
+// ---- the packed import (include/acvm_amd.h acvm_batch_import_device_wire_packed): row j is bytes [offsets[j], offsets[j + 1]) of one buffer.
+// kernels_wire_pack.hip judges the offsets -- untrusted device data -- and unpacks the rows that pass into pitched slots of the handle's own
+// (d_unpack: d_stage is the import's behind it, which may move it); nothing of the handle is written before the one wait, and any finding ends
+// the call there. Then the device import of the container runs over the slots, the rows' lengths its d_lengths.
+static const char *offsets_class_text(uint32_t cls) {
+    static const char *const text[REPITCH_CLASSES] = {"", "the row's end lies in front of its start", "the row ends beyond the buffer", "the row is longer than the pitch"};
+    return text[cls < REPITCH_CLASSES ? cls : 0];
+}
+int acvm_batch_import_device_wire_packed(acvm_batch_t *b, const acvm_wire_in_desc_t *d, const void *d_bytes, uint64_t n_bytes, const uint64_t *d_offsets) try {
+    // the descriptor and the buffer are judged by the plan of the import that will read the slots
+    const bool deflate = d && d->container == ACVM_WIRE_GZIP_DEFLATE;
+    WireInPlan plan;
+    if (deflate) {
+        WireInflatePlan inflate;
+        std::string err;
+        if (int rc = wire_inflate_plan(b ? &b->B : nullptr, b ? b->plan().initial_ids.data() : nullptr, b ? (uint32_t)b->plan().initial_ids.size() : 0u, d, d_bytes, true, 0, &inflate, &err))
+            return set_err(rc, err);
+    } else if (int rc = wire_in_plan_of(b, d, d_bytes, true, &plan)) return rc;
+    if (b->B && !d_offsets) return set_err(ACVM_E_INVALID, "null offsets");
+    if (!b->B) return deflate ? import_wire_gzip(b, d, d_bytes, nullptr, true) : import_wire_and_wait(b, plan, d_bytes, nullptr, nullptr);
+    HIPCHK(hipSetDevice(b->device));
+    // d_unpack: [result: 2 words][lengths][slots]
+    const size_t at_lengths = 256, at_slots = at_lengths + align256((size_t)b->B * 8), need = at_slots + (size_t)b->B * d->pitch;
+    if (need > b->unpack_cap) {
+        HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->d_unpack) { hipFree(b->d_unpack); b->d_unpack = nullptr; b->unpack_cap = 0; }
+        HIPCHK(hipMalloc((void **)&b->d_unpack, need));
+        b->unpack_cap = need;
+    }
+    hipStream_t s = b->stream;
+    uint64_t *d_result = (uint64_t *)b->d_unpack, *d_lengths = (uint64_t *)(b->d_unpack + at_lengths);
+    uint8_t *d_slots = b->d_unpack + at_slots;
+    HIPCHK(hipMemsetAsync(d_result, 0, 16, s));
+    launch_wire_offsets(s, d_offsets, b->B, n_bytes, d->pitch, d_lengths, nullptr, d_result);
+    launch_wire_repitch(s, WireRepitch{b->B, (const uint8_t *)d_bytes, 0u, d_offsets, n_bytes, 0u, nullptr, d_slots, d->pitch, nullptr, 0u, 0u, 0u, wire_repitch_units(d->pitch)});
+    HIPCHK(hipGetLastError());
+    uint64_t result[2] = {0u, 0u};
+    HIPCHK(hipMemcpyAsync(result, d_result, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (the one wait in front of the import)
+    if (result[0]) {
+        const uint32_t cls = wire_offsets_key_class(result[1]);
+        return set_err(ACVM_E_INVALID, "wire offsets: " + std::to_string(result[0]) + " findings, the first of them instance " + std::to_string(wire_offsets_key_instance(result[1])) +
+                                           ", class " + std::to_string(cls) + " (" + offsets_class_text(cls) + "); the handle stays as it was");
+    }
+    return deflate ? import_wire_gzip(b, d, d_slots, d_lengths, true) : import_wire_and_wait(b, plan, d_slots, d_lengths, nullptr);
+} ABI_CATCH
+
+// The shipped scan, offsets check and repitch kernel through their launchers on rows of the caller's, no handle (include/acvm_amd.h). Both
+// buffers start on the device as the caller's, so that what the kernels leave alone comes back as it went in.
+int acvm_debug_wire_repitch(uint32_t unpack, uint32_t n, uint64_t pitch, uint8_t *rows, uint64_t *lengths, uint8_t *packed, uint64_t packed_bytes, uint32_t displacement,
+                            uint64_t *offsets, uint64_t capacity, uint32_t scan_chunk, uint32_t *findings, uint64_t *result) try {
+    if (!offsets || !result || (n && !lengths) || (n && pitch && !rows) || (packed_bytes && !packed) || (unpack && n && !findings)) return set_err(ACVM_E_INVALID, "null argument");
+    if (displacement > 15u) return set_err(ACVM_E_INVALID, "displacement " + std::to_string(displacement) + " is above 15");
+    if ((unsigned __int128)n * pitch > ((unsigned __int128)1 << 36) || packed_bytes > ((uint64_t)1 << 36)) return set_err(ACVM_E_INVALID, "too large for this probe");
+    if (!unpack) {
+        if (capacity > packed_bytes) return set_err(ACVM_E_INVALID, "capacity " + std::to_string(capacity) + " is above the packed buffer's " + std::to_string(packed_bytes) + " bytes");
+        for (uint32_t i = 0; i < n; i++)
+            if (lengths[i] > pitch) return set_err(ACVM_E_INVALID, "row " + std::to_string(i) + ": length " + std::to_string(lengths[i]) + " is above the pitch " + std::to_string(pitch));
+    }
+    struct Mem {
+        void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        ~Mem() {
+            for (void *q : p)
+                if (q) hipFree(q);
+        }
+    } m;
+    const size_t row_bytes = (size_t)n * pitch;
+    const size_t sizes[5] = {row_bytes + 16, (size_t)packed_bytes + 32, ((size_t)n + 1) * 8, ((size_t)n + 1) * 8, REPITCH_STATE_WORDS * 8 + (size_t)n * 4 + 4};
+    for (int k = 0; k < 5; k++) HIPCHK(hipMalloc(&m.p[k], sizes[k]));
+    uint8_t *d_rows = (uint8_t *)m.p[0], *d_packed = (uint8_t *)m.p[1] + displacement;
+    uint64_t *d_lengths = (uint64_t *)m.p[2], *d_offsets = (uint64_t *)m.p[3], *d_state = (uint64_t *)m.p[4];
+    uint32_t *d_findings = (uint32_t *)(d_state + REPITCH_STATE_WORDS);
+    if (row_bytes) HIPCHK(hipMemcpy(d_rows, rows, row_bytes, hipMemcpyHostToDevice));
+    if (packed_bytes) HIPCHK(hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_state, 0, REPITCH_STATE_WORDS * 8));
+    if (!unpack) {
+        if (n) HIPCHK(hipMemcpy(d_lengths, lengths, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemset(d_offsets, 0, 8));
+        const uint32_t chunk = scan_chunk ? scan_chunk : std::max(n, 1u);
+        for (uint32_t done = 0; done < n; done += chunk) {
+            const uint32_t rows_now = std::min(chunk, n - done);
+            const uint8_t *from = d_rows + (size_t)done * pitch;
+            launch_wire_scan(nullptr, d_lengths + done, rows_now, d_offsets + done, capacity, d_state);
+            launch_wire_repitch(nullptr, WireRepitch{rows_now, from, pitch, nullptr, (uint64_t)rows_now * pitch, (uint32_t)((uintptr_t)from & 15u), d_lengths + done, d_packed, 0u,
+                                                     d_offsets + done, 0u, capacity, (uint32_t)((uintptr_t)d_packed & 15u), wire_repitch_units(pitch)});
+        }
+    } else {
+        HIPCHK(hipMemcpy(d_offsets, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+        launch_wire_offsets(nullptr, d_offsets, n, packed_bytes, pitch, d_lengths, d_findings, d_state);
+        launch_wire_repitch(nullptr, WireRepitch{n, d_packed, 0u, d_offsets, packed_bytes, (uint32_t)((uintptr_t)d_packed & 15u), nullptr, d_rows, pitch, nullptr, 0u, 0u,
+                                                 (uint32_t)((uintptr_t)d_rows & 15u), wire_repitch_units(pitch)});
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (row_bytes) HIPCHK(hipMemcpy(rows, d_rows, row_bytes, hipMemcpyDeviceToHost));
+    if (packed_bytes) HIPCHK(hipMemcpy(packed, d_packed, packed_bytes, hipMemcpyDeviceToHost));
+    if (!unpack) HIPCHK(hipMemcpy(offsets, d_offsets, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+    if (unpack && n) {
+        HIPCHK(hipMemcpy(lengths, d_lengths, (size_t)n * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(findings, d_findings, (size_t)n * 4, hipMemcpyDeviceToHost));
+    }
+    HIPCHK(hipMemcpy(result, d_state, REPITCH_STATE_WORDS * 8, hipMemcpyDeviceToHost));
+    return 0;
+} ABI_CATCH
+
 // The shipped inflater through its launcher on rows of the caller's, no handle (include/acvm_amd.h). The device's output starts as the caller's
 // `out`, so that what the kernel leaves alone comes back as it went in.
 int acvm_debug_inflate_rows(const uint8_t *rows, uint64_t pitch, const uint64_t *lengths, uint32_t n, uint64_t out_cap, uint8_t *out, uint64_t *out_lengths,

@@ -263,6 +263,16 @@ struct WireInflate {
     uint64_t *result;
 };
 void launch_wire_inflate(hipStream_t s, const WireInflate &x);
+// ---- kernels_wire_pack.hip (acvm_batch_witness_maps_wire_packed_device, acvm_batch_import_device_wire_packed): wire_repitch.hpp's pieces.
+// launch_wire_scan: offsets[0 .. m] of a chunk of m rows from its lengths, offsets[0] = state[REPITCH_STATE_BASE], which is left at offsets[m];
+// state[REPITCH_STATE_FIT] grows by the rows with offsets[i + 1] <= capacity. One block; state is two device words, zero before the first chunk.
+// launch_wire_repitch: the copy wire_repitch.hpp describes. launch_wire_offsets: an untrusted offsets column [n + 1] judged against n_bytes and
+// the longest row accepted -- lengths[j] (0 for a row with a finding) and findings[j] (either may be null), result[0] += the findings,
+// result[1] = max(wire_offsets_key): two device words, zero before the call.
+struct WireRepitch;
+void launch_wire_scan(hipStream_t s, const uint64_t *lengths, uint32_t m, uint64_t *offsets, uint64_t capacity, uint64_t *state);
+void launch_wire_repitch(hipStream_t s, const WireRepitch &x);
+void launch_wire_offsets(hipStream_t s, const uint64_t *offsets, uint32_t n, uint64_t n_bytes, uint64_t longest, uint64_t *lengths, uint32_t *findings, uint64_t *result);
 // ---- kernels_select.hip (acvm_batch_outcomes_device): the outcome columns of n instances -- every one Solved, then the exact lanes' records
 // {status, err, opcode index, index in the range} over them; any column may be null
 void launch_outcomes_fill(hipStream_t s, uint32_t n, uint8_t *status, uint8_t *err, uint32_t *opcode_index);

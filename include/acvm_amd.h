@@ -1030,8 +1030,9 @@ long long acvm_batch_witness_map_bytes(acvm_batch_t *b, uint32_t instance, uint8
  *     rounded up to 16: about 0.72 of the stored container's. d_lengths[i] is the member's length; a row that names no instance is a map of
  *     0 entries, 63 bytes. Descriptor, pitch and alignment rule, states, refusals, what is never written or loaded and the host-to-device
  *     traffic (the plan's tables, 1 384 bytes of code table among them) are the other containers'. The position inside a row is 64-bit.
- * Not here: a node form, an asynchronous variant (the way back in is acvm_batch_import_device_wire_gzip, below), a packed output with an offsets column instead of a pitch, adaptive codes or longer match distances, any change to
- * acvm_batch_witness_map_bytes. A body of 4 GiB or more wraps ISIZE as gzip defines it.
+ * Not here: a node form, an asynchronous variant (the way back in is acvm_batch_import_device_wire_gzip, below), adaptive codes or longer match distances, any change to
+ * acvm_batch_witness_map_bytes. A body of 4 GiB or more wraps ISIZE as gzip defines it. A packed output with an offsets column instead of a
+ * pitch is acvm_batch_witness_maps_wire_packed_device, below; these three calls are as they were.
  */
 enum { ACVM_WIRE_BINCODE = 0,        /* the bincode body alone */
        ACVM_WIRE_GZIP_STORED = 1,    /* one gzip member around it, stored blocks */
@@ -1094,8 +1095,8 @@ int acvm_batch_witness_maps_wire(acvm_batch_t *b, const acvm_wire_desc_t *d, uin
  * ACVM_WIRE_BINCODE slots and the device path runs.
  * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant (compressed deflate is inflated on the device by
  * acvm_batch_import_device_wire_gzip, below; these two calls are as they were), keys
- * outside the handle's initial id set (the reference's ACVM::new would take them; here the plan is keyed by the initial ids), a per-row offset
- * column instead of a pitch.
+ * outside the handle's initial id set (the reference's ACVM::new would take them; here the plan is keyed by the initial ids). A per-row offset
+ * column instead of a pitch is acvm_batch_import_device_wire_packed, below.
  */
 typedef struct {
     uint32_t container;   /* ACVM_WIRE_BINCODE or ACVM_WIRE_GZIP_STORED: what every slot holds */
@@ -1148,7 +1149,8 @@ int acvm_batch_set_initial_witness_maps_wire(acvm_batch_t *b, const uint8_t *byt
  * maps. out ([n][out_cap], out_cap a multiple of 4) goes up as it is and comes back with row i's bytes in front, so what the kernel leaves
  * alone is seen to be left alone; out_lengths[i] the bytes stored, findings[2 i], [2 i + 1] the class (0: none) and the block count, crcs
  * (may be NULL) the CRC-32 of the bytes stored. lengths may be NULL (pitch).
- * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant, raw-deflate or zlib wrappers, multi-member files,
+ * Not here: a node form, an acvm_batch_solve_then_import form, an asynchronous variant, raw-deflate or zlib wrappers, multi-member files
+ * within one row (a packed buffer of one member per row is acvm_batch_import_device_wire_packed, below),
  * bodies outside canonical shape on the device, parallel decoding within one row.
  */
 int acvm_batch_import_device_wire_gzip(acvm_batch_t *b, const acvm_wire_in_desc_t *d /* container must be ACVM_WIRE_GZIP_DEFLATE */,
@@ -1157,6 +1159,59 @@ int acvm_batch_set_initial_witness_maps_gzip(acvm_batch_t *b, const uint8_t *byt
                                              const uint64_t *lengths /* host [B], required */);
 int acvm_debug_inflate_rows(const uint8_t *rows /* host */, uint64_t pitch, const uint64_t *lengths, uint32_t n, uint64_t out_cap,
                             uint8_t *out /* host [n][out_cap] */, uint64_t *out_lengths, uint32_t *findings /* [n][2]: class, block */, uint32_t *crcs);
+/*
+ * PACKED wire buffers: an offsets column in place of the pitch. Row i occupies bytes [offsets[i], offsets[i + 1]) of one buffer, offsets[0] = 0,
+ * no byte between rows -- memory in proportion to what is written, not to acvm_batch_wire_bound. A packed buffer of gzip members is, byte for
+ * byte, one multi-member .gz file (gzip.decompress reads it in one call).
+ * acvm_batch_witness_maps_wire_packed_device: the export. The descriptor is acvm_wire_desc_t with pitch == 0; all three containers, range and
+ * list form; the rows are byte for byte those of acvm_batch_witness_maps_wire_device, whose kernels make them in the handle's staging arena in
+ * chunks -- whole blocks of 64 rows, at most 64 MiB of slots -- behind which each chunk's lengths are scanned into the offsets (the running
+ * base stays in a device word) and its rows packed into d_bytes. Device memory taken is the chunk and the tables, never n * bound.
+ *   - What is written: d_offsets[0 .. n], always; *total = offsets[n]; *n_fit = the leading rows with offsets[i + 1] <= capacity; rows below
+ *     n_fit complete.
+ *   - What is never written or loaded: a byte of d_bytes at or behind offsets[n_fit], a byte in front of d_bytes; no byte of d_bytes is loaded,
+ *     none is read-modify-written, and rows that share a dword each store their own bytes.
+ *   - d_bytes == NULL with capacity == 0 is the sizing call: the offsets, total, nothing else. It costs a full encode -- for
+ *     ACVM_WIRE_GZIP_DEFLATE a member's length is known only once it is made; the other containers run the same launches. A caller whose
+ *     buffer was too small continues with the list form on the remaining instances.
+ *   - States, refusals and host-to-device traffic: those of acvm_batch_witness_maps_wire_device; nothing per instance crosses the bus. Also
+ *     refused with ACVM_E_INVALID, nothing enqueued: a descriptor pitch other than 0; null offsets; a null buffer with a capacity.
+ *   - acvm_batch_witness_maps_wire_packed: the same into host memory, range form; out needs no alignment (NULL with capacity 0: sizing). Per
+ *     chunk the rows are packed on the device and the chunk's packed range comes down in one copy straight to out + its base: no slot bytes
+ *     behind a row's length cross the bus and no row is moved on the host.
+ * acvm_batch_import_device_wire_packed: the way back in. d->container: any of the three (ACVM_WIRE_GZIP_DEFLATE takes
+ * acvm_batch_import_device_wire_gzip's path, the others acvm_batch_import_device_wire's); d->pitch: the staging pitch, a nonzero multiple of 16
+ * and so the longest row accepted. The call needs B * pitch bytes of staging in device memory, which the handle keeps.
+ *   - The offsets are untrusted device data. They are judged and the rows unpacked into the staging slots first, which writes nothing of the
+ *     handle; no load touches a byte outside [d_bytes, d_bytes + n_bytes) -- a buffer may end in mid-dword -- and there is one host
+ *     synchronisation. Findings, a class space of their own:
+ *       1  offsets[j + 1] < offsets[j]
+ *       2  offsets[j + 1] > n_bytes
+ *       3  a row longer than the pitch
+ *     A row with a finding is not copied. Any finding is ACVM_E_INVALID: the message ("wire offsets: ...") gives the number of findings and the
+ *     smallest (instance, class), and the handle stays AS IT WAS -- a previous import still solves.
+ *   - Then the device import of the container runs over the slots with the rows' lengths as its d_lengths; its findings, its messages and its
+ *     "left without initial witnesses" rule are unchanged, and on success the handle is bit for bit what the pitched import leaves for the
+ *     same rows (acvm_debug_import_state).
+ *   - Refused on the host, nothing enqueued, the handle as it was: what the pitched import of the container refuses; null offsets with B > 0.
+ * acvm_debug_wire_repitch runs the shipped scan and repitch kernels through their launchers on host rows of the caller's, any bytes at any
+ * lengths, zero included; no handle. unpack == 0: rows ([n][pitch], any pitch) and lengths give packed and offsets [n + 1], the scan run in
+ * chunks of scan_chunk rows (0: one chunk), a row copied when it ends at or in front of capacity (<= packed_bytes); result = {total, n_fit}.
+ * unpack != 0: packed and offsets give rows, lengths (0 for a row with a finding) and findings [n] (the class, 0: none); result = {the count
+ * of findings, the key of the smallest (instance, class): ~(instance << 4 | class)}. displacement 0 .. 15: the packed buffer's device address
+ * mod 16. Both buffers go up as given and come back whole, so that what the kernels leave alone is seen to be left alone.
+ * Not here: a host form of the packed import, a node form, an acvm_batch_solve_then_import form, an asynchronous variant.
+ */
+int acvm_batch_witness_maps_wire_packed_device(acvm_batch_t *b, const acvm_wire_desc_t *d, const uint32_t *d_instances /* DEVICE or NULL */,
+                                               void *d_bytes /* DEVICE, 16-byte aligned, may be NULL */, uint64_t capacity, uint64_t *d_offsets /* DEVICE [n + 1] */,
+                                               uint64_t *total, uint32_t *n_fit /* either may be NULL */);
+int acvm_batch_witness_maps_wire_packed(acvm_batch_t *b, const acvm_wire_desc_t *d, uint8_t *out /* host, may be NULL */, uint64_t capacity,
+                                        uint64_t *offsets /* host [n + 1] */, uint64_t *total, uint32_t *n_fit);
+int acvm_batch_import_device_wire_packed(acvm_batch_t *b, const acvm_wire_in_desc_t *d, const void *d_bytes /* DEVICE, 16-byte aligned */,
+                                         uint64_t n_bytes, const uint64_t *d_offsets /* DEVICE [B + 1] */);
+int acvm_debug_wire_repitch(uint32_t unpack, uint32_t n, uint64_t pitch, uint8_t *rows /* host [n][pitch] */, uint64_t *lengths /* [n] */,
+                            uint8_t *packed /* host [packed_bytes] */, uint64_t packed_bytes, uint32_t displacement, uint64_t *offsets /* [n + 1] */,
+                            uint64_t capacity, uint32_t scan_chunk, uint32_t *findings /* [n], unpack only */, uint64_t *result /* [2] */);
 
 
 /*
